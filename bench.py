@@ -12,35 +12,38 @@ phase[n] = (uint32)(n << 2) (the reference bench's ramp, cordic_tb.cpp:138),
 x = 2^31-1, y = 0.  Multi-GPU: independent shards by global sample index,
 no data-path collective (weak scaling), driven through the C++ cordic_group
 layer of the C ABI.  `value` is always compute only; with
-more than one GPU the line ALSO carries, behind the timed region and never
-inside `value`, the final gather onto one GPU (8e (ii)): `gather.rccl` =
+more than one GPU and --full the line ALSO carries, behind the timed region
+and never inside `value`, the final gather onto one GPU (8e (ii)): `gather.rccl` =
 ncclSend / ncclRecv of the C++ layer between the ranks, `gather.peer` = peer
 copies of the one-process layout, and `scale` = compute only next to
 compute + gather.  A gather that cannot run is a labelled `gather.*.error`;
 nothing behind the timed region can lose the main line (LineGuard).
 
 `--gpus N` always means N GPUs: started by torch.distributed.run the world
-size must equal N; started plainly with N > 1 the script re-executes itself
-under torch.distributed.run with N ranks (one GPU each); fewer than N visible
-GPUs is an error, never a silent 1-GPU run.  `--single-process` instead
+size must equal N; started plainly with N > 1 the script runs itself under
+torch.distributed.run with N ranks (one GPU each, a child process); fewer
+than N visible GPUs is an error, never a silent 1-GPU run.  `--single-process` instead
 drives all N devices from one host process (cordic_group, no process group).
 
 Rank 0 prints ONE JSON line of at most 4 KB (tools/bench_line.py: the contract
 keys, `roofline`, `cpu_baseline`, `digest_check`, `full_recurrence`, `scale`;
 numbers and short tokens only) and writes everything else it collected to
---detail (default ./bench_detail.json).  The default command measures: the K
-timed steps, the oracle's digest of EVERY output, the full-recurrence kernel,
-one second of sustained running (power / clock), three rocprofv3 counter
-passes (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU) and the CPU baseline -- about
-half a minute.  `--full` adds what round 5's default line carried: copy probes
-on the run's own arrays, the other BASELINE configurations at their sizes, the
-host-array entry points and the small-batch sweep (minutes; all of it lands in
-the detail file).  The helpers that do not decide the metric live in
-tools/bench_*.py.
+--detail (default ./bench_detail.json).  The default command does only what
+the headline needs: it sets up, warms up, times the K steps (with their HIP
+events: `roofline`), writes the last step's outputs when --dump-outputs is
+given, and prints the line.  `--full` adds everything else: the oracle's digest
+of EVERY output, the full-recurrence kernel, two seconds of sustained running
+(power / clock), three rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE,
+SQ_INSTS_VALU), the CPU baseline, copy probes on the run's own arrays, with
+more than one GPU the gather and the one-process run, and (cfg2, one GPU) the
+other BASELINE configurations at their sizes, the host-array entry points and
+the small-batch sweep (minutes; all of it lands in the detail file).  The
+helpers that do not decide the metric live in tools/bench_*.py.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import threading
 import time
@@ -56,8 +59,9 @@ import torch  # noqa: E402
 
 import build_stamp  # noqa: E402
 from bench_common import (HBM_PEAK_GBS, MODE, RW, SHARE_GPU, WORKLOADS,  # noqa: E402
-                          RawWords, claim_stdout, coll_device, dist_init, emit,
-                          ranks_on_this_node, spot_indices, usable_cpus)
+                          RawWords, claim_stdout, coll_device, dist_init,
+                          dump_outputs, dump_windows, emit, ranks_on_this_node,
+                          spot_indices, usable_cpus)
 from bench_line import publish  # noqa: E402
 from bench_oracle import (cpu_baseline, oracle_digest_leg,  # noqa: E402
                           reduce_digest_legs)
@@ -72,7 +76,7 @@ GATHER_CHUNKS = 8           # pieces per shard behind the compute
 
 def visible_gpus():
     """HIP devices this process can see, through the C ABI (no torch.cuda
-    initialisation in a parent that is about to exec)."""
+    initialisation in a parent that only starts the ranks)."""
     import cordic_amd as ca
     n = ca.device_count()
     return n if n > 0 else 0
@@ -85,7 +89,7 @@ def resolve_launch(args):
       "single-process"  --single-process: one host process, --gpus devices,
                         the C++ cordic_group layer, no process group
       "spawn"           plain `python bench.py --gpus N` with N > 1 (or
-                        --spawn): re-exec under torch.distributed.run with N
+                        --spawn): a child torch.distributed.run with N
                         ranks, one GPU each
       "direct"          N = 1, this process"""
     need = args.gpus
@@ -114,8 +118,9 @@ def resolve_launch(args):
 
 
 def respawn(args):
-    """Replace this process by `python -m torch.distributed.run` with --gpus
-    ranks running this same command line."""
+    """Run `python -m torch.distributed.run` with --gpus ranks running this
+    same command line as a child process and leave with its status (not an
+    exec: this process has already opened the GPU to count the devices)."""
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -128,7 +133,8 @@ def respawn(args):
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get(
                    "HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    r = subprocess.run(cmd, env=env)
+    sys.exit(r.returncode)
 
 
 class LineGuard:
@@ -363,9 +369,9 @@ def single_process_block(args, ndev, expect):
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(ndev),
            "--single-process", "--workload", args.workload, "--steps",
            str(args.steps), "--warmup", str(args.warmup), "--log2-samples",
-           str(args.log2_samples), "--input", args.input,
-           "--no-cpu-baseline", "--no-pmc", "--no-power", "--no-full-digest",
-           "--detail", dpath]
+           str(args.log2_samples), "--input", args.input, "--full",
+           "--no-other-paths", "--no-copy-probe", "--no-cpu-baseline",
+           "--no-pmc", "--no-power", "--no-full-digest", "--detail", dpath]
     for flag, on in (("--no-seed", args.no_seed), ("--generic", args.generic),
                      ("--static-chunks", args.static_chunks)):
         if on:
@@ -516,7 +522,8 @@ def run_group(args, w, launch):
             probes.append(copy_probe(ptrs, n, RW[kind]))
 
     lap("copy_probe")
-    sampler = start_power(devices[0], rank == 0 and not args.no_power)
+    sampler = start_power(devices[0], rank == 0 and args.full
+                          and not args.no_power)
 
     # W untimed warm-up steps, the last of them BEHIND the barrier: the ranks'
     # rendezvous (an RCCL kernel plus host round trips) leaves the device idle
@@ -545,6 +552,15 @@ def run_group(args, w, launch):
     barrier()
     elapsed = time.perf_counter() - t0
     lap("timed_region")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step wrote, before anything else runs on grp
+        lo, cnt = grp.range(n_total, first)
+        win = dump_windows(cnt)
+        names = ("mag", "phase") if kind == "r2p" else ("x", "y")
+        dump_outputs(args.dump_outputs, lo, win, {
+            nm: np.concatenate([grp.read(0, arr, o, c) for o, c in win])
+            for nm, arr in zip(names, (2, 3))})
+        lap("dump_outputs")
     power = finish_power(sampler, lambda: step(grp), grp.sync, t0, elapsed,
                          args.steps, float(nlocal) * n,
                          seconds=2.0 if args.full else 1.0)
@@ -561,87 +577,89 @@ def run_group(args, w, launch):
     kern_total_ms, per_shard_ms = grp.elapsed(0, len(marks) - 1)
     kern_avg_s = kern_total_ms / args.steps / 1e3
 
-    # ---- after the timed region: correctness of what was just computed
-    digest = local_digest = grp.digest(n_total)
-    if dist is not None:
-        d = torch.tensor([digest - (1 << 64) if digest >= 1 << 63 else digest],
-                         dtype=torch.int64, device=coll_device(dev))
-        dist.all_reduce(d, op=dist.ReduceOp.SUM)     # digests of shards add
-        digest = int(d.item()) & 0xFFFFFFFFFFFFFFFF
-
+    # ---- after the timed region (--full): correctness of what was just
+    # computed
+    digest = oracle_sum = leg = None
     check = digest_check = None
-    ocfg = O.config_cli(MODE[m], iw, ow, xtra, pw, ns)
-    # EVERY output of EVERY rank against the oracle: each rank pushes its own
-    # shards' samples through the scalar oracle (its share of the node's host
-    # cores) and compares digests; the verdicts are reduced
-    lo = grp.range(n_total, first)[0]
-    cnt_all = sum(grp.range(n_total, first + sh)[1] for sh in range(nlocal))
-    leg = oracle_digest_leg(args, w, ocfg, lo, cnt_all, x0, y0,
-                            threads=max(1, usable_cpus()
-                                        // ranks_on_this_node(world)))
-    legs = None
-    oracle_sum = None
-    if leg is not None:
-        legs = reduce_digest_legs(dist, dev, world,
-                                  local_digest == leg["digest"], leg)
-        oracle_sum = legs[2]
-    if rank == 0:
-        start0 = grp.range(n_total, first)[0]
+    if args.full:
+        digest = local_digest = grp.digest(n_total)
+        if dist is not None:
+            d = torch.tensor([digest - (1 << 64) if digest >= 1 << 63 else digest],
+                             dtype=torch.int64, device=coll_device(dev))
+            dist.all_reduce(d, op=dist.ReduceOp.SUM)     # digests of shards add
+            digest = int(d.item()) & 0xFFFFFFFFFFFFFFFF
 
-        def oracle(off, cnt):
-            if kind == "r2p":
-                xi = grp.read(0, 0, off, cnt)
-                yi = grp.read(0, 1, off, cnt)
-                ra, rb = O.topolar(ocfg, xi, yi)
-                return ra, rb.view(np.int32)
-            if kind == "p2r":
-                ph = grp.read(0, 0, off, cnt).view(np.uint32)
-            else:
-                idx = np.arange(cnt, dtype=np.uint64) + np.uint64(start0 + off)
-                ph = ((idx * np.uint64(0x01234567))
-                      & np.uint64(0xffffffff)).astype(np.uint32)
-            return O.rotate(ocfg, x0, y0, ph)
-        check = True
-        for off, cnt in spot_indices(n):
-            ra, rb = oracle(off, cnt)
-            check = check and bool(
-                np.array_equal(grp.read(0, 2, off, cnt), ra)
-                and np.array_equal(grp.read(0, 3, off, cnt), rb))
-        # the device digest kernel against the oracle's outputs over the same
-        # leading 2^20 samples of shard 0
-        cnt = min(n, 1 << 20)
-        ra, rb = oracle(0, cnt)
-        want = (cpu_digest(ra, start0)
-                + cpu_digest(rb, start0 + (1 << 40))) % (1 << 64)
-        with torch.cuda.device(devices[0]):
-            dd = torch.zeros(1, dtype=torch.int64, device="cuda")
-            ca.digest_u32(ptrs[2], start0, dd, n=cnt)
-            ca.digest_u32(ptrs[3], start0 + (1 << 40), dd, n=cnt)
-            torch.cuda.synchronize()
-            got = int(dd.cpu().numpy().view(np.uint64)[0])
-        digest_check = {"samples": cnt, "device": "%016x" % got,
-                        "oracle": "%016x" % want, "equal": got == want}
-        if legs is not None:
-            all_ok, samples_all, _, slowest = legs
-            digest_check = {
-                "samples": samples_all, "device": "%016x" % digest,
-                "oracle": "%016x" % oracle_sum,
-                "equal": all_ok and digest == oracle_sum,
-                "oracle_seconds": slowest, "oracle_threads": leg["cores"],
-                "ranks": world,
-                "what": "position-aware 64-bit digest of ALL outputs of ALL "
-                        "ranks: each rank's device digest over what its timed "
-                        "kernels wrote vs oracle/cordic_oracle.c: orc_digest of "
-                        "its own shards (every sample through the scalar "
-                        "oracle); verdicts AND digests reduced over the ranks",
-                "leading_2^20_also_equal": got == want}
-            check = check and digest_check["equal"]
+        ocfg = O.config_cli(MODE[m], iw, ow, xtra, pw, ns)
+        # EVERY output of EVERY rank against the oracle: each rank pushes its own
+        # shards' samples through the scalar oracle (its share of the node's host
+        # cores) and compares digests; the verdicts are reduced
+        lo = grp.range(n_total, first)[0]
+        cnt_all = sum(grp.range(n_total, first + sh)[1] for sh in range(nlocal))
+        leg = oracle_digest_leg(args, w, ocfg, lo, cnt_all, x0, y0,
+                                threads=max(1, usable_cpus()
+                                            // ranks_on_this_node(world)))
+        legs = None
+        if leg is not None:
+            legs = reduce_digest_legs(dist, dev, world,
+                                      local_digest == leg["digest"], leg)
+            oracle_sum = legs[2]
+        if rank == 0:
+            start0 = grp.range(n_total, first)[0]
+
+            def oracle(off, cnt):
+                if kind == "r2p":
+                    xi = grp.read(0, 0, off, cnt)
+                    yi = grp.read(0, 1, off, cnt)
+                    ra, rb = O.topolar(ocfg, xi, yi)
+                    return ra, rb.view(np.int32)
+                if kind == "p2r":
+                    ph = grp.read(0, 0, off, cnt).view(np.uint32)
+                else:
+                    idx = np.arange(cnt, dtype=np.uint64) + np.uint64(start0 + off)
+                    ph = ((idx * np.uint64(0x01234567))
+                          & np.uint64(0xffffffff)).astype(np.uint32)
+                return O.rotate(ocfg, x0, y0, ph)
+            check = True
+            for off, cnt in spot_indices(n):
+                ra, rb = oracle(off, cnt)
+                check = check and bool(
+                    np.array_equal(grp.read(0, 2, off, cnt), ra)
+                    and np.array_equal(grp.read(0, 3, off, cnt), rb))
+            # the device digest kernel against the oracle's outputs over the same
+            # leading 2^20 samples of shard 0
+            cnt = min(n, 1 << 20)
+            ra, rb = oracle(0, cnt)
+            want = (cpu_digest(ra, start0)
+                    + cpu_digest(rb, start0 + (1 << 40))) % (1 << 64)
+            with torch.cuda.device(devices[0]):
+                dd = torch.zeros(1, dtype=torch.int64, device="cuda")
+                ca.digest_u32(ptrs[2], start0, dd, n=cnt)
+                ca.digest_u32(ptrs[3], start0 + (1 << 40), dd, n=cnt)
+                torch.cuda.synchronize()
+                got = int(dd.cpu().numpy().view(np.uint64)[0])
+            digest_check = {"samples": cnt, "device": "%016x" % got,
+                            "oracle": "%016x" % want, "equal": got == want}
+            if legs is not None:
+                all_ok, samples_all, _, slowest = legs
+                digest_check = {
+                    "samples": samples_all, "device": "%016x" % digest,
+                    "oracle": "%016x" % oracle_sum,
+                    "equal": all_ok and digest == oracle_sum,
+                    "oracle_seconds": slowest, "oracle_threads": leg["cores"],
+                    "ranks": world,
+                    "what": "position-aware 64-bit digest of ALL outputs of ALL "
+                            "ranks: each rank's device digest over what its timed "
+                            "kernels wrote vs oracle/cordic_oracle.c: orc_digest of "
+                            "its own shards (every sample through the scalar "
+                            "oracle); verdicts AND digests reduced over the ranks",
+                    "leading_2^20_also_equal": got == want}
+                check = check and digest_check["equal"]
 
     lap("oracle_digest")
     # ---- constant-vector feeds: also time the full-recurrence kernel (every
     # sample runs all micro-rotations) so both numbers are on record
     full = None
-    if seeded:
+    if seeded and args.full:
         grp2 = ca.Group(cfg.with_flags(cfg.flags | ca.FLAG_NO_SEED), devices=devices,
                         first_shard=first, total_shards=total)
         for sh in range(nlocal):        # same inputs, bit for bit
@@ -797,15 +815,16 @@ def run_group(args, w, launch):
             "from_profile": from_profile(
                 args.workload + ("_noseed" if args.no_seed else "")),
             "bit_exact_vs_oracle": check,
-            "digest": "%016x" % digest,
             "digest_check": digest_check,
         }
+        if digest is not None:
+            out["digest"] = "%016x" % digest
         if full is not None:
             out["full_recurrence_kernel"] = full
         guard.line = out
 
-    # ---- the final gather onto one GPU, ALWAYS with more
-    # than one GPU (and with --gather on one), never inside `value`
+    # ---- the final gather onto one GPU, with more than one
+    # GPU and --full (and with --gather), never inside `value`
     compute_ms = elapsed / args.steps * 1e3
     gather = None
 
@@ -818,7 +837,7 @@ def run_group(args, w, launch):
             out["launch"]["%s_error" % phase] = (
                 "timed out after %.0f s" % limit_s)
     guard.on_timeout = timed_out
-    if (total > 1 or args.gather) and not args.no_gather:
+    if (args.gather or (total > 1 and args.full)) and not args.no_gather:
         gather = {}
         if launch == "single-process":
             guard.arm("peer", args.gather_limit)
@@ -843,8 +862,8 @@ def run_group(args, w, launch):
 
     single = None
     lap("gather")
-    if (launch == "torchrun" and not args.no_single_process_check
-            and (world > 1 or os.environ.get("BENCH_FORCE_SINGLE_CHECK"))):
+    if (launch == "torchrun" and args.full
+            and not args.no_single_process_check and (world > 1 or os.environ.get("BENCH_FORCE_SINGLE_CHECK"))):
         # the C++ one-process layer on the same GPUs, for the record (and the
         # peer-copy gather): rank 0 drives every device while the other ranks
         # wait on the HOST (a gloo barrier: no GPU kernel spins meanwhile)
@@ -887,7 +906,7 @@ def run_group(args, w, launch):
         lap("single_process_check")
         roof = out["roofline"]
         pm = None
-        if not args.no_pmc and total == 1:
+        if args.full and not args.no_pmc and total == 1:
             try:
                 pm = measure_pmc(args)
             except Exception as e:            # never lose the main line
@@ -899,12 +918,14 @@ def run_group(args, w, launch):
                 roof["traffic_over_algorithmic"] = roof["traffic"] / (
                     w["bytes"] * n)
             lap("pmc_passes")
-        add_valu(roof, n / kern_avg_s, pm, power, out["from_profile"],
-                 args.workload)
-        if not args.no_cpu_baseline and total == 1:
+        if args.full:
+            add_valu(roof, n / kern_avg_s, pm, power, out["from_profile"],
+                     args.workload)
+        if args.full and not args.no_cpu_baseline and total == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload, leg=leg)
             lap("cpu_baseline")
-        if total == 1 and args.workload == "cfg2" and args.full:
+        if (total == 1 and args.workload == "cfg2" and args.full
+                and not args.no_other_paths):
             import bench_paths
             torch.cuda.empty_cache()
             out["other_paths"] = bench_paths.other_paths(args)
@@ -955,12 +976,21 @@ def main():
                     help="go through the self-launch path (re-exec under "
                     "torch.distributed.run) even for --gpus 1")
     ap.add_argument("--full", action="store_true",
-                    help="everything round 5's default command ran: copy "
-                    "probes before and after the timed region, two seconds of "
-                    "sustained running, and (cfg2, one GPU) the other BASELINE "
+                    help="everything beside the timed steps: the oracle digest "
+                    "of every output and the spot checks, the full-recurrence "
+                    "kernel, two seconds of sustained running (power / clock), "
+                    "the rocprofv3 counter passes, the VALU model, the CPU "
+                    "baseline, copy probes before and after the timed region, "
+                    "with more than one GPU the gather and the one-process "
+                    "run, and (cfg2, one GPU) the other BASELINE "
                     "configurations at their sizes, the host-array entry points "
-                    "and the small-batch sweep; minutes instead of half a "
-                    "minute, all of it in the detail file")
+                    "and the small-batch sweep; minutes, all of it in the "
+                    "detail file.  The --no-* switches below leave parts out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last of them "
+                    "computed: DIR/<output>.npy (float64) for a fixed, seeded "
+                    "sample of 2^20 samples of shard 0 (all of it when "
+                    "smaller) and DIR/index.npy, their global sample indices")
     ap.add_argument("--detail", default="bench_detail.json",
                     help="where the full record goes (the printed line is a "
                     "<= 4 KB selection of it: tools/bench_line.py); '-' or "
@@ -970,8 +1000,8 @@ def main():
                     "run's own arrays, before and after the timed region "
                     "(roofline.copy_frac in the detail file; part of --full)")
     ap.add_argument("--no-other-paths", action="store_true",
-                    help="(accepted for round 1-5 command lines: the other "
-                    "entry points are measured only with --full)")
+                    help="with --full: leave out the other entry points "
+                    "(other_paths of the detail file)")
     ap.add_argument("--host-paths-only", action="store_true",
                     help="print only the host-array entry points' rates "
                     "(other_paths.host_arrays of the default line)")
@@ -1050,8 +1080,6 @@ def main():
         args.copy_probe = True
     if args.no_copy_probe:
         args.copy_probe = False
-    if args.no_other_paths and args.full:
-        raise SystemExit("bench.py: --full and --no-other-paths disagree")
     if args.ramp_shift >= 0:
         w0 = WORKLOADS[args.workload]
         w0["shift"] = args.ramp_shift

@@ -88,14 +88,16 @@ def test_launch_decisions_and_respawn_command(monkeypatch):
 
     seen = {}
 
-    def fake_exec(prog, argv, env):
-        seen.update(prog=prog, argv=argv, env=env)
-        raise RuntimeError("exec")
-    monkeypatch.setattr(bench.os, "execvpe", fake_exec)
+    def fake_run(argv, env):
+        seen.update(prog=argv[0], argv=argv, env=env)
+        return subprocess.CompletedProcess(argv, 3)
+    # a child process, never an exec of this one (it has opened the GPU)
+    monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20",
                                       "--warmup", "5", "--spawn"])
-    with pytest.raises(RuntimeError, match="exec"):
+    with pytest.raises(SystemExit) as ex:
         bench.respawn(ns(gpus=8))
+    assert ex.value.code == 3           # the ranks' status is the command's
     a = seen["argv"]
     assert a[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in a and a[a.index("--nproc-per-node") + 1] == "8"
@@ -210,25 +212,20 @@ def test_the_detail_file_is_written_atomically_and_never_over_devnull(tmp_path):
     os.unlink(got)
 
 
-SMALL = ["--steps", "5", "--warmup", "1", "--log2-samples", "22",
+SMALL = ["--steps", "5", "--warmup", "1", "--log2-samples", "22", "--full",
          "--no-cpu-baseline", "--no-other-paths", "--no-pmc", "--no-power"]
 
 
-@pytest.mark.gpu
-def test_the_drivers_default_command_prints_one_small_line_quickly(tmp_path):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` exactly as the driver
-    runs it (cwd = the repo, no other flag): ONE line of at most 4 KB with
-    `roofline` (traffic measured by this run's counter passes) and
-    `cpu_baseline`, the full record in ./bench_detail.json, and all of it
-    inside a minute (round 5: 20.7 KB after 116 s, lost)."""
-    import shutil
+def _driver_command(extra):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` + extra, cwd = the
+    repo -> (wall seconds, the line, the detail record)"""
     import time
     e = {k: v for k, v in os.environ.items()
          if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CORDIC_SEED_MIN_SAMPLES")}
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "20",
-                        "--warmup", "5"], cwd=ROOT, env=e, text=True, timeout=600,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+                        "--warmup", "5"] + extra, cwd=ROOT, env=e, text=True,
+                       timeout=600, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     wall = time.perf_counter() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     rows = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -241,13 +238,36 @@ def test_the_drivers_default_command_prints_one_small_line_quickly(tmp_path):
     assert d["value"] == pytest.approx(line["value"], rel=1e-5)
     assert line["metric"].startswith("Msamples/sec (sin+cos pairs) at 16-stage/32-bit")
     assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5
+    assert line["ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-5)
     assert line["config"]["samples_per_gpu"] == 1 << 30
-    assert line["digest_check"] == {"samples": 1 << 30, "equal": True}
     roof = line["roofline"]
     assert roof["bound"] in ("hbm", "valu") and roof["peak"] == 8000.0
     assert roof["placement"] == "on"
-    assert roof["limiter"] in ("power", "hbm", "valu", "latency")
     assert 0.3 < roof["frac"] < 1.0
+    return wall, line, d
+
+
+@pytest.mark.gpu
+def test_the_drivers_default_command_prints_one_small_line_quickly(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` exactly as the driver
+    runs it (cwd = the repo, no other flag): ONE line of at most 4 KB, the
+    record in ./bench_detail.json, inside a minute (round 5: 20.7 KB after
+    116 s, lost) -- and nothing but the timed steps: no oracle, counter,
+    power or CPU leg.  The same command with --full (the other paths left
+    out): `roofline` with traffic measured by this run's counter passes,
+    `cpu_baseline`, the oracle's digest of every output, also inside a
+    minute."""
+    import shutil
+    _, line, d = _driver_command([])
+    for k in ("digest_check", "bit_exact_vs_oracle", "cpu_baseline",
+              "full_recurrence"):
+        assert k not in line, k
+    assert "pmc" not in d["roofline"] and "power" not in d["roofline"]
+    assert "other_paths" not in d
+    _, line, d = _driver_command(["--full", "--no-other-paths"])
+    assert line["digest_check"] == {"samples": 1 << 30, "equal": True}
+    roof = line["roofline"]
+    assert roof["limiter"] in ("power", "hbm", "valu", "latency")
     if shutil.which("rocprofv3"):
         assert 0.99 < roof["traffic_over_algorithmic"] < 1.02
         assert roof["traffic"] == pytest.approx(
@@ -262,7 +282,57 @@ def test_the_drivers_default_command_prints_one_small_line_quickly(tmp_path):
     assert d["full_recurrence_kernel"]["outputs_identical_to_seeded_kernel"] is True
     # where the time of the command went, phase by phase (detail file)
     assert sum(d["phases_s"].values()) <= d["wall_s"] + 0.5
-    assert "other_paths" not in d               # that is --full
+    assert "other_paths" not in d               # left out: --no-other-paths
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_what_the_timed_steps_computed(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs of a fixed, seeded
+    sample (float64, <= 64 MB) with their global sample indices -- here
+    compared with the oracle sample by sample."""
+    import numpy as np
+    import oracle_lib as O
+    out = tmp_path / "dump"
+    r = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log2-samples",
+             "23", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _line(r.stdout, want_detail=False)
+    assert line["steps"] == 3
+    assert sorted(p.name for p in out.iterdir()) == ["index.npy", "x.npy",
+                                                     "y.npy"]
+    got = {k: np.load(out / (k + ".npy")) for k in ("index", "x", "y")}
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    idx = got["index"]
+    assert idx.dtype == np.float64 and idx.size == 1 << 20
+    assert len(np.unique(idx)) == idx.size and idx.max() < 1 << 23
+    ii = idx.astype(np.uint64)
+    c = O.config_cli(O.P2R, 32, 32, 2, 32, 16)
+    ph = ((ii << np.uint64(2)) & np.uint64(0xffffffff)).astype(np.uint32)
+    ox, oy = O.rotate(c, 2 ** 31 - 1, 0, ph)
+    assert got["x"].dtype == np.float64
+    assert np.array_equal(got["x"], ox.astype(np.float64))
+    assert np.array_equal(got["y"], oy.astype(np.float64))
+    # a workload outside the cordic_group layer (per-sample vectors, torch
+    # tensors): the whole batch when it is no larger than the sample
+    out = tmp_path / "dump_p2rxy"
+    r = run(["--workload", "p2rxy", "--steps", "3", "--warmup", "1",
+             "--log2-samples", "20", "--no-cpu-baseline", "--no-pmc",
+             "--no-power", "--no-full-digest", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = {k: np.load(out / (k + ".npy")) for k in ("index", "x", "y")}
+    assert np.array_equal(got["index"], np.arange(1 << 20, dtype=np.float64))
+    i32 = np.arange(1 << 20, dtype=np.uint32)
+
+    def ramp(mul):
+        return ((i32 * np.uint32(mul)) >> np.uint32(8)).astype(np.int64)
+
+    def signed(v, bits=32):
+        v &= (1 << bits) - 1
+        return ((v ^ (1 << (bits - 1))) - (1 << (bits - 1))).astype(np.int32)
+    ox, oy = O.rotate(c, signed(ramp(0x9E3779B1)), signed(ramp(0x85EBCA77)),
+                      (i32 << np.uint32(2)).astype(np.uint32))
+    assert np.array_equal(got["x"], ox.astype(np.float64))
+    assert np.array_equal(got["y"], oy.astype(np.float64))
 
 
 @pytest.mark.gpu
@@ -332,7 +402,7 @@ def test_traffic_is_measured_in_the_same_run():
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not installed")
     d = _line(run(["--gpus", "1", "--steps", "5", "--warmup", "1",
-                   "--log2-samples", "26", "--no-cpu-baseline",
+                   "--log2-samples", "26", "--full", "--no-cpu-baseline",
                    "--no-other-paths"]).stdout)
     r = d["roofline"]
     assert "error" not in r["pmc"], r["pmc"]
@@ -347,7 +417,7 @@ def test_power_and_clock_are_sampled_in_the_same_run():
     if not glob.glob("/sys/class/drm/card*/device/hwmon/hwmon*/power1_input"):
         pytest.skip("no amdgpu hwmon files in this container")
     args = ["--steps", "20", "--warmup", "2", "--log2-samples", "26",
-            "--no-cpu-baseline", "--no-other-paths", "--no-pmc"]
+            "--full", "--no-cpu-baseline", "--no-other-paths", "--no-pmc"]
     d = _line(run(["--gpus", "1"] + args).stdout)
     pw = d["roofline"]["power"]
     assert 500 <= pw["limit_w"] <= 3000
@@ -407,7 +477,8 @@ def test_every_line_says_which_ceiling_binds(workload):
     evidence which bound is hit -- instruction count from this run's own
     SQ_INSTS_VALU pass, clock from this run's hwmon samples."""
     r = run(["--workload", workload, "--steps", "6", "--warmup", "2",
-             "--log2-samples", "24", "--no-cpu-baseline", "--no-other-paths",
+             "--log2-samples", "24", "--full", "--no-cpu-baseline",
+             "--no-other-paths",
              "--no-copy-probe", "--pmc-counters", "SQ_INSTS_VALU"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -477,8 +548,9 @@ def test_the_drivers_multi_rank_command_on_one_gpu(workload, ranks):
            "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), BENCH, "--gpus", str(ranks),
            "--workload", workload, "--steps", "4", "--warmup", "1",
-           "--log2-samples", str(lg), "--no-cpu-baseline", "--no-other-paths",
-           "--no-pmc", "--no-power", "--no-copy-probe", "--detail", _detail_path()]
+           "--log2-samples", str(lg), "--full", "--no-cpu-baseline",
+           "--no-other-paths", "--no-pmc", "--no-power", "--no-copy-probe",
+           "--detail", _detail_path()]
     r = subprocess.run(cmd, env=e, text=True, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -531,7 +603,7 @@ def test_the_drivers_multi_rank_command_on_one_gpu(workload, ranks):
         assert "error" not in sp, sp
     if "launch" not in d:
         return
-    # the DEFAULT multi-rank line carries both scalings of
+    # the --full multi-rank line carries both scalings of
     # SURVEY 8(e) -- compute only (`value`) and compute + the final gather,
     # over the C++ layer's RCCL send / recv between the ranks and over peer
     # copies in the embedded one-process run -- and what arrives at the root
@@ -577,8 +649,8 @@ def _torchrun(ranks, extra, env, timeout=900):
                           stderr=subprocess.PIPE, timeout=timeout)
 
 
-QUIET = ["--no-cpu-baseline", "--no-other-paths", "--no-pmc", "--no-power",
-         "--no-copy-probe"]
+QUIET = ["--full", "--no-cpu-baseline", "--no-other-paths", "--no-pmc",
+         "--no-power", "--no-copy-probe"]
 
 
 @pytest.mark.gpu

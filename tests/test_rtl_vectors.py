@@ -3,8 +3,9 @@
 tests/golden/rtl_vectors.json holds per-sample vectors produced by executing
 the Verilog emitted by the real reference generator with tests/vsim.py
 (tests/golden/make_rtl_vectors.py).  The live tests below additionally run
-vsim on the checked-in rtl/*.v (when /root/reference is mounted) and on fresh
-parameter sets emitted by oracle/_ref/gencordic (when it is built)."""
+vsim on the checked-in rtl/*.v (when the reference tree is mounted; stored
+vsim outputs of them otherwise) and on fresh parameter sets emitted by
+oracle/_ref/gencordic (when it is built)."""
 import json
 import os
 import re
@@ -107,33 +108,58 @@ def drive(m, x, y, ph, cpo=None):
     return vsim.run_pipelined(m, samples)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_RTL), reason="reference not mounted")
-@pytest.mark.parametrize("core,mode,cpo", [("cordic", O.P2R, None),
-                                           ("topolar", O.R2P, None),
-                                           ("seqcordic", O.SP2R, 17),
-                                           ("seqpolar", O.SR2P, 21)])
-def test_checked_in_rtl_executed_by_vsim_equals_oracle(core, mode, cpo):
-    """rtl/{cordic,topolar,seqcordic,seqpolar}.v, read where they lie."""
-    m = vsim.Module(open(os.path.join(REF_RTL, core + ".v")).read())
+CHECKED_IN = os.path.join(ROOT, "tests", "golden", "checked_in_rtl_vectors.json")
+CHECKED_IN_CORES = [("cordic", O.P2R, None), ("topolar", O.R2P, None),
+                    ("seqcordic", O.SP2R, 17), ("seqpolar", O.SR2P, 21)]
+
+
+def checked_in_inputs(mode, cpo):
+    """the oracle's config of the checked-in cores and the inputs they are
+    driven with (seeded: the same in every run)"""
     c = O.config_cli(mode, 13, 13, 2)
-    assert (m.params["IW"], m.params["WW"], m.params["PW"]) == (c.iw, c.ww, c.pw)
     rng = np.random.RandomState(5)
     n = 2500 if cpo is None else 400
     x = rng.randint(-4096, 4096, n)
     y = rng.randint(-4096, 4096, n)
     ph = rng.randint(0, 1 << c.pw, n)
     x[:4], y[:4] = [-4096, 4095, 0, -4096], [-4096, 4095, 0, 4095]
+    return c, x, y, ph
+
+
+def run_checked_in(core, mode, cpo):
+    """vsim on the reference's rtl/<core>.v -> (IW, WW, PW), output columns"""
+    m = vsim.Module(open(os.path.join(REF_RTL, core + ".v")).read())
+    c, x, y, ph = checked_in_inputs(mode, cpo)
     rot = mode in (O.P2R, O.SP2R)
     res = drive(m, x, y, ph if rot else None, cpo)
-    if rot:
+    keys = ("o_xval", "o_yval") if rot else ("o_mag", "o_phase")
+    params = {k: m.params[k] for k in ("IW", "WW", "PW")}
+    return params, {k: [r[k] for r in res] for k in keys}
+
+
+@pytest.mark.parametrize("core,mode,cpo", CHECKED_IN_CORES)
+def test_checked_in_rtl_executed_by_vsim_equals_oracle(core, mode, cpo):
+    """rtl/{cordic,topolar,seqcordic,seqpolar}.v, read where they lie when the
+    reference tree is there; otherwise what vsim computed from them, stored
+    (tests/golden/checked_in_rtl_vectors.json,
+    tests/golden/make_checked_in_rtl_vectors.py)."""
+    if os.path.isdir(REF_RTL):
+        params, out = run_checked_in(core, mode, cpo)
+    else:
+        with open(CHECKED_IN) as f:
+            e = json.load(f)[core]
+        params, out = e["params"], e["out"]
+    c, x, y, ph = checked_in_inputs(mode, cpo)
+    assert (params["IW"], params["WW"], params["PW"]) == (c.iw, c.ww, c.pw)
+    if mode in (O.P2R, O.SP2R):
         ox, oy = O.rotate(c, x.astype(np.int32), y.astype(np.int32),
                           ph.astype(np.uint32))
-        assert [r["o_xval"] for r in res] == ox.tolist()
-        assert [r["o_yval"] for r in res] == oy.tolist()
+        assert out["o_xval"] == ox.tolist()
+        assert out["o_yval"] == oy.tolist()
     else:
         mag, p = O.topolar(c, x.astype(np.int32), y.astype(np.int32))
-        assert [r["o_mag"] for r in res] == mag.tolist()
-        assert [r["o_phase"] & ((1 << c.pw) - 1) for r in res] == p.tolist()
+        assert out["o_mag"] == mag.tolist()
+        assert [v & ((1 << c.pw) - 1) for v in out["o_phase"]] == p.tolist()
 
 
 @pytest.mark.skipif(not os.path.exists(GEN), reason="oracle/_ref not built")

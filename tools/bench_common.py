@@ -202,3 +202,40 @@ class RawWords:
 
     def numel(self):
         return self._n
+
+
+DUMP_SEED = 20240611           # --dump-outputs: which windows of a shard
+DUMP_SAMPLES = 1 << 20         # samples per output array (8 MB as float64)
+DUMP_WINDOW = 4096
+
+
+def dump_windows(n):
+    """(offset, count) windows of a shard of n samples whose outputs
+    --dump-outputs writes: all of it up to DUMP_SAMPLES, else DUMP_SAMPLES /
+    DUMP_WINDOW windows at offsets drawn with a fixed seed (the same ones in
+    every run of the same size)."""
+    if n <= DUMP_SAMPLES:
+        return [(0, n)]
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    picks = rng.choice(n // DUMP_WINDOW, size=DUMP_SAMPLES // DUMP_WINDOW,
+                       replace=False)
+    return [(int(k) * DUMP_WINDOW, DUMP_WINDOW) for k in sorted(picks)]
+
+
+def dump_outputs(dirname, index0, windows, arrays):
+    """--dump-outputs: write every output array (name -> 1-D integer array
+    holding the windows' samples back to back) as DIR/<name>.npy in float64
+    (exact for 32-bit words), beside DIR/index.npy, the global sample index of
+    each element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    idx = np.concatenate([np.arange(o, o + c, dtype=np.int64)
+                          for o, c in windows]) + index0
+    out = dict(arrays, index=idx)
+    if sum(v.size * 8 for v in out.values()) > 64 << 20:
+        raise SystemExit("bench.py: --dump-outputs would exceed 64 MB")
+    for name, v in out.items():
+        assert v.size == idx.size, name
+        np.save(os.path.join(dirname, name + ".npy"),
+                np.ascontiguousarray(v, dtype=np.float64))

@@ -14,12 +14,25 @@ import build_stamp
 
 T0 = time.perf_counter()
 from bench_common import (HBM_PEAK_GBS, MODE, SHARE_GPU, WORKLOADS, coll_device,
-                          dist_init, emit, ranks_on_this_node, usable_cpus)
+                          dist_init, dump_outputs, dump_windows, emit,
+                          ranks_on_this_node, usable_cpus)
 from bench_line import publish
 from bench_oracle import cpu_baseline, oracle_digest_leg, reduce_digest_legs
 from bench_pmc import from_profile, measure_pmc
 from bench_power import finish_power, start_power
 from bench_valu import add_valu
+
+def dump_tensors(args, dev, index0, tensors):
+    """--dump-outputs: the windows of dump_windows() of each output tensor
+    (name -> 1-D device tensor of n samples), as bench.py's run_group writes
+    them"""
+    n = next(iter(tensors.values())).numel()
+    win = dump_windows(n)
+    ti = torch.from_numpy(np.concatenate(
+        [np.arange(o, o + c, dtype=np.int64) for o, c in win])).to(dev)
+    dump_outputs(args.dump_outputs, index0, win,
+                 {k: t[ti].cpu().numpy() for k, t in tensors.items()})
+
 
 def bench_table(args, w, ca, dist, dev, world, rank):
     """Table cores (row F4): same timing discipline, gather kernel."""
@@ -61,6 +74,8 @@ def bench_table(args, w, ca, dist, dev, world, rank):
         ev[k + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_tensors(args, dev, index0, {"out": out})
     power = finish_power(sampler, lambda: tab.lookup(phase, out),
                          torch.cuda.synchronize, t0, elapsed, args.steps,
                          float(n))
@@ -245,6 +260,9 @@ def run_direct(args, w, launch):
         ev[k + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_tensors(args, dev, index0, dict(zip(
+            ("mag", "phase") if w["kind"] == "r2p" else ("x", "y"), (a, b))))
     power = finish_power(sampler, step, torch.cuda.synchronize, t0, elapsed,
                          args.steps, float(n),
                          seconds=2.0 if args.full else 1.0)

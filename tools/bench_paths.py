@@ -35,6 +35,7 @@ def other_paths(args, steps=24, warmup=4):
         cmd = [sys.executable, BENCH, "--workload", wl, "--detail", dpath,
                "--steps", str(steps), "--warmup", str(warmup),
                "--log2-samples", str(log2n), "--input", args.input,
+               "--full", "--no-other-paths", "--no-copy-probe",
                "--no-cpu-baseline",
                "--pmc-counters", "SQ_INSTS_VALU+SQ_INSTS_VALU_INT64"]
         if args.no_pmc:

@@ -19,7 +19,10 @@ def main():
     fd, path = tempfile.mkstemp(prefix="bench_row_", suffix=".json", dir="/tmp")
     os.close(fd)
     try:
+        # (the clock, power, VALU and oracle figures are --full's; the other
+        # entry points and the copy probes stay out of an A/B row)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"),
+                            "--full", "--no-other-paths", "--no-copy-probe",
                             "--detail", path] + args, text=True,
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         if r.returncode != 0:

@@ -22,11 +22,11 @@ bash tools/gpu_session.sh env sweep > $OUT/session.log 2>&1
 for w in cfg2 cfg3 cfg4 cfg5 p2rxy ddc cfg1; do timeout 900 bash tools/profile_workload.sh $w > $OUT/prof_$w.log 2>&1; done
 for w in cfg2 cfg4 p2rxy; do timeout 900 bash tools/profile_workload.sh $w --input random > $OUT/prof_${w}_random.log 2>&1; done
 (time timeout 1800 python bench.py --full --detail $OUT/full_detail.json) > $OUT/full.line 2> $OUT/full.err
-# the driver's multi-rank command, default flags, 8 ranks SHARING this GPU (test
+# the driver's multi-rank command with --full, 8 ranks SHARING this GPU (test
 # switch; RCCL entry points from tests/rccl_shim): the line an 8-GPU node prints
 BENCH_TEST_SHARE_GPU=1 CORDIC_RCCL_LIB=$PWD/tests/rccl_shim/librccl_shim.so HSA_ENABLE_IPC_MODE_LEGACY=0 \
 	timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-	--master-port 29533 bench.py --gpus 8 --workload cfg4 --log2-samples 26 --steps 20 --warmup 5 \
+	--master-port 29533 bench.py --gpus 8 --workload cfg4 --log2-samples 26 --steps 20 --warmup 5 --full \
 	--detail $OUT/bench_8_ranks_one_gpu.json > $OUT/bench_8_ranks_one_gpu.line 2> $OUT/bench_8_ranks_one_gpu.err
 for seed in 11 12 13; do timeout 900 python tools/fuzz_gpu.py 1500 $seed 2>&1 | grep "fuzz ok" >> $OUT/fuzz.txt; done
 wc -c $OUT/*.line

@@ -44,14 +44,15 @@ for task in "$@"; do
 		# record is stamped with the code state (build.kernel_sources_sha256)
 		mkdir -p gpurun_out/bench_sweep
 		for w in ${SWEEP_WORKLOADS:-cfg2 cfg1 cfg3 cfg4 cfg5 cfg5seq p2rxy ddc nat32 nat24 nat16 natr2p24 sintbl qtrtbl qtrtbl16 qtrtbl24 quadtbl quadtbl24}; do
-			python bench.py --workload $w --input ramp --no-cpu-baseline --copy-probe \
+			python bench.py --workload $w --input ramp --full --no-other-paths --no-cpu-baseline --copy-probe \
 				--detail gpurun_out/bench_sweep/${w}_ramp.json \
 				--pmc-counters SQ_INSTS_VALU+SQ_INSTS_VALU_INT64 > gpurun_out/bench_sweep/${w}_ramp.line 2>> $log
-			python bench.py --workload $w --input random --no-cpu-baseline --no-pmc --copy-probe \
+			python bench.py --workload $w --input random --full --no-other-paths --no-cpu-baseline --no-pmc --copy-probe \
 				--detail gpurun_out/bench_sweep/${w}_random.json \
 				> gpurun_out/bench_sweep/${w}_random.line 2>> $log
 		done
-		python bench.py --detail gpurun_out/bench_sweep/default.json > gpurun_out/bench_sweep/default.line 2>> $log ;;
+		# the default line's figures with the oracle and CPU legs (--full); ${log%/*}: the log's folder
+		python bench.py --full --no-other-paths --detail ${log%/*}/bench_sweep/default.json > ${log%/*}/bench_sweep/default.line 2>> $log ;;
 	*)	echo "unknown task $task" | tee -a $log ;;
 	esac
 done

@@ -133,6 +133,7 @@ ABI = {
     "cordic_jobset_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32)]),
+    "cordic_jobset_path": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "cordic_plan_run_jobs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_int32, C.c_void_p]),
     "cordic_plan_p2r_const_batch": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -524,6 +525,8 @@ class _CJob(C.Structure):
 
 
 JOBS_PHASE_ARRAYS, JOBS_NCO, JOBS_R2P, JOBS_P2R_XY, JOBS_MIX = 0, 1, 2, 3, 4
+# enum cordic_jobs_path: how the latest run of a set went
+JOBS_PATH_NONE, JOBS_PATH_FUSED, JOBS_PATH_ONE_BY_ONE = 0, 1, 2
 
 
 def _job_array(jobs):
@@ -564,6 +567,15 @@ class Jobset:
         _check(lib().cordic_jobset_info(self._h, C.byref(a), C.byref(b),
                                         C.byref(c)), "cordic_jobset_info")
         return dict(samples=a.value, tiles=b.value, tail_samples=c.value)
+
+    @property
+    def path(self):
+        """JOBS_PATH_NONE before the first run, else JOBS_PATH_FUSED or
+        JOBS_PATH_ONE_BY_ONE: the way the latest run went"""
+        p = C.c_int32()
+        _check(lib().cordic_jobset_path(self._h, C.byref(p)),
+               "cordic_jobset_path")
+        return p.value
 
     def run(self, x0=0, y0=0, stream=None, plan=None):
         _check(lib().cordic_plan_run_jobs((plan or self.plan)._h, self._h, x0,

@@ -12,6 +12,7 @@
 
 #include "cordic_amd.h"
 #include "cordic_internal.h"
+#include "cordic_jobs_fused.h"
 
 using namespace cordic_amd;
 
@@ -403,6 +404,8 @@ struct cordic_jobset {
 	uint32_t *d_tiles = nullptr, *d_tails = nullptr;
 	JobTables tabs;
 	cordic_config cfg;		// of the plan it was cut for (PW decides NCO words)
+	// enum cordic_jobs_path of the latest run (runs take the set const)
+	mutable std::atomic<int> path{CORDIC_JOBS_PATH_NONE};
 };
 
 namespace {
@@ -616,6 +619,14 @@ int cordic_jobset_info(const cordic_jobset *set, uint64_t *samples,
 	return CORDIC_OK;
 }
 
+int cordic_jobset_path(const cordic_jobset *set, int32_t *path)
+{
+	if (!set || !path)
+		return CORDIC_ERR_ARGS;
+	*path = set->path.load(std::memory_order_relaxed);
+	return CORDIC_OK;
+}
+
 int cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 		int32_t xval, int32_t yval, void *stream)
 {
@@ -634,10 +645,19 @@ int cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 		RotatorJob j;
 		if (set->kind != CORDIC_JOBS_R2P)
 			attach_dirs(plan, j);
+		// the instances of launch_xy_jobs first, then the tile forms of the
+		// other single-call kernels (cordic_jobs_fused.h)
 		int rc = launch_xy_jobs(plan->cfg, set->kind, j, set->tabs, stream);
-		if (rc != CORDIC_ERR_UNSUPPORTED)
+		if (rc == CORDIC_ERR_UNSUPPORTED)
+			rc = launch_xy_jobs_fused(plan->cfg, set->kind, j, set->tabs, stream);
+		if (rc != CORDIC_ERR_UNSUPPORTED) {
+			if (rc == CORDIC_OK)
+				set->path.store(CORDIC_JOBS_PATH_FUSED, std::memory_order_relaxed);
 			return rc;
-		// no tile-reading instance for this core: the jobs one by one
+		}
+		// the single call runs the generic kernel on this core: the jobs one
+		// by one
+		set->path.store(CORDIC_JOBS_PATH_ONE_BY_ONE, std::memory_order_relaxed);
 		for (const cordic_job &jb : set->jobs) {
 			if (jb.n == 0)
 				continue;
@@ -663,10 +683,14 @@ int cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 		j.queue = q;
 		return launch_rotator_jobs(plan->cfg, feed, j, set->tabs, stream);
 	});
-	if (rc != CORDIC_ERR_UNSUPPORTED)
+	if (rc != CORDIC_ERR_UNSUPPORTED) {
+		if (rc == CORDIC_OK)
+			set->path.store(CORDIC_JOBS_PATH_FUSED, std::memory_order_relaxed);
 		return rc;
+	}
 	// no seeded kernel for this core (or no tile queue to be had right now):
 	// the jobs one by one through the ordinary entry points -- same results
+	set->path.store(CORDIC_JOBS_PATH_ONE_BY_ONE, std::memory_order_relaxed);
 	for (const cordic_job &jb : set->jobs) {
 		if (jb.n == 0)
 			continue;

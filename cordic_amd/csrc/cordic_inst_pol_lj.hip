@@ -47,7 +47,8 @@ bool launch_pol_lj(int nlive, int grid, hipStream_t st, const dev::CoreParams &k
 
 // Job sets (CORDIC_JOBS_R2P): the 20-stage core of BASELINE config 3 and the
 // 29 stages gencordic derives for 24-bit ports on static instances, every
-// other count on the dynamic-exit one; unit gain: the jobs one by one.
+// other count on the dynamic-exit one; unit gain: the tile form of topolar_lj's
+// unit-gain instance (cordic_jobs_pol.hip), also in one launch.
 bool launch_pol_lj_jobs(int nlive, int grid, hipStream_t st,
 		const dev::CoreParams &kp, const TileDescXY *tiles, uint32_t ntiles)
 {

@@ -43,8 +43,10 @@ bool CORDIC_XYDIR_NAME(int nlive, int grid, hipStream_t st,
 
 // Job sets (CORDIC_JOBS_P2R_XY / CORDIC_JOBS_MIX): tile-reading instances for
 // the stage counts the including unit lists in CORDIC_XYDIR_JOB_STAGES (the
-// BASELINE cores and gencordic's own derivations); other counts run their jobs
-// one by one (launch_xy_jobs returns CORDIC_ERR_UNSUPPORTED).
+// BASELINE cores and gencordic's own derivations); for other counts
+// launch_xy_jobs returns CORDIC_ERR_UNSUPPORTED and the set runs on the
+// instances of cordic_jobs_xydir.hip or on the dynamic-exit tile kernel
+// (cordic_jobs_fused.h), still in one launch.
 bool CORDIC_XYDIR_JOBS_NAME(int nlive, int grid, hipStream_t st,
 		const dev::CoreParams &kp, const dev::DirArgs &da,
 		const TileDescXY *tiles, uint32_t ntiles, size_t lds)

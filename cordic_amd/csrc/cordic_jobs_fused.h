@@ -1,0 +1,50 @@
+// cordic_jobs_fused.h -- tile-reading kernels for the data-fed job-set kinds
+// (CORDIC_JOBS_R2P / _P2R_XY / _MIX) on the cores that launch_xy_jobs has no
+// instance for.  A set gets the tile form of the kernel family that ONE long
+// call on its core uses (launch_rot_feed, launch_topolar); the tile
+// descriptors (TileDescXY) are the ones cordic_jobset_create cuts for every
+// data-fed set.  Host-visible types only.
+//
+// None of these units holds a kernel of the DESIGN section 4.4 sweep (no swept
+// workload runs a job set), so tools/build_stamp.py does not hash them.
+#ifndef CORDIC_JOBS_FUSED_H
+#define CORDIC_JOBS_FUSED_H
+
+#include <hip/hip_runtime_api.h>
+
+#include "cordic_internal.h"
+
+namespace cordic_amd {
+
+namespace dev { struct CoreParams; struct DirArgs; }
+
+// The whole set in one launch of a tile kernel (+ the existing trailing-sample
+// launch of launch_xy_jobs).  Called after launch_xy_jobs has answered
+// CORDIC_ERR_UNSUPPORTED; CORDIC_ERR_UNSUPPORTED again: the single call on
+// this core runs the generic kernel (WW > 40, wrap at a width other than 32,
+// the A/B flags) -- the caller runs the jobs one by one.
+int	launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &job,
+		const JobTables &tabs, void *stream);
+
+// ---- launchers of the tile kernels (cordic_jobs_rot.hip, cordic_jobs_rotw.hip,
+// cordic_jobs_pol.hip, cordic_jobs_xydir.hip); false: no instance
+//
+// rotator with per-sample vectors (a mixer when kp.xy_nco): the dynamic-exit
+// form of rotator_unrolled in the container of the single call --
+// lj = 0: Narrow32 (wrap at WW 32), 30: WW <= 34, 29: WW 35, 28 .. 24: WW 36 .. 40
+bool	launch_rot_xy_tiles(int lj, int grid, hipStream_t st, const dev::CoreParams &kp,
+		const TileDescXY *tiles, uint32_t ntiles);
+bool	launch_rot_xy_tiles_w(int lj, int grid, hipStream_t st, const dev::CoreParams &kp,
+		const TileDescXY *tiles, uint32_t ntiles);
+// ... with looked-up directions: rotator_xydir<LJ, N, true> for the counts
+// that cordic_inst_xydir_lj29 / _lj30 do not carry (lj = 29: WW 35, 30: WW <= 34)
+bool	launch_xydir_tiles(int lj, int nlive, int grid, hipStream_t st,
+		const dev::CoreParams &kp, const dev::DirArgs &da, const TileDescXY *tiles,
+		uint32_t ntiles, size_t lds);
+// converter: lj = 0: Narrow32 (wrap at WW 32), 30: topolar_lj with unit gain
+// (WW <= 34), 29 .. 24: topolar_ljw (WW 35 .. 40)
+bool	launch_pol_tiles(int lj, int grid, hipStream_t st, const dev::CoreParams &kp,
+		const TileDescXY *tiles, uint32_t ntiles);
+
+} // namespace cordic_amd
+#endif

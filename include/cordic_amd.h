@@ -409,13 +409,18 @@ int	cordic_plan_nco(const cordic_plan *plan, size_t n,
  *                             phase0 + (index0 + i) * fcw
  * These are cut into tiles of 256 .. 2048 whole vectors (shorter tiles for
  * small sets, so that every CU gets several blocks) and run as ONE launch of
- * the tile-reading instance of the call's own kernel (topolar_lj, rotator_xydir;
- * + one small launch for trailing samples).  Tile-reading instances exist for
- * the left-justified converter (WW <= 34, no reachable overflow, no unit gain:
- * static for 20 and 29 stages, dynamic-exit otherwise) and for the looked-up-
- * direction rotator at WW 35 with 16 / 24 / 29 stages and WW <= 34 with 16 / 19
- * / 27; every other core runs its jobs one by one behind the same call.
- * Results: bit for bit those of the per-job calls.
+ * the tile-reading form of the kernel family that one long call on the same
+ * core uses (+ one small launch for trailing samples).  That covers every core
+ * up to WW 40 that the single call serves on a vector kernel: the left-
+ * justified converter (WW <= 34, WW 35 .. 40, with or without unit gain), the
+ * 32-bit containers of cores that wrap at WW 32, the looked-up-direction
+ * rotator (WW <= 35 with a direction table, 13 / 16 / 19 / 20 / 24 / 27 / 29
+ * stages) and the unrolled rotator of every other rotator or mixer core (unit
+ * gain, CORDIC_FLAG_NO_TAILS, other stage counts, WW 36 .. 40).  Jobs run one
+ * by one behind the same call on cores with WW > 40, wrap at widths other than
+ * 32, and under CORDIC_FLAG_FORCE_GENERIC / CORDIC_FLAG_NO_LJ.
+ * Results: bit for bit those of the per-job calls.  cordic_jobset_path tells
+ * which way the last run of a set went.
  * Cores without a table-seeded kernel (WW > 35, fewer than 11 live stages,
  * CORDIC_FLAG_NO_SEED) run constant-vector jobs one by one behind the same call.
  */
@@ -439,6 +444,14 @@ void	cordic_jobset_destroy(cordic_jobset *set);
  * trailing-sample launch (any pointer may be NULL) */
 int	cordic_jobset_info(const cordic_jobset *set, uint64_t *samples,
 		uint32_t *tiles, uint32_t *tail_samples);
+enum cordic_jobs_path {
+	CORDIC_JOBS_PATH_NONE = 0,	/* not run yet                         */
+	CORDIC_JOBS_PATH_FUSED = 1,	/* tile-reading launch (+ tail launch) */
+	CORDIC_JOBS_PATH_ONE_BY_ONE = 2	/* the per-job entry points            */
+};
+/* the path the most recent cordic_plan_run_jobs on this set took (also when
+ * a constant-vector set fell back because no tile queue was free) */
+int	cordic_jobset_path(const cordic_jobset *set, int32_t *path);
 int	cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 		int32_t xval, int32_t yval, void *stream);
 int	cordic_plan_p2r_const_batch(const cordic_plan *plan, size_t njobs,

@@ -75,6 +75,7 @@ def jobset_fuzz(rng, plan, cfg, ocfg, x, y, ph, paths):
         js.run(x0, y0)
         torch.cuda.synchronize()
         fam = ca.last_kernel()
+        path = js.path
         js.close()
         ga, gb = oa.cpu().numpy(), ob.cpu().numpy()
         for (lo, hi), w in zip(pieces, want):
@@ -86,9 +87,25 @@ def jobset_fuzz(rng, plan, cfg, ocfg, x, y, ph, paths):
                                  "pw %d nlive %d piece [%d, %d) of %r"
                                  % (kind, cfg.mode, cfg.iw, cfg.ow, cfg.ww, cfg.pw,
                                     cfg.nlive, lo, hi, pieces))
-        key = "jobs%d:%s" % (kind, {ca.KERNEL_SEEDED: "seeded",
-                                    ca.KERNEL_DIRECTIONS: "dirs",
-                                    ca.KERNEL_LEFT_JUSTIFIED: "lj"}.get(fam, "one-by-one"))
+        # the path the set reports (cordic_jobset_path); a fused run by the
+        # kernel family it ran on
+        if path == ca.JOBS_PATH_FUSED:
+            what = {ca.KERNEL_SEEDED: "seeded", ca.KERNEL_DIRECTIONS: "dirs",
+                    ca.KERNEL_LEFT_JUSTIFIED: "lj",
+                    ca.KERNEL_UNROLLED: "unrolled"}.get(fam, "fused")
+        else:
+            assert path == ca.JOBS_PATH_ONE_BY_ONE, path
+            what = "one-by-one"
+            # data-fed kinds up to WW 40 fuse unless the single call on the
+            # core runs the generic kernel (wrap at a width other than 32, no
+            # live stage or more than the 40 of the dynamic-exit kernels, a
+            # rotator whose 64-bit fold needs in_shl > 30)
+            if (kind >= ca.JOBS_R2P and cfg.ww <= 40
+                    and not (cfg.needs_wrap and cfg.ww != 32)
+                    and 1 <= cfg.nlive <= 40
+                    and not (rot and cfg.ww > 32 and cfg.ww - cfg.iw - 1 > 30)):
+                what = "one-by-one-ww40"
+        key = "jobs%d:%s" % (kind, what)
         paths[key] = paths.get(key, 0) + 1
 
 

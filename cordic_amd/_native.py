@@ -100,6 +100,18 @@ ABI = {
                                     C.c_uint32, C.c_uint64, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    "cordic_mix16": (C.c_int, [_cfgp, C.c_size_t, C.c_uint32, C.c_uint32,
+                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "cordic_plan_mix16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                    C.c_uint32, C.c_uint64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "cordic_plan_p2r16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "cordic_jobset_create16": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t,
+                                         C.c_void_p, C.POINTER(C.c_void_p)]),
     "cordic_plan_create": (C.c_int, [_cfgp, C.POINTER(C.c_void_p)]),
     "cordic_plan_destroy": (None, [C.c_void_p]),
     "cordic_plan_config": (_cfgp, [C.c_void_p]),
@@ -424,6 +436,13 @@ class Plan:
     def p2r(self, x, y, phase, ox, oy, n=None, stream=None):
         """per-sample vectors through the plan (directions looked up)"""
         n = phase.numel() if n is None else n
+        if any(_is16(t) for t in (x, y, phase, ox, oy)):
+            # (cordic_p2r16's kernel: no looked-up directions on int16 arrays)
+            _same16("cordic_plan_p2r16", x, y, phase, ox, oy)
+            _check(lib().cordic_plan_p2r16(
+                self._h, n, _ptr(x), _ptr(y), _ptr(phase), _ptr(ox), _ptr(oy),
+                _stream(stream)), "cordic_plan_p2r16")
+            return
         _check(lib().cordic_plan_p2r(self._h, n, _ptr(x), _ptr(y), _ptr(phase),
                                      _ptr(ox), _ptr(oy), _stream(stream)),
                "cordic_plan_p2r")
@@ -431,6 +450,13 @@ class Plan:
     def mix(self, phase0, fcw, index0, x, y, ox, oy, n=None, stream=None):
         """fused NCO mixer through the plan (directions looked up)"""
         n = x.numel() if n is None else n
+        if any(_is16(t) for t in (x, y, ox, oy)):
+            _same16("cordic_plan_mix16", x, y, ox, oy)
+            _check(lib().cordic_plan_mix16(
+                self._h, n, phase0 & 0xffffffff, fcw & 0xffffffff, index0,
+                _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _stream(stream)),
+                "cordic_plan_mix16")
+            return
         _check(lib().cordic_plan_mix(self._h, n, phase0 & 0xffffffff,
                                      fcw & 0xffffffff, index0, _ptr(x), _ptr(y),
                                      _ptr(ox), _ptr(oy), _stream(stream)),
@@ -524,16 +550,32 @@ class _CJob(C.Structure):
                 ("d_xval", C.c_void_p), ("d_yval", C.c_void_p)]
 
 
+class _CJob16(_CJob):
+    """cordic_job16: cordic_job whose sample pointers are int16_t / uint16_t
+    ones -- the same fields at the same offsets"""
+
+
 JOBS_PHASE_ARRAYS, JOBS_NCO, JOBS_R2P, JOBS_P2R_XY, JOBS_MIX = 0, 1, 2, 3, 4
 # enum cordic_jobs_path: how the latest run of a set went
 JOBS_PATH_NONE, JOBS_PATH_FUSED, JOBS_PATH_ONE_BY_ONE = 0, 1, 2
 
 
-def _job_array(jobs):
+def _jobs_are16(jobs):
+    """True: every sample tensor of the jobs is 16-bit (cordic_job16), False:
+    none is; a mixture is refused"""
+    sizes = {t.element_size() for jb in jobs
+             for t in (jb.get(k) for k in ("phase", "x", "y", "ox", "oy"))
+             if hasattr(t, "element_size")}
+    if 2 in sizes and len(sizes) > 1:
+        raise TypeError("job set: 16-bit and wider sample arrays in one set")
+    return sizes == {2}
+
+
+def _job_array(jobs, ctype=_CJob):
     """jobs: dicts with phase (tensor or None), ox, oy, n; for NCO / MIX jobs
     phase0, fcw, index0; for the data-fed kinds x, y (R2P: ox = o_mag, oy =
-    o_phase) -> a C array of cordic_job"""
-    arr = (_CJob * max(1, len(jobs)))()
+    o_phase) -> a C array of cordic_job (ctype=_CJob16: of cordic_job16)"""
+    arr = (ctype * max(1, len(jobs)))()
     for k, jb in enumerate(jobs):
         ph = jb.get("phase")
         arr[k].d_phase = _ptr(ph) if ph is not None else None
@@ -555,10 +597,16 @@ class Jobset:
     def __init__(self, plan, kind, jobs):
         self.plan = plan
         self._keep = jobs          # the tensors behind the addresses
-        arr = _job_array(jobs)
         h = C.c_void_p()
-        _check(lib().cordic_jobset_create(plan._h, kind, len(jobs), arr,
-                                          C.byref(h)), "cordic_jobset_create")
+        self.io16 = _jobs_are16(jobs)
+        if self.io16:      # int16 / uint16 tensors: cordic_job16
+            _check(lib().cordic_jobset_create16(
+                plan._h, kind, len(jobs), _job_array(jobs, _CJob16),
+                C.byref(h)), "cordic_jobset_create16")
+        else:
+            _check(lib().cordic_jobset_create(
+                plan._h, kind, len(jobs), _job_array(jobs), C.byref(h)),
+                "cordic_jobset_create")
         self._h = h
 
     @property
@@ -1189,11 +1237,12 @@ def _stream(stream):
 def _is16(t):
     """int16 / uint16 sample tensors select the 16-bit-container entry points
     (include/cordic_amd.h: cordic_*16)."""
-    return t.element_size() == 2
+    return hasattr(t, "element_size") and t.element_size() == 2
 
 
 def _same16(what, *tensors):
-    if any(t.element_size() != 2 for t in tensors):
+    # (None and raw addresses go through: the library answers for them)
+    if any(hasattr(t, "element_size") and t.element_size() != 2 for t in tensors):
         raise TypeError("%s: every sample array must be 16-bit" % what)
 
 
@@ -1237,6 +1286,13 @@ def nco(cfg, n, phase0, fcw, index0, x0, y0, ox, oy, stream=None):
 def mix(cfg, phase0, fcw, index0, x, y, ox, oy, n=None, stream=None):
     """cordic_mix: per-sample x / y rotated by phase0 + (index0 + i) * fcw"""
     n = x.numel() if n is None else n
+    if any(_is16(t) for t in (x, y, ox, oy)):
+        _same16("cordic_mix16", x, y, ox, oy)
+        _check(lib().cordic_mix16(cfg.ref, n, phase0 & 0xffffffff,
+                                  fcw & 0xffffffff, index0, _ptr(x), _ptr(y),
+                                  _ptr(ox), _ptr(oy), _stream(stream)),
+               "cordic_mix16")
+        return
     _check(lib().cordic_mix(cfg.ref, n, phase0 & 0xffffffff, fcw & 0xffffffff,
                             index0, _ptr(x), _ptr(y), _ptr(ox), _ptr(oy),
                             _stream(stream)), "cordic_mix")

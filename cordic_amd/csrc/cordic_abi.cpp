@@ -404,6 +404,9 @@ struct cordic_jobset {
 	uint32_t *d_tiles = nullptr, *d_tails = nullptr;
 	JobTables tabs;
 	cordic_config cfg;		// of the plan it was cut for (PW decides NCO words)
+	// cordic_jobset_create16: the sample arrays (and the pointers of `jobs`)
+	// are int16 / uint16 ones
+	bool	io16 = false;
 	// enum cordic_jobs_path of the latest run (runs take the set const)
 	mutable std::atomic<int> path{CORDIC_JOBS_PATH_NONE};
 };
@@ -479,12 +482,20 @@ uint32_t xy_tile_vecs(uint64_t total_vecs)
 }
 } // namespace
 
-int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
-		const cordic_job *jobs, cordic_jobset **out)
+namespace {
+// esize: bytes per sample of every array of the jobs -- 4, or 2 for the sets of
+// cordic_jobset_create16 (whose cordic_job16 has cordic_job's layout)
+int jobset_create(const cordic_plan *plan, int kind, size_t njobs,
+		const cordic_job *jobs, cordic_jobset **out, unsigned esize)
 {
 	if (!plan || !out || (njobs && !jobs) || kind < CORDIC_JOBS_PHASE_ARRAYS
 			|| kind > CORDIC_JOBS_MIX)
 		return CORDIC_ERR_ARGS;
+	const uintptr_t amask = esize - 1;
+	// address of sample s of an array
+	auto at = [esize](const void *p, uint64_t s) -> uint64_t {
+		return (uint64_t)((uintptr_t)p + (uintptr_t)s * esize);
+	};
 	const bool rot = plan->cfg.mode == CORDIC_P2R || plan->cfg.mode == CORDIC_SP2R;
 	if (rot == (kind == CORDIC_JOBS_R2P))
 		return CORDIC_ERR_MODE;
@@ -503,9 +514,10 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 			continue;
 		if (!jb.d_oxval || !jb.d_oyval || (phase_array && !jb.d_phase)
 				|| (xy && (!jb.d_xval || !jb.d_yval))
-				|| ((uintptr_t)jb.d_oxval & 3) || ((uintptr_t)jb.d_oyval & 3)
-				|| (phase_array && ((uintptr_t)jb.d_phase & 3))
-				|| (xy && (((uintptr_t)jb.d_xval & 3) || ((uintptr_t)jb.d_yval & 3))))
+				|| ((uintptr_t)jb.d_oxval & amask) || ((uintptr_t)jb.d_oyval & amask)
+				|| (phase_array && ((uintptr_t)jb.d_phase & amask))
+				|| (xy && (((uintptr_t)jb.d_xval & amask)
+					|| ((uintptr_t)jb.d_yval & amask))))
 			return CORDIC_ERR_ARGS;
 		samples += jb.n;
 		vecs += jb.n / 4;
@@ -524,15 +536,15 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 		};
 		auto in_word = [&](uint64_t s) -> uint64_t {
 			return gen_phase ? nco_word(s)
-				: phase_array ? (uint64_t)(uintptr_t)(jb.d_phase + s) : 0;
+				: phase_array ? at(jb.d_phase, s) : 0;
 		};
 		auto xy_desc = [&](uint64_t s, uint32_t live) {
 			TileDescXY d{};
-			d.in0 = (uint64_t)(uintptr_t)(jb.d_xval + s);
-			d.in1 = (uint64_t)(uintptr_t)(jb.d_yval + s);
+			d.in0 = at(jb.d_xval, s);
+			d.in1 = at(jb.d_yval, s);
 			d.in2 = in_word(s);
-			d.o0 = (uint64_t)(uintptr_t)(jb.d_oxval + s);
-			d.o1 = (uint64_t)(uintptr_t)(jb.d_oyval + s);
+			d.o0 = at(jb.d_oxval, s);
+			d.o1 = at(jb.d_oyval, s);
 			d.live = live;
 			return d;
 		};
@@ -544,8 +556,8 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 			}
 			TileDesc d{};
 			d.in = in_word(v0 * 4);
-			d.ox = (uint64_t)(uintptr_t)(jb.d_oxval + v0 * 4);
-			d.oy = (uint64_t)(uintptr_t)(jb.d_oyval + v0 * 4);
+			d.ox = at(jb.d_oxval, v0 * 4);
+			d.oy = at(jb.d_oyval, v0 * 4);
 			d.live = live;
 			tiles.push_back(d);
 		}
@@ -556,8 +568,8 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 			}
 			TailDesc d{};
 			d.in = in_word(s);
-			d.ox = (uint64_t)(uintptr_t)(jb.d_oxval + s);
-			d.oy = (uint64_t)(uintptr_t)(jb.d_oyval + s);
+			d.ox = at(jb.d_oxval, s);
+			d.oy = at(jb.d_oyval, s);
 			tails.push_back(d);
 		}
 		if (tiles.size() > 0x7fffffffu || tails.size() > 0x7fffffffu
@@ -569,6 +581,7 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 		return CORDIC_ERR_NOMEM;
 	set->kind = kind;
 	set->cfg = plan->cfg;
+	set->io16 = esize == 2;
 	set->jobs.assign(jobs, jobs + njobs);
 	if (hipGetDevice(&set->device) != hipSuccess) {
 		(void)hipGetLastError();
@@ -597,6 +610,58 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 	set->tabs.samples = samples;
 	*out = set;
 	return CORDIC_OK;
+}
+} // namespace
+
+int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
+		const cordic_job *jobs, cordic_jobset **out)
+{
+	return jobset_create(plan, kind, njobs, jobs, out, 4);
+}
+
+static int fits16(const cordic_config &c, bool phase_array);
+
+int cordic_jobset_create16(const cordic_plan *plan, int kind, size_t njobs,
+		const cordic_job16 *jobs, cordic_jobset **out)
+{
+	static_assert(sizeof(cordic_job16) == sizeof(cordic_job)
+		&& offsetof(cordic_job16, d_phase) == offsetof(cordic_job, d_phase)
+		&& offsetof(cordic_job16, phase0) == offsetof(cordic_job, phase0)
+		&& offsetof(cordic_job16, fcw) == offsetof(cordic_job, fcw)
+		&& offsetof(cordic_job16, index0) == offsetof(cordic_job, index0)
+		&& offsetof(cordic_job16, d_oxval) == offsetof(cordic_job, d_oxval)
+		&& offsetof(cordic_job16, d_oyval) == offsetof(cordic_job, d_oyval)
+		&& offsetof(cordic_job16, n) == offsetof(cordic_job, n)
+		&& offsetof(cordic_job16, d_xval) == offsetof(cordic_job, d_xval)
+		&& offsetof(cordic_job16, d_yval) == offsetof(cordic_job, d_yval),
+		"cordic_job16 is cordic_job with 16-bit sample pointers");
+	if (!plan || !out || (njobs && !jobs) || kind < CORDIC_JOBS_PHASE_ARRAYS
+			|| kind > CORDIC_JOBS_MIX)
+		return CORDIC_ERR_ARGS;
+	// (the constant-vector kinds would need the seeded kernel's tile form on
+	// 16-bit arrays)
+	if (kind < CORDIC_JOBS_R2P)
+		return CORDIC_ERR_UNSUPPORTED;
+	const bool rot = plan->cfg.mode == CORDIC_P2R || plan->cfg.mode == CORDIC_SP2R;
+	if (rot == (kind == CORDIC_JOBS_R2P))
+		return CORDIC_ERR_MODE;
+	if (int rc = fits16(plan->cfg, kind != CORDIC_JOBS_MIX))
+		return rc;
+	// the set keeps its jobs as cordic_job: same layout, the pointers are never
+	// dereferenced on the host and every address is computed in bytes
+	std::vector<cordic_job> wide(njobs);
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_job16 &a = jobs[k];
+		cordic_job &b = wide[k];
+		b.d_phase = reinterpret_cast<const uint32_t *>(a.d_phase);
+		b.phase0 = a.phase0; b.fcw = a.fcw; b.index0 = a.index0;
+		b.d_oxval = reinterpret_cast<int32_t *>(a.d_oxval);
+		b.d_oyval = reinterpret_cast<int32_t *>(a.d_oyval);
+		b.n = a.n;
+		b.d_xval = reinterpret_cast<const int32_t *>(a.d_xval);
+		b.d_yval = reinterpret_cast<const int32_t *>(a.d_yval);
+	}
+	return jobset_create(plan, kind, njobs, wide.data(), out, 2);
 }
 
 void cordic_jobset_destroy(cordic_jobset *set)
@@ -641,6 +706,36 @@ int cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 	}
 	if (!same_core(set->cfg, plan->cfg) || dev != set->device)
 		return CORDIC_ERR_ARGS;
+	if (set->io16) {
+		int rc = launch_xy_jobs16(plan->cfg, set->kind, set->tabs, stream);
+		if (rc != CORDIC_ERR_UNSUPPORTED) {
+			if (rc == CORDIC_OK)
+				set->path.store(CORDIC_JOBS_PATH_FUSED, std::memory_order_relaxed);
+			return rc;
+		}
+		// the single 16-bit call runs the generic kernel on this core
+		set->path.store(CORDIC_JOBS_PATH_ONE_BY_ONE, std::memory_order_relaxed);
+		for (const cordic_job &jb : set->jobs) {
+			if (jb.n == 0)
+				continue;
+			const int16_t *x = reinterpret_cast<const int16_t *>(jb.d_xval);
+			const int16_t *y = reinterpret_cast<const int16_t *>(jb.d_yval);
+			int16_t *ox = reinterpret_cast<int16_t *>(jb.d_oxval);
+			int16_t *oy = reinterpret_cast<int16_t *>(jb.d_oyval);
+			rc = set->kind == CORDIC_JOBS_R2P
+				? launch_topolar(plan->cfg, (size_t)jb.n, jb.d_xval, jb.d_yval,
+					jb.d_oxval, reinterpret_cast<uint32_t *>(jb.d_oyval), stream,
+					true)
+				: set->kind == CORDIC_JOBS_MIX
+				? cordic_plan_mix16(plan, (size_t)jb.n, jb.phase0, jb.fcw, jb.index0,
+					x, y, ox, oy, stream)
+				: cordic_plan_p2r16(plan, (size_t)jb.n, x, y,
+					reinterpret_cast<const uint16_t *>(jb.d_phase), ox, oy, stream);
+			if (rc != CORDIC_OK)
+				return rc;
+		}
+		return CORDIC_OK;
+	}
 	if (set->kind >= CORDIC_JOBS_R2P) {
 		RotatorJob j;
 		if (set->kind != CORDIC_JOBS_R2P)
@@ -823,13 +918,13 @@ int cordic_plan_nco(const cordic_plan *plan, size_t n, uint32_t phase0,
 
 // 16-bit containers: the job carries the int16 / uint16 arrays behind its
 // int32 pointers (cordic_internal.h: RotatorJob::io16)
-namespace {
-int fits16(const cordic_config &c, bool phase_array)
+static int fits16(const cordic_config &c, bool phase_array)
 {
 	if (c.iw > 16 || c.ow > 16 || (phase_array && c.pw > 16))
 		return CORDIC_ERR_CONTAINER;
 	return CORDIC_OK;
 }
+namespace {
 template <typename T> const int32_t *as_i32(const T *p)
 {
 	return reinterpret_cast<const int32_t *>(p);
@@ -938,6 +1033,41 @@ int cordic_plan_nco16(const cordic_plan *plan, size_t n, uint32_t phase0,
 		j.queue = q;
 		return launch_rotator(plan->cfg, Feed::Nco_ConstXY, j, stream);
 	});
+}
+
+int cordic_mix16(const cordic_config *cfg, size_t n, uint32_t phase0, uint32_t fcw,
+		uint64_t index0, const int16_t *d_xval, const int16_t *d_yval,
+		int16_t *d_oxval, int16_t *d_oyval, void *stream)
+{
+	if (!cfg)
+		return CORDIC_ERR_ARGS;
+	if (int rc = fits16(*cfg, false))
+		return rc;
+	RotatorJob j = job16(d_xval, d_yval, nullptr, d_oxval, d_oyval, n);
+	j.phase0 = phase0; j.fcw = fcw; j.index0 = index0; j.xy_nco = true;
+	return launch_rotator(*cfg, Feed::PhaseArray_XYArray, j, stream);
+}
+
+// (the plan forms run the kernel of cordic_p2r16: the direction tables are for
+// the left-justified 64-bit container and are not attached)
+int cordic_plan_mix16(const cordic_plan *plan, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, const int16_t *d_xval,
+		const int16_t *d_yval, int16_t *d_oxval, int16_t *d_oyval, void *stream)
+{
+	if (!plan)
+		return CORDIC_ERR_ARGS;
+	return cordic_mix16(&plan->cfg, n, phase0, fcw, index0, d_xval, d_yval,
+			d_oxval, d_oyval, stream);
+}
+
+int cordic_plan_p2r16(const cordic_plan *plan, size_t n, const int16_t *d_xval,
+		const int16_t *d_yval, const uint16_t *d_phase, int16_t *d_oxval,
+		int16_t *d_oyval, void *stream)
+{
+	if (!plan)
+		return CORDIC_ERR_ARGS;
+	return cordic_p2r16(&plan->cfg, n, d_xval, d_yval, d_phase, d_oxval, d_oyval,
+			stream);
 }
 
 // ------------------------------------------------------------- table cores

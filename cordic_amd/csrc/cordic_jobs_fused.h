@@ -26,6 +26,20 @@ namespace dev { struct CoreParams; struct DirArgs; }
 int	launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &job,
 		const JobTables &tabs, void *stream);
 
+// The same for a set on int16 / uint16 arrays (cordic_jobset_create16), in
+// cordic_jobs_io16.hip: the tile forms of the kernels of cordic_p2r16 /
+// cordic_r2p16 (Narrow32 with Io16 loads and stores) and a trailing-sample
+// kernel of its own.  CORDIC_ERR_UNSUPPORTED: the single 16-bit call runs the
+// generic kernel on this core (WW > 32, wrap below WW 32, more than kDynStages
+// live stages, CORDIC_FLAG_FORCE_GENERIC) -- the caller runs the jobs one by one.
+int	launch_xy_jobs16(const cordic_config &cfg, int kind, const JobTables &tabs,
+		void *stream);
+
+// kernel arguments of a core (as make_params of cordic_kernels.hip) and the
+// CUs of the current device (< 0: no device), shared by the two launchers
+dev::CoreParams make_params_jobs(const cordic_config &c);
+int	jobs_cus_now();
+
 // ---- launchers of the tile kernels (cordic_jobs_rot.hip, cordic_jobs_rotw.hip,
 // cordic_jobs_pol.hip, cordic_jobs_xydir.hip); false: no instance
 //

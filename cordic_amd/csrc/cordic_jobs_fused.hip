@@ -13,7 +13,6 @@
 
 namespace cordic_amd {
 
-namespace {
 using dev::CoreParams;
 
 // Twin of make_params in cordic_kernels.hip (anonymous namespace there); the
@@ -44,7 +43,7 @@ CoreParams make_params_jobs(const cordic_config &c)
 	return kp;
 }
 
-int cus_now()
+int jobs_cus_now()
 {
 	int dev = 0, cus = 0;
 	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus,
@@ -52,7 +51,6 @@ int cus_now()
 		return -1;
 	return cus;
 }
-} // namespace
 
 int launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &j,
 		const JobTables &tabs, void *stream)
@@ -78,7 +76,7 @@ int launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &j
 		return CORDIC_ERR_UNSUPPORTED;
 	if (tabs.ntiles) {
 		const TileDescXY *tiles = reinterpret_cast<const TileDescXY *>(tabs.tiles);
-		const int cus = cus_now();
+		const int cus = jobs_cus_now();
 		if (cus < 0) {
 			(void)hipGetLastError();
 			return CORDIC_ERR_DEVICE;

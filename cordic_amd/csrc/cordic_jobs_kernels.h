@@ -18,15 +18,19 @@ namespace dev {
 
 // ---- rotator, per-sample vectors (CORDIC_JOBS_P2R_XY; CORDIC_JOBS_MIX when
 // kp.xy_nco): rotator_unrolled<C, kDynStages, NGEN, Feed::PhaseArray_XYArray,
-// true, Io32, UG> per tile.  A mixer tile's phases start from the descriptor's
-// {fcw, phase} pair (TileDescXY::in2), as in rotator_xydir<.., true>.
-template <typename C, int NGEN, bool UG>
+// true, IO, UG> per tile.  A mixer tile's phases start from the descriptor's
+// {fcw, phase} pair (TileDescXY::in2), as in rotator_xydir<.., true>.  IO = Io16
+// (Narrow32 only, cordic_jobs_io16.hip): the descriptor's addresses are those
+// of int16 / uint16 arrays, a lane moves 8 bytes per array per pass.
+template <typename C, int NGEN, bool UG, typename IO = Io32>
 __global__ __launch_bounds__(kBlock) void rotator_xy_tiles(CoreParams kp,
 		const TileDescXY *__restrict__ tiles, uint32_t ntiles)
 {
 	using T = typename std::conditional<C::wide, int64_t, int32_t>::type;
 	using U = typename std::make_unsigned<T>::type;
 	using Z = typename std::conditional<C::wide, int64_t, uint32_t>::type;
+	using IVec = typename IO::ivec;
+	using UVec = typename IO::uvec;
 	constexpr int NLIVE = kDynStages;
 	// the fold as four multiply-adds in a 64-bit container, stage 1 folded in
 	// on the left-justified ones (rotator_unrolled: kMadFold, fold1)
@@ -64,17 +68,17 @@ __global__ __launch_bounds__(kBlock) void rotator_xy_tiles(CoreParams kp,
 
 	for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
 		const TileDescXY d = tiles[t];
-		const i32x4g *__restrict__ xin = reinterpret_cast<const i32x4g *>((uintptr_t)d.in0);
-		const i32x4g *__restrict__ yin = reinterpret_cast<const i32x4g *>((uintptr_t)d.in1);
-		const u32x4g *__restrict__ phin = reinterpret_cast<const u32x4g *>((uintptr_t)d.in2);
-		i32x4g *__restrict__ ox = reinterpret_cast<i32x4g *>((uintptr_t)d.o0);
-		i32x4g *__restrict__ oy = reinterpret_cast<i32x4g *>((uintptr_t)d.o1);
+		const IVec *__restrict__ xin = reinterpret_cast<const IVec *>((uintptr_t)d.in0);
+		const IVec *__restrict__ yin = reinterpret_cast<const IVec *>((uintptr_t)d.in1);
+		const UVec *__restrict__ phin = reinterpret_cast<const UVec *>((uintptr_t)d.in2);
+		IVec *__restrict__ ox = reinterpret_cast<IVec *>((uintptr_t)d.o0);
+		IVec *__restrict__ oy = reinterpret_cast<IVec *>((uintptr_t)d.o1);
 		const uint32_t acc0 = (uint32_t)d.in2, fcw = (uint32_t)(d.in2 >> 32);
 		const size_t nvec = d.live;
 		size_t g = threadIdx.x;
 		// software prefetch (see rotator_unrolled)
-		u32x4g nph{};
-		i32x4g nx{}, ny{};
+		UVec nph{};
+		IVec nx{}, ny{};
 		if (g < nvec) {
 			if (!gen_phase)
 				nph = CORDIC_LOAD_IN(&phin[g]);
@@ -82,8 +86,8 @@ __global__ __launch_bounds__(kBlock) void rotator_xy_tiles(CoreParams kp,
 			ny = CORDIC_LOAD_IN(&yin[g]);
 		}
 		for (; g < nvec; g += kBlock) {
-			const u32x4 tph = nph;
-			const i32x4 tx = nx, ty = ny;
+			const u32x4 tph = IO::widen(nph);
+			const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
 			const size_t gn = g + kBlock;
 			if (gn < nvec) {
 				if (!gen_phase)
@@ -176,8 +180,8 @@ __global__ __launch_bounds__(kBlock) void rotator_xy_tiles(CoreParams kp,
 			}
 			apply_unit_gain<UG>(rx, kp);
 			apply_unit_gain<UG>(ry, kp);
-			CORDIC_STORE_OUT(true, &ox[g], rx);
-			CORDIC_STORE_OUT(true, &oy[g], ry);
+			CORDIC_STORE_OUT(true, &ox[g], IO::narrow(rx));
+			CORDIC_STORE_OUT(true, &oy[g], IO::narrow(ry));
 		}
 	}
 }
@@ -283,26 +287,28 @@ __global__ __launch_bounds__(kBlock) void topolar_ljw_tiles(CoreParams kp,
 }
 
 // ---- converter in the 32-bit container (wrap at WW 32): topolar_unrolled<
-// Narrow32, kDynStages, 0, true, Io32, UG> per tile
-template <bool UG>
+// Narrow32, kDynStages, 0, true, IO, UG> per tile
+template <bool UG, typename IO = Io32>
 __global__ __launch_bounds__(kBlock) void topolar_narrow_tiles(CoreParams kp,
 		const TileDescXY *__restrict__ tiles, uint32_t ntiles)
 {
+	using IVec = typename IO::ivec;
+	using UVec = typename IO::uvec;
 	for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
 		const TileDescXY d = tiles[t];
-		const i32x4g *__restrict__ xin = reinterpret_cast<const i32x4g *>((uintptr_t)d.in0);
-		const i32x4g *__restrict__ yin = reinterpret_cast<const i32x4g *>((uintptr_t)d.in1);
-		i32x4g *__restrict__ omag = reinterpret_cast<i32x4g *>((uintptr_t)d.o0);
-		u32x4g *__restrict__ oph = reinterpret_cast<u32x4g *>((uintptr_t)d.o1);
+		const IVec *__restrict__ xin = reinterpret_cast<const IVec *>((uintptr_t)d.in0);
+		const IVec *__restrict__ yin = reinterpret_cast<const IVec *>((uintptr_t)d.in1);
+		IVec *__restrict__ omag = reinterpret_cast<IVec *>((uintptr_t)d.o0);
+		UVec *__restrict__ oph = reinterpret_cast<UVec *>((uintptr_t)d.o1);
 		const size_t nvec = d.live;
 		size_t g = threadIdx.x;
-		i32x4g nx{}, ny{};		// software prefetch
+		IVec nx{}, ny{};		// software prefetch
 		if (g < nvec) {
 			nx = CORDIC_LOAD_IN(&xin[g]);
 			ny = CORDIC_LOAD_IN(&yin[g]);
 		}
 		for (; g < nvec; g += kBlock) {
-			const i32x4 tx = nx, ty = ny;
+			const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
 			const size_t gn = g + kBlock;
 			if (gn < nvec) {
 				nx = CORDIC_LOAD_IN(&xin[gn]);
@@ -333,8 +339,8 @@ __global__ __launch_bounds__(kBlock) void topolar_narrow_tiles(CoreParams kp,
 				rp[v] = (uint32_t)p[v] >> kp.pw_shl;	// rtl/topolar.v:269
 			}
 			apply_unit_gain<UG>(rm, kp);
-			CORDIC_STORE_OUT(true, &omag[g], rm);
-			CORDIC_STORE_OUT(true, &oph[g], rp);
+			CORDIC_STORE_OUT(true, &omag[g], IO::narrow(rm));
+			CORDIC_STORE_OUT(true, &oph[g], IO::narrow(rp));
 		}
 	}
 }

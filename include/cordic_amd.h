@@ -421,6 +421,8 @@ int	cordic_plan_nco(const cordic_plan *plan, size_t n,
  * 32, and under CORDIC_FLAG_FORCE_GENERIC / CORDIC_FLAG_NO_LJ.
  * Results: bit for bit those of the per-job calls.  cordic_jobset_path tells
  * which way the last run of a set went.
+ * The data-fed kinds on int16_t / uint16_t arrays: cordic_jobset_create16
+ * ("16-bit sample containers" below).
  * Cores without a table-seeded kernel (WW > 35, fewer than 11 live stages,
  * CORDIC_FLAG_NO_SEED) run constant-vector jobs one by one behind the same call.
  */
@@ -479,7 +481,13 @@ void	cordic_jobset_reap(void);
  * memory traffic.  They require IW <= 16 and OW <= 16, and PW <= 16 wherever
  * a phase ARRAY is read or written (the NCO forms take PW-bit scalars, any
  * PW); otherwise CORDIC_ERR_CONTAINER.  Arrays should be 8-byte aligned for
- * the vector path. */
+ * the vector path.
+ *
+ * The data-fed calls on 16-bit arrays: cordic_mix16 / cordic_plan_mix16 are
+ * cordic_mix on int16_t samples (PW-bit scalars, any PW), cordic_plan_p2r16 is
+ * cordic_p2r16 for a caller that holds a plan (PW <= 16: it reads a phase
+ * array).  All of them run the kernel of cordic_p2r16 -- the full recurrence in
+ * the 32-bit container; the plan's direction tables are not used. */
 int	cordic_p2r16(const cordic_config *cfg, size_t n,
 		const int16_t *d_xval, const int16_t *d_yval,
 		const uint16_t *d_phase,
@@ -501,6 +509,45 @@ int	cordic_plan_nco16(const cordic_plan *plan, size_t n,
 		uint32_t phase0, uint32_t fcw, uint64_t index0,
 		int32_t xval, int32_t yval,
 		int16_t *d_oxval, int16_t *d_oyval, void *stream);
+int	cordic_mix16(const cordic_config *cfg, size_t n,
+		uint32_t phase0, uint32_t fcw, uint64_t index0,
+		const int16_t *d_xval, const int16_t *d_yval,
+		int16_t *d_oxval, int16_t *d_oyval, void *stream);
+int	cordic_plan_mix16(const cordic_plan *plan, size_t n,
+		uint32_t phase0, uint32_t fcw, uint64_t index0,
+		const int16_t *d_xval, const int16_t *d_yval,
+		int16_t *d_oxval, int16_t *d_oyval, void *stream);
+int	cordic_plan_p2r16(const cordic_plan *plan, size_t n,
+		const int16_t *d_xval, const int16_t *d_yval,
+		const uint16_t *d_phase,
+		int16_t *d_oxval, int16_t *d_oyval, void *stream);
+
+/* Job sets on 16-bit arrays: the data-fed kinds (CORDIC_JOBS_R2P, _P2R_XY,
+ * _MIX) of "job sets" above with every sample array an int16_t / uint16_t one.
+ * cordic_job16 is cordic_job with 16-bit sample pointers, field for field.
+ * Container rule as for the single calls: IW <= 16 and OW <= 16, PW <= 16 for
+ * R2P and P2R_XY sets (phase arrays), any PW for MIX; CORDIC_ERR_CONTAINER
+ * otherwise.  The constant-vector kinds return CORDIC_ERR_UNSUPPORTED.
+ * Addresses need 2-byte alignment; jobs may be ragged and empty and must not
+ * overlap each other's outputs.  The result is an ordinary cordic_jobset (it
+ * remembers its container): cordic_plan_run_jobs, cordic_jobset_info / _path /
+ * _destroy and HIP graph capture work on it as on any other set.  It runs as
+ * ONE launch of the tile-reading form of cordic_p2r16's / cordic_r2p16's
+ * kernel (+ one small launch for trailing samples) on the cores whose single
+ * 16-bit call runs that kernel: WW <= 32, wrap at WW 32 only, no
+ * CORDIC_FLAG_FORCE_GENERIC; on any other core the jobs run one by one through
+ * the 16-bit single calls (CORDIC_JOBS_PATH_ONE_BY_ONE). */
+typedef struct cordic_job16 {
+	const uint16_t *d_phase;	/* P2R_XY: n values                     */
+	uint32_t phase0, fcw;		/* MIX: phase0 +                        */
+	uint64_t index0;		/*   (index0 + i) * fcw  (mod 2^PW)     */
+	int16_t	*d_oxval, *d_oyval;	/* n values each (R2P: o_mag, o_phase
+					 * as uint16_t)                         */
+	uint64_t n;			/* samples                              */
+	const int16_t *d_xval, *d_yval;	/* n values each                        */
+} cordic_job16;
+int	cordic_jobset_create16(const cordic_plan *plan, int kind, size_t njobs,
+		const cordic_job16 *jobs, cordic_jobset **set);
 
 /* Host only: the phase-side seed table of a core as 32-bit words
  *   [0] stages M  [1] bucket shift S  [2] nbuckets  [3] nleaves

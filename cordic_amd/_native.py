@@ -252,12 +252,24 @@ ABI = {
     "cordic_quad_destroy": (None, [C.c_void_p]),
     "cordic_quad_lookup": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "cordic_quad_nco": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                   C.c_uint32, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "cordic_quad_nco16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                   C.c_uint32, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "cordic_table_config_init": (C.c_int, [C.c_void_p] + [C.c_int] * 4),
     "cordic_table_values": (C.c_int, [C.c_void_p, _i32p, C.c_size_t]),
     "cordic_table_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cordic_table_destroy": (None, [C.c_void_p]),
     "cordic_table_lookup": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "cordic_table_nco": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                   C.c_uint32, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "cordic_table_nco16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                   C.c_uint32, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "cordic_p2r_host": (C.c_int, [_cfgp, C.c_size_t, _i32p, _i32p, C.c_int,
                                   _u32p, _i32p, _i32p]),
     "cordic_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
@@ -886,6 +898,16 @@ def _queue_info(fn, handle):
     return {k: int(getattr(q, k)) for k, _ in _CQueueInfo._fields_}
 
 
+def _osc_nco(fn, handle, sin, cos, n, phase0, fcw, index0, stream):
+    n = sin.numel() if n is None else n
+    if _is16(sin) or _is16(cos):
+        fn += "16"
+        _same16(fn, sin, cos)
+    _check(getattr(lib(), fn)(handle, n, phase0 & 0xffffffff, fcw & 0xffffffff,
+                              index0 & 0xffffffffffffffff, _ptr(sin), _ptr(cos),
+                              _stream(stream)), fn)
+
+
 class Table:
     """A -t tbl / -t qtr core: cordic_table_config + its device table."""
 
@@ -925,6 +947,14 @@ class Table:
         _check(lib().cordic_table_lookup(self._h, n, _ptr(phase), _ptr(val),
                                          _stream(stream)),
                "cordic_table_lookup")
+
+    def nco(self, sin, cos=None, n=None, phase0=0, fcw=1, index0=0,
+            stream=None):
+        """cordic_table_nco: sin[i] = the core at phase0 + (index0 + i) * fcw,
+        cos[i] = the core a quarter turn ahead (None: sine only); int16
+        tensors take the 16-bit entry point."""
+        _osc_nco("cordic_table_nco", self._h, sin, cos, n, phase0, fcw, index0,
+                 stream)
 
     def close(self):
         if self._h:
@@ -995,6 +1025,12 @@ class Quad:
         n = phase.numel() if n is None else n
         _check(lib().cordic_quad_lookup(self._h, n, _ptr(phase), _ptr(val),
                                         _stream(stream)), "cordic_quad_lookup")
+
+    def nco(self, sin, cos=None, n=None, phase0=0, fcw=1, index0=0,
+            stream=None):
+        """cordic_quad_nco: as Table.nco with o_sin of this core"""
+        _osc_nco("cordic_quad_nco", self._h, sin, cos, n, phase0, fcw, index0,
+                 stream)
 
     def close(self):
         if self._h:

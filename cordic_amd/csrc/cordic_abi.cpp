@@ -13,6 +13,7 @@
 #include "cordic_amd.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
+#include "cordic_table_nco.h"
 
 using namespace cordic_amd;
 
@@ -1215,6 +1216,41 @@ int cordic_table_lookup(const cordic_table *tbl, size_t n,
 	});
 }
 
+// the table as an oscillator (cordic_table_nco.hip): one store-only launch,
+// queued and counted like the lookup's
+static int table_nco(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, void *d_sin, void *d_cos, bool io16,
+		void *stream)
+{
+	if (!tbl)
+		return CORDIC_ERR_ARGS;
+	if (io16 && tbl->cfg.ow > 16)
+		return CORDIC_ERR_CONTAINER;
+	if (n == 0)
+		return CORDIC_OK;
+	if (!d_sin)
+		return CORDIC_ERR_ARGS;
+	return with_queue(tbl->queues, stream, [&](uint32_t *q) {
+		return launch_table_nco(tbl->cfg, tbl->d_tbl, tbl->d_lds16,
+				tbl->lds_mode, tbl->lds_entries, n, phase0, fcw, index0,
+				d_sin, d_cos, io16, stream, q);
+	});
+}
+
+int cordic_table_nco(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
+		void *stream)
+{
+	return table_nco(tbl, n, phase0, fcw, index0, d_sin, d_cos, false, stream);
+}
+
+int cordic_table_nco16(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
+		void *stream)
+{
+	return table_nco(tbl, n, phase0, fcw, index0, d_sin, d_cos, true, stream);
+}
+
 // ------------------------------------------------- quadratic sine core
 struct cordic_quad {
 	cordic_quad_config cfg;
@@ -1307,6 +1343,38 @@ int cordic_quad_lookup(const cordic_quad *core, size_t n, const uint32_t *d_phas
 		return launch_quad_lookup(core->cfg, core->d_tab, n, d_phase, d_sin,
 				stream, q);
 	});
+}
+
+static int quad_nco(const cordic_quad *core, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, void *d_sin, void *d_cos, bool io16,
+		void *stream)
+{
+	if (!core)
+		return CORDIC_ERR_ARGS;
+	if (io16 && core->cfg.ow > 16)
+		return CORDIC_ERR_CONTAINER;
+	if (n == 0)
+		return CORDIC_OK;
+	if (!d_sin)
+		return CORDIC_ERR_ARGS;
+	return with_queue(core->queues, stream, [&](uint32_t *q) {
+		return launch_quad_nco(core->cfg, core->d_tab, n, phase0, fcw, index0,
+				d_sin, d_cos, io16, stream, q);
+	});
+}
+
+int cordic_quad_nco(const cordic_quad *core, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
+		void *stream)
+{
+	return quad_nco(core, n, phase0, fcw, index0, d_sin, d_cos, false, stream);
+}
+
+int cordic_quad_nco16(const cordic_quad *core, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
+		void *stream)
+{
+	return quad_nco(core, n, phase0, fcw, index0, d_sin, d_cos, true, stream);
 }
 
 // Scratch of the clocked views.  cordic_*_reserve sizes it up front; a *_ticks

@@ -611,6 +611,23 @@ int	cordic_table_queue_info(const cordic_table *tbl, cordic_queue_info *info);
 /* d_val[i] = o_val of the core for i_phase = d_phase[i] (low PW bits) */
 int	cordic_table_lookup(const cordic_table *tbl, size_t n,
 		const uint32_t *d_phase, int32_t *d_val, void *stream);
+/* The table as an oscillator: no phase array, the kernel makes
+ *   p_i = (phase0 + (index0 + i) * fcw) mod 2^PW            (as cordic_nco)
+ * and stores d_sin[i] = o_val for i_phase = p_i and, unless d_cos is NULL,
+ * d_cos[i] = o_val for i_phase = p_i + 2^(PW-2): the core driven a quarter
+ * turn ahead, as two instances of it make a quadrature pair.  One launch on
+ * `stream`, queued, captured and counted as cordic_table_lookup is; a job cut
+ * by index0 into consecutive calls gives the bits of one call.  d_sin / d_cos:
+ * any 4-byte- (cordic_table_nco16: 2-byte-) aligned addresses that do not
+ * overlap; nothing outside [0, n) is written.  n == 0: CORDIC_OK.  The int16
+ * form needs OW <= 16 (CORDIC_ERR_CONTAINER otherwise; PW is free, there is no
+ * phase array) and stores the low 16 bits of the 32-bit form's values. */
+int	cordic_table_nco(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
+		void *stream);
+int	cordic_table_nco16(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
+		void *stream);
 /* which kernel serves this table: 0 = gather from the table in L2, 1 = packed
  * int16 copy of a quarter-wave table in LDS, 2 = full-wave table folded to its
  * first quadrant in LDS (OW <= 16, PW <= 17, and -- for 2 -- the generated
@@ -674,6 +691,15 @@ int	cordic_quad_queue_info(const cordic_quad *core, cordic_queue_info *info);
  * sign-extended OW-bit values */
 int	cordic_quad_lookup(const cordic_quad *core, size_t n,
 		const uint32_t *d_phase, int32_t *d_sin, void *stream);
+
+/* The core as an oscillator: cordic_table_nco's contract with o_sin of this
+ * core (d_cos[i] = o_sin for i_phase = p_i + 2^(PW-2)). */
+int	cordic_quad_nco(const cordic_quad *core, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
+		void *stream);
+int	cordic_quad_nco16(const cordic_quad *core, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
+		void *stream);
 
 /* ------------------------------------------- clocked view (streaming shim)
  *

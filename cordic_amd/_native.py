@@ -270,6 +270,23 @@ ABI = {
     "cordic_table_nco16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
                                    C.c_uint32, C.c_uint64, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]),
+    "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                             C.c_void_p,
+                                             C.POINTER(C.c_void_p)]),
+    "cordic_quad_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_void_p)]),
+    "cordic_quad_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                            C.c_void_p,
+                                            C.POINTER(C.c_void_p)]),
+    "cordic_oscbank_destroy": (None, [C.c_void_p]),
+    "cordic_oscbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32)]),
+    "cordic_oscbank_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cordic_oscbank_retune": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]),
     "cordic_p2r_host": (C.c_int, [_cfgp, C.c_size_t, _i32p, _i32p, C.c_int,
                                   _u32p, _i32p, _i32p]),
     "cordic_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
@@ -908,6 +925,79 @@ def _osc_nco(fn, handle, sin, cos, n, phase0, fcw, index0, stream):
                               _stream(stream)), fn)
 
 
+class _COscJob(C.Structure):
+    """cordic_osc_job / cordic_osc_job16 (the same layout)"""
+    _fields_ = [("phase0", C.c_uint32), ("fcw", C.c_uint32),
+                ("index0", C.c_uint64), ("n", C.c_uint64),
+                ("d_sin", C.c_void_p), ("d_cos", C.c_void_p)]
+
+
+class _COscTuning(C.Structure):
+    _fields_ = [("phase0", C.c_uint32), ("fcw", C.c_uint32),
+                ("index0", C.c_uint64)]
+
+
+_OSC_KEYS = ("phase0", "fcw", "index0", "n", "sin", "cos")
+
+
+class OscBank:
+    """cordic_oscbank: many oscillator jobs of one Table / Quad core, cut once
+    and run as one launch.  jobs: tuples (phase0, fcw, index0, n, sin, cos) or
+    dicts with those keys; sin / cos are tensors or device addresses, cos may
+    be None (sine only)."""
+
+    def __init__(self, core, fn, jobs, i16=False):
+        self.core = core           # the bank must go before its core handle
+        jobs = [tuple(jb.get(k) for k in _OSC_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = jobs          # the tensors behind the addresses
+        arr = (_COscJob * max(1, len(jobs)))()
+        for k, (phase0, fcw, index0, n, sin, cos) in enumerate(jobs):
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+            arr[k].fcw = (fcw or 0) & 0xffffffff
+            arr[k].index0 = (index0 or 0) & 0xffffffffffffffff
+            arr[k].n = n
+            arr[k].d_sin = _ptr(sin)
+            arr[k].d_cos = _ptr(cos)
+        fn += "16" if i16 else ""
+        h = C.c_void_p()
+        _check(getattr(lib(), fn)(core._h, len(jobs), arr, C.byref(h)), fn)
+        self._h = h
+
+    def info(self):
+        a, b, c = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        _check(lib().cordic_oscbank_info(self._h, C.byref(a), C.byref(b),
+                                         C.byref(c)), "cordic_oscbank_info")
+        return dict(samples=a.value, tiles=b.value, edge_samples=c.value)
+
+    def run(self, index_offset=0, stream=None):
+        _check(lib().cordic_oscbank_run(
+            self._h, index_offset & 0xffffffffffffffff, _stream(stream)),
+            "cordic_oscbank_run")
+
+    def retune(self, first, tunings, stream=None):
+        """tunings: (phase0, fcw, index0) of jobs first, first + 1, ..."""
+        arr = (_COscTuning * max(1, len(tunings)))()
+        for k, (phase0, fcw, index0) in enumerate(tunings):
+            arr[k].phase0 = phase0 & 0xffffffff
+            arr[k].fcw = fcw & 0xffffffff
+            arr[k].index0 = index0 & 0xffffffffffffffff
+        _check(lib().cordic_oscbank_retune(self._h, first, len(tunings), arr,
+                                           _stream(stream)),
+               "cordic_oscbank_retune")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cordic_oscbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Table:
     """A -t tbl / -t qtr core: cordic_table_config + its device table."""
 
@@ -955,6 +1045,10 @@ class Table:
         tensors take the 16-bit entry point."""
         _osc_nco("cordic_table_nco", self._h, sin, cos, n, phase0, fcw, index0,
                  stream)
+
+    def bank(self, jobs, i16=False):
+        """cordic_table_bank_create(16): the jobs as one OscBank"""
+        return OscBank(self, "cordic_table_bank_create", jobs, i16)
 
     def close(self):
         if self._h:
@@ -1031,6 +1125,10 @@ class Quad:
         """cordic_quad_nco: as Table.nco with o_sin of this core"""
         _osc_nco("cordic_quad_nco", self._h, sin, cos, n, phase0, fcw, index0,
                  stream)
+
+    def bank(self, jobs, i16=False):
+        """cordic_quad_bank_create(16): the jobs as one OscBank"""
+        return OscBank(self, "cordic_quad_bank_create", jobs, i16)
 
     def close(self):
         if self._h:

@@ -3,6 +3,7 @@
 // the device launchers (cordic_kernels.hip).
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +14,7 @@
 #include "cordic_amd.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
+#include "cordic_table_bank.h"
 #include "cordic_table_nco.h"
 
 using namespace cordic_amd;
@@ -1375,6 +1377,296 @@ int cordic_quad_nco16(const cordic_quad *core, size_t n, uint32_t phase0,
 		void *stream)
 {
 	return quad_nco(core, n, phase0, fcw, index0, d_sin, d_cos, true, stream);
+}
+
+// ------------------------------------------------------- oscillator banks
+// Many oscillator jobs of one table / quadratic core in one launch
+// (include/cordic_amd.h, "oscillator banks"; kernel: cordic_table_bank.hip).
+// The host cuts the jobs' output streams into tiles and edges once; tunings
+// stay a per-job device array that cordic_oscbank_retune rewrites in place.
+struct cordic_oscbank {
+	const cordic_table *tbl = nullptr;	// exactly one of the two
+	const cordic_quad *quad = nullptr;
+	int	device = -1;
+	bool	io16 = false;
+	// host mirror of the device tunings, the source of retune's copy.  It is
+	// pageable memory on purpose: the runtime reads a pageable source of a
+	// host-to-device copy into its own staging before hipMemcpyAsync returns
+	// (only pinned sources are read later, in stream order), so the mirror
+	// may be overwritten by the next retune, or freed by destroy, as soon as
+	// the call is back -- also when the CALLER's array is pinned memory.
+	// "The values are taken before the call returns" rests on that.
+	std::vector<cordic_osc_tuning> tunings;
+	OscTile *d_tiles = nullptr;
+	OscEdge *d_edges = nullptr;
+	cordic_osc_tuning *d_tunings = nullptr;
+	BankTables tabs;
+	uint64_t samples = 0;
+	uint32_t edge_samples = 0;
+};
+
+namespace {
+int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njobs,
+		const cordic_osc_job *jobs, cordic_oscbank **out, bool io16)
+{
+	if ((!tbl && !quad) || !out || (njobs && !jobs))
+		return CORDIC_ERR_ARGS;
+	const int ow = tbl ? tbl->cfg.ow : quad->cfg.ow;
+	const int pw = tbl ? tbl->cfg.pw : quad->cfg.pw;
+	if (io16 && ow > 16)
+		return CORDIC_ERR_CONTAINER;
+	if (quad && (size_t)quad->cfg.entries * 16 > 64 * 1024)
+		return CORDIC_ERR_UNSUPPORTED;
+	if (njobs > 0xffffffffull)
+		return CORDIC_ERR_ARGS;
+	const unsigned esize = io16 ? 2 : 4;
+	const uint64_t W = 16 / esize;
+	const uint32_t quarter = 1u << (pw - 2);
+	// one output stream of a job, cut on its own address
+	struct Stream { uint64_t addr, n, head, nvec; uint32_t job, lead; };
+	std::vector<Stream> streams;
+	uint64_t samples = 0, total_vecs = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_osc_job &jb = jobs[k];
+		if (jb.n == 0)
+			continue;
+		const uintptr_t s = (uintptr_t)jb.d_sin, c = (uintptr_t)jb.d_cos;
+		if (!s || (s & (esize - 1)) || (c & (esize - 1))
+				|| jb.n > (~(uint64_t)0 - (s > c ? s : c)) / esize)
+			return CORDIC_ERR_ARGS;
+		for (int q = 0; q < (c ? 2 : 1); q++) {
+			Stream st;
+			st.addr = q ? c : s;
+			st.n = jb.n;
+			st.head = ((16u - (st.addr & 15u)) & 15u) / esize;
+			if (st.head > st.n) st.head = st.n;
+			st.nvec = (st.n - st.head) / W;
+			st.job = (uint32_t)k;
+			st.lead = q ? quarter : 0u;
+			streams.push_back(st);
+			samples += jb.n;
+			total_vecs += st.nvec;
+		}
+	}
+	// no two output ranges may overlap: sorted by address, each against its
+	// successor
+	std::sort(streams.begin(), streams.end(),
+		[](const Stream &a, const Stream &b) { return a.addr < b.addr; });
+	for (size_t k = 1; k < streams.size(); k++)
+		if (streams[k - 1].addr + streams[k - 1].n * esize > streams[k].addr)
+			return CORDIC_ERR_ARGS;
+	int resident = tbl ? table_bank_resident(tbl->cfg, tbl->d_lds16, tbl->lds_mode,
+			tbl->lds_entries) : quad_bank_resident(quad->cfg);
+	if (resident < 0) {
+		(void)hipGetLastError();
+		resident = 512;
+	}
+	uint64_t with_vecs = 0;
+	for (const Stream &st : streams)
+		with_vecs += st.nvec != 0;
+	const uint32_t shift = bank_tile_shift(total_vecs, with_vecs, (uint64_t)resident);
+	const uint64_t T = (uint64_t)1 << shift;
+	uint64_t ntiles = 0;
+	for (const Stream &st : streams)
+		ntiles += (st.nvec + T - 1) / T;
+	// (at most two edges per stream: the edge list and its samples stay
+	// within 32 bits as well)
+	if (ntiles > 0xffffffffull || streams.size() > 0x0fffffffull)
+		return CORDIC_ERR_ARGS;
+	// (the streams are in address order and do not overlap: so are the tiles)
+	std::vector<OscTile> tiles;
+	std::vector<OscEdge> edges;
+	tiles.reserve((size_t)ntiles);
+	uint64_t edge_samples = 0;
+	for (const Stream &st : streams) {
+		if (st.head) {
+			edges.push_back(OscEdge{st.addr, 0u, (uint32_t)st.head, st.job, st.lead});
+			edge_samples += st.head;
+		}
+		for (uint64_t v0 = 0; v0 < st.nvec; v0 += T) {
+			const uint64_t live = st.nvec - v0 < T ? st.nvec - v0 : T;
+			const uint64_t first = st.head + v0 * W;
+			tiles.push_back(OscTile{st.addr + first * esize, (uint32_t)first,
+				(uint32_t)live, st.job, st.lead});
+		}
+		const uint64_t done = st.head + st.nvec * W;
+		if (done < st.n) {
+			edges.push_back(OscEdge{st.addr + done * esize, (uint32_t)done,
+				(uint32_t)(st.n - done), st.job, st.lead});
+			edge_samples += st.n - done;
+		}
+	}
+	cordic_oscbank *b = new (std::nothrow) cordic_oscbank;
+	if (!b)
+		return CORDIC_ERR_NOMEM;
+	b->tbl = tbl;
+	b->quad = quad;
+	b->io16 = io16;
+	b->samples = samples;
+	b->edge_samples = (uint32_t)edge_samples;
+	b->tunings.resize(njobs);
+	for (size_t k = 0; k < njobs; k++)
+		b->tunings[k] = cordic_osc_tuning{jobs[k].phase0, jobs[k].fcw, jobs[k].index0};
+	if (hipGetDevice(&b->device) != hipSuccess) {
+		(void)hipGetLastError();
+		b->device = -1;
+	}
+	auto upload = [](const void *src, size_t bytes, void **dst) {
+		if (!bytes)
+			return true;
+		return hipMalloc(dst, bytes) == hipSuccess
+			&& hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+	};
+	if (!upload(tiles.data(), tiles.size() * sizeof(OscTile), (void **)&b->d_tiles)
+			|| !upload(edges.data(), edges.size() * sizeof(OscEdge), (void **)&b->d_edges)
+			|| !upload(b->tunings.data(), njobs * sizeof(cordic_osc_tuning),
+				(void **)&b->d_tunings)) {
+		(void)hipGetLastError();
+		cordic_oscbank_destroy(b);
+		return CORDIC_ERR_DEVICE;
+	}
+	b->tabs.tiles = b->d_tiles;
+	b->tabs.edges = b->d_edges;
+	b->tabs.tunings = b->d_tunings;
+	b->tabs.ntiles = (uint32_t)tiles.size();
+	b->tabs.nedges = (uint32_t)edges.size();
+	b->tabs.tile_shift = shift;
+	*out = b;
+	return CORDIC_OK;
+}
+
+int oscbank_create16(const cordic_table *tbl, const cordic_quad *quad, size_t njobs,
+		const cordic_osc_job16 *jobs, cordic_oscbank **out)
+{
+	static_assert(sizeof(cordic_osc_job16) == sizeof(cordic_osc_job)
+		&& offsetof(cordic_osc_job16, phase0) == offsetof(cordic_osc_job, phase0)
+		&& offsetof(cordic_osc_job16, fcw) == offsetof(cordic_osc_job, fcw)
+		&& offsetof(cordic_osc_job16, index0) == offsetof(cordic_osc_job, index0)
+		&& offsetof(cordic_osc_job16, n) == offsetof(cordic_osc_job, n)
+		&& offsetof(cordic_osc_job16, d_sin) == offsetof(cordic_osc_job, d_sin)
+		&& offsetof(cordic_osc_job16, d_cos) == offsetof(cordic_osc_job, d_cos),
+		"cordic_osc_job16 is cordic_osc_job with 16-bit sample pointers");
+	if ((!tbl && !quad) || !out || (njobs && !jobs))
+		return CORDIC_ERR_ARGS;
+	// same layout; the pointers are never dereferenced on the host and every
+	// address is computed in bytes
+	std::vector<cordic_osc_job> wide(njobs);
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_osc_job16 &a = jobs[k];
+		wide[k] = cordic_osc_job{a.phase0, a.fcw, a.index0, a.n,
+			reinterpret_cast<int32_t *>(a.d_sin), reinterpret_cast<int32_t *>(a.d_cos)};
+	}
+	return oscbank_create(tbl, quad, njobs, wide.data(), out, true);
+}
+
+// the bank's device current?  (its tables hold device addresses)
+int oscbank_device(const cordic_oscbank *bank)
+{
+	int dev = -1;
+	if (hipGetDevice(&dev) != hipSuccess) {
+		(void)hipGetLastError();
+		return CORDIC_ERR_DEVICE;
+	}
+	return dev == bank->device ? CORDIC_OK : CORDIC_ERR_ARGS;
+}
+} // namespace
+
+int cordic_table_bank_create(const cordic_table *tbl, size_t njobs,
+		const cordic_osc_job *jobs, cordic_oscbank **bank)
+{
+	return oscbank_create(tbl, nullptr, njobs, jobs, bank, false);
+}
+
+int cordic_table_bank_create16(const cordic_table *tbl, size_t njobs,
+		const cordic_osc_job16 *jobs, cordic_oscbank **bank)
+{
+	return oscbank_create16(tbl, nullptr, njobs, jobs, bank);
+}
+
+int cordic_quad_bank_create(const cordic_quad *core, size_t njobs,
+		const cordic_osc_job *jobs, cordic_oscbank **bank)
+{
+	return oscbank_create(nullptr, core, njobs, jobs, bank, false);
+}
+
+int cordic_quad_bank_create16(const cordic_quad *core, size_t njobs,
+		const cordic_osc_job16 *jobs, cordic_oscbank **bank)
+{
+	return oscbank_create16(nullptr, core, njobs, jobs, bank);
+}
+
+void cordic_oscbank_destroy(cordic_oscbank *bank)
+{
+	if (!bank)
+		return;
+	if (bank->d_tiles) (void)hipFree(bank->d_tiles);
+	if (bank->d_edges) (void)hipFree(bank->d_edges);
+	if (bank->d_tunings) (void)hipFree(bank->d_tunings);
+	delete bank;
+}
+
+int cordic_oscbank_info(const cordic_oscbank *bank, uint64_t *samples,
+		uint32_t *tiles, uint32_t *edge_samples)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	if (samples) *samples = bank->samples;
+	if (tiles) *tiles = bank->tabs.ntiles;
+	if (edge_samples) *edge_samples = bank->edge_samples;
+	return CORDIC_OK;
+}
+
+int cordic_oscbank_run(const cordic_oscbank *bank, uint64_t index_offset,
+		void *stream)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	if (int rc = oscbank_device(bank))
+		return rc;
+	if (bank->samples == 0)
+		return CORDIC_OK;
+	// (PW <= 32: the low 32 bits of a sample index are all that matters)
+	const uint32_t off = (uint32_t)index_offset;
+	if (bank->tbl) {
+		const cordic_table *t = bank->tbl;
+		return with_queue(t->queues, stream, [&](uint32_t *q) {
+			return launch_table_bank(t->cfg, t->d_tbl, t->d_lds16, t->lds_mode,
+					t->lds_entries, bank->tabs, off, bank->io16, stream, q);
+		});
+	}
+	const cordic_quad *c = bank->quad;
+	return with_queue(c->queues, stream, [&](uint32_t *q) {
+		return launch_quad_bank(c->cfg, c->d_tab, bank->tabs, off, bank->io16,
+				stream, q);
+	});
+}
+
+int cordic_oscbank_retune(cordic_oscbank *bank, size_t first, size_t count,
+		const cordic_osc_tuning *tunings, void *stream)
+{
+	if (!bank || first > bank->tunings.size()
+			|| count > bank->tunings.size() - first || (count && !tunings))
+		return CORDIC_ERR_ARGS;
+	if (int rc = oscbank_device(bank))
+		return rc;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	if (st && hipStreamIsCapturing(st, &cs) != hipSuccess) {
+		(void)hipGetLastError();
+		return CORDIC_ERR_DEVICE;
+	}
+	if (cs != hipStreamCaptureStatusNone)
+		return CORDIC_ERR_UNSUPPORTED;
+	if (count == 0)
+		return CORDIC_OK;
+	std::copy(tunings, tunings + count, bank->tunings.begin() + (long)first);
+	if (hipMemcpyAsync(bank->d_tunings + first, bank->tunings.data() + first,
+			count * sizeof(cordic_osc_tuning), hipMemcpyHostToDevice, st)
+			!= hipSuccess) {
+		(void)hipGetLastError();
+		return CORDIC_ERR_DEVICE;
+	}
+	return CORDIC_OK;
 }
 
 // Scratch of the clocked views.  cordic_*_reserve sizes it up front; a *_ticks

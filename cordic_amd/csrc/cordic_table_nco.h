@@ -1,7 +1,8 @@
 // cordic_table_nco.h -- oscillator (phase-accumulator) forms of the table and
 // quadratic sine cores: the phase of sample i is phase0 + (index0 + i) * fcw,
 // made in the kernel, so the launch reads no sample array and only stores.
-// Launchers for cordic_abi.cpp, and (device side) the cores' sample functions.
+// Launchers for cordic_abi.cpp, and (device side) the cores' sample functions
+// and table layouts, shared with the oscillator banks (cordic_table_bank.hip).
 //
 // The sample functions RESTATE table_sample, the LDS sample of
 // table_lookup_lds, quad_sample and QuadParams of cordic_kernels.hip: that file
@@ -125,6 +126,62 @@ __device__ __forceinline__ int32_t quad_sample(const i32x4 e, uint32_t ph,
 	const int s = 32 - qp.ow;
 	return (int32_t)((w >> qp.xtra) << s) >> s;		// :308
 }
+
+typedef int16_t i16x8 __attribute__((ext_vector_type(8)));
+
+template <typename T> struct OutVec;
+template <> struct OutVec<int32_t> { typedef i32x4 type; };
+template <> struct OutVec<int16_t> { typedef i16x8 type; };
+
+// ---- the layouts: stage() fills the block's LDS copy (if any; blocks of 1024
+// threads) and returns what sample() gathers from
+template <bool QUARTER> struct CoreL2 {
+	typedef int32_t entry;
+	const int32_t *tbl;
+	int pw, ow;
+	__device__ __forceinline__ const entry *stage(unsigned char *) const { return tbl; }
+	__device__ __forceinline__ int32_t sample(const entry *t, uint32_t ph) const
+	{
+		return table_sample<QUARTER>(t, ph, pw, ow);
+	}
+};
+
+template <int MODE, typename E> struct CoreLds {
+	typedef E entry;
+	const E *packed;
+	int entries, pw, ow;
+	__device__ __forceinline__ const entry *stage(unsigned char *raw) const
+	{
+		E *lds = reinterpret_cast<E *>(raw);
+		for (int i = threadIdx.x; i < entries; i += 1024)
+			lds[i] = packed[i];
+		__syncthreads();
+		return lds;
+	}
+	__device__ __forceinline__ int32_t sample(const entry *lds, uint32_t ph) const
+	{
+		return table_sample_lds<MODE, E>(lds, ph, pw, ow);
+	}
+};
+
+struct CoreQuad {
+	typedef i32x4 entry;
+	const i32x4 *tab;
+	QuadParams qp;
+	__device__ __forceinline__ const entry *stage(unsigned char *raw) const
+	{
+		i32x4 *lds = reinterpret_cast<i32x4 *>(raw);
+		for (int i = threadIdx.x; i < (1 << qp.lgtbl); i += 1024)
+			lds[i] = tab[i];
+		__syncthreads();
+		return lds;
+	}
+	__device__ __forceinline__ int32_t sample(const entry *lds, uint32_t ph) const
+	{
+		const uint32_t imask = (1u << qp.lgtbl) - 1u;
+		return quad_sample(lds[(ph >> (qp.dxbits - 1)) & imask], ph, qp);
+	}
+};
 
 } // namespace tnco
 } // namespace cordic_amd

@@ -26,66 +26,10 @@ namespace tnco {
 
 using dev::for_each_queued_tile;
 
-typedef int16_t i16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct OutVec;
-template <> struct OutVec<int32_t> { typedef i32x4 type; };
-template <> struct OutVec<int16_t> { typedef i16x8 type; };
-
 struct NcoArgs {
 	uint32_t base;		// phase0 + (uint32_t)index0 * fcw
 	uint32_t fcw;
 	uint32_t quarter;	// 2^(PW-2): the cosine's lead
-};
-
-// ---- the layouts: stage() fills the block's LDS copy (if any) and returns
-// what sample() gathers from
-template <bool QUARTER> struct CoreL2 {
-	typedef int32_t entry;
-	const int32_t *tbl;
-	int pw, ow;
-	__device__ __forceinline__ const entry *stage(unsigned char *) const { return tbl; }
-	__device__ __forceinline__ int32_t sample(const entry *t, uint32_t ph) const
-	{
-		return table_sample<QUARTER>(t, ph, pw, ow);
-	}
-};
-
-template <int MODE, typename E> struct CoreLds {
-	typedef E entry;
-	const E *packed;
-	int entries, pw, ow;
-	__device__ __forceinline__ const entry *stage(unsigned char *raw) const
-	{
-		E *lds = reinterpret_cast<E *>(raw);
-		for (int i = threadIdx.x; i < entries; i += 1024)
-			lds[i] = packed[i];
-		__syncthreads();
-		return lds;
-	}
-	__device__ __forceinline__ int32_t sample(const entry *lds, uint32_t ph) const
-	{
-		return table_sample_lds<MODE, E>(lds, ph, pw, ow);
-	}
-};
-
-struct CoreQuad {
-	typedef i32x4 entry;
-	const i32x4 *tab;
-	QuadParams qp;
-	__device__ __forceinline__ const entry *stage(unsigned char *raw) const
-	{
-		i32x4 *lds = reinterpret_cast<i32x4 *>(raw);
-		for (int i = threadIdx.x; i < (1 << qp.lgtbl); i += 1024)
-			lds[i] = tab[i];
-		__syncthreads();
-		return lds;
-	}
-	__device__ __forceinline__ int32_t sample(const entry *lds, uint32_t ph) const
-	{
-		const uint32_t imask = (1u << qp.lgtbl) - 1u;
-		return quad_sample(lds[(ph >> (qp.dxbits - 1)) & imask], ph, qp);
-	}
 };
 
 // elements in front of the first 16-byte boundary of `p` (at most n)

@@ -319,6 +319,31 @@ ABI = {
                                      C.c_void_p, C.c_void_p]),
     "cordic_quality_p2r_result": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cordic_quality_r2p_result": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cordic_quality_create_quad": (C.c_int, [C.c_void_p,
+                                             C.POINTER(C.c_void_p)]),
+    "cordic_quality_create_table": (C.c_int, [C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
+    "cordic_quality_sine": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "cordic_quality_sine16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "cordic_quality_sine_nco": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                          C.c_uint32, C.c_uint64, C.c_void_p,
+                                          C.c_void_p]),
+    "cordic_quality_sine_nco16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                            C.c_uint32, C.c_uint32,
+                                            C.c_uint64, C.c_void_p,
+                                            C.c_void_p]),
+    "cordic_quality_sine_result": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cordic_sfdr_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "cordic_sfdr_destroy": (None, [C.c_void_p]),
+    "cordic_sfdr_load_iq": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_sfdr_load_sine": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64,
+                                        C.c_void_p, C.c_void_p]),
+    "cordic_sfdr_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_sfdr_bins": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64,
+                                   C.c_void_p]),
     "cordic_fill_circle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_uint64, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p]),
@@ -1247,6 +1272,21 @@ class _CR2PQuality(C.Structure):
                     "pass_phase", "pass_mag", "pass")])
 
 
+class _CSineQuality(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("max_err", C.c_double),
+                ("max_err_index", C.c_uint64), ("max_err_phase", C.c_uint32),
+                ("max_val", C.c_int32), ("min_val", C.c_int32),
+                ("scale", C.c_double), ("tbl_err", C.c_double),
+                ("limit", C.c_double), ("judged", C.c_int32),
+                ("pass", C.c_int32)]
+
+
+class _CSfdrResult(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("master", C.c_double),
+                ("spur", C.c_double), ("spur_bin", C.c_uint64),
+                ("sfdr_dbc", C.c_double)]
+
+
 def _as_dict(st):
     return {k: getattr(st, k) for k, _ in st._fields_}
 
@@ -1256,11 +1296,24 @@ class Quality:
     (bench/cpp/cordic_tb.cpp:223-337, topolar_tb.cpp:222-315), reduced on the
     device; calls accumulate until reset()."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, _create="cordic_quality_create"):
         self.cfg = cfg
         self._h = C.c_void_p()
-        _check(lib().cordic_quality_create(cfg.ref, C.byref(self._h)),
-               "cordic_quality_create")
+        # (Quad / Table objects carry their config struct as .c)
+        ref = cfg.ref if hasattr(cfg, "ref") else C.byref(getattr(cfg, "c", cfg))
+        _check(getattr(lib(), _create)(ref, C.byref(self._h)), _create)
+
+    @classmethod
+    def for_quad(cls, quadcfg):
+        """statistics of a -t qtbl core (a Quad or its cordic_quad_config):
+        sine(), sine_nco(), sine_result()"""
+        return cls(quadcfg, "cordic_quality_create_quad")
+
+    @classmethod
+    def for_table(cls, tablecfg):
+        """the same for a -t tbl / -t qtr core (a Table or its config); the
+        reference has no threshold for these: judged = 0"""
+        return cls(tablecfg, "cordic_quality_create_table")
 
     def reset(self, stream=None):
         _check(lib().cordic_quality_reset(self._h, _stream(stream)),
@@ -1291,6 +1344,32 @@ class Quality:
                                         _stream(stream)),
                "cordic_quality_r2p")
 
+    def sine(self, phase, val, n=None, stream=None):
+        """outputs of *_lookup on a phase array; int16 values take the 16-bit
+        entry point"""
+        n = phase.numel() if n is None else n
+        fn = "cordic_quality_sine16" if _is16(val) else "cordic_quality_sine"
+        _check(getattr(lib(), fn)(self._h, n, _ptr(phase), _ptr(val),
+                                  _stream(stream)), fn)
+
+    def sine_nco(self, val, n=None, phase0=0, fcw=1, index0=0, stream=None):
+        """outputs of *_nco / *_nco16 / a bank's job (a cos array: phase0 +
+        2^(PW-2)); int16 values take the 16-bit entry point"""
+        n = val.numel() if n is None else n
+        fn = ("cordic_quality_sine_nco16" if _is16(val)
+              else "cordic_quality_sine_nco")
+        _check(getattr(lib(), fn)(self._h, n, phase0 & 0xffffffff,
+                                  fcw & 0xffffffff,
+                                  index0 & 0xffffffffffffffff, _ptr(val),
+                                  _stream(stream)), fn)
+
+    def sine_result(self, raw=False):
+        """dict of cordic_sine_quality (raw: the struct's bytes)"""
+        r = _CSineQuality()
+        _check(lib().cordic_quality_sine_result(self._h, C.byref(r)),
+               "cordic_quality_sine_result")
+        return bytes(r) if raw else _as_dict(r)
+
     def p2r_result(self):
         r = _CP2RQuality()
         _check(lib().cordic_quality_p2r_result(self._h, C.byref(r)),
@@ -1306,6 +1385,56 @@ class Quality:
     def close(self):
         if self._h:
             lib().cordic_quality_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Sfdr:
+    """cordic_sfdr: 2^lgn complex doubles on the device, a forward fp64 FFT
+    and the reference benches' spur search (cordic_tb.cpp:340-371,
+    quadtbl_tb.cpp:185-219)."""
+
+    def __init__(self, lgn):
+        self.lgn = lgn
+        self._h = C.c_void_p()
+        _check(lib().cordic_sfdr_create(lgn, C.byref(self._h)),
+               "cordic_sfdr_create")
+
+    def load_iq(self, re, im, index0=0, n=None, stream=None):
+        n = re.numel() if n is None else n
+        _check(lib().cordic_sfdr_load_iq(self._h, n, index0, _ptr(re),
+                                         _ptr(im), _stream(stream)),
+               "cordic_sfdr_load_iq")
+
+    def load_sine(self, sin, index0=0, n=None, stream=None):
+        n = sin.numel() if n is None else n
+        _check(lib().cordic_sfdr_load_sine(self._h, n, index0, _ptr(sin),
+                                           _stream(stream)),
+               "cordic_sfdr_load_sine")
+
+    def run(self, stream=None):
+        r = _CSfdrResult()
+        _check(lib().cordic_sfdr_run(self._h, C.byref(r), _stream(stream)),
+               "cordic_sfdr_run")
+        return _as_dict(r)
+
+    def bins(self, first=0, count=None):
+        """bins of the last transform as a numpy complex128 array"""
+        import numpy as np
+        count = (1 << self.lgn) - first if count is None else count
+        out = np.empty(count, dtype=np.complex128)
+        _check(lib().cordic_sfdr_bins(self._h, first, count, out.ctypes.data),
+               "cordic_sfdr_bins")
+        return out
+
+    def close(self):
+        if self._h:
+            lib().cordic_sfdr_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

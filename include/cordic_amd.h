@@ -1056,7 +1056,8 @@ int	cordic_group_write(cordic_group *grp, int local_shard, int array,
  * the device, add the per-block partial sums up on the host (fixed grid, no
  * atomics: reproducible bit for bit) and apply the reference's thresholds.
  * A handle belongs to the device that was current at creation and to one
- * caller at a time; it accumulates either p2r or r2p statistics.
+ * caller at a time; it accumulates either p2r or r2p statistics (or, made by
+ * cordic_quality_create_quad / _table below, a sine core's).
  */
 typedef struct cordic_quality cordic_quality;
 
@@ -1123,6 +1124,118 @@ int	cordic_quality_r2p_result(cordic_quality *q, cordic_r2p_quality *out);
  * fed, topolar_tb.cpp:142, so they are self-consistent either way). */
 int	cordic_fill_circle(int32_t *d_x, int32_t *d_y, size_t n, uint64_t index0,
 		int lgnsamples, int iw, int pw, void *stream);
+
+/* The sine-producing cores (-t qtbl, -t tbl, -t qtr): bench/cpp/quadtbl_tb.cpp
+ * :146-179 compares every output with sin(2 pi p / 2^PW) * (2^(OW-1) - 1) and
+ * keeps the largest difference and the extreme output values; the quadratic
+ * core is judged against |TBL_ERR| + 2 (:176), the table cores have no bench
+ * and no threshold in the reference.  A handle from one of the two creates
+ * below does that over arrays the engine wrote -- *_lookup, *_nco, *_nco16 or
+ * a bank's job -- under the contract of the handles above: calls accumulate
+ * until cordic_quality_reset, fixed grid, no atomics, _result synchronises
+ * and finishes on the host, one device, one kind of statistic.
+ *
+ * The statistic is the reference's: ph = p * 2 pi / 2^PW evaluated as fp64
+ * sinpi(2 p / 2^PW) (the argument reduces exactly; the bench's (int) of a
+ * PW = 32 phase, :155, is immaterial by periodicity), scl = 2^(OW-1) - 1,
+ * err = |sin(ph) * scl - o| with o sign-extended from OW bits (the 16-bit
+ * forms hold the low 16 bits of the same value).  It consists of maxima and
+ * an integer minimum and maximum only -- no sums -- so a sweep fed in pieces
+ * gives a cordic_sine_quality that is BIT-IDENTICAL to the same sweep fed at
+ * once, whatever the cut (max_err_index counts samples in feeding order).
+ *
+ * CORDIC_ERR_ARGS: NULL handle / out-pointer / array with n > 0; a _sine* call
+ * on a handle from cordic_quality_create, or a _p2r / _nco / _r2p call (and
+ * their results) on a sine handle; _sine_result before any sample was fed.
+ * CORDIC_ERR_CONTAINER: a ...16 form on a core with OW > 16.  n == 0 is
+ * CORDIC_OK and the pointers are not looked at.
+ */
+typedef struct cordic_sine_quality {	/* quadtbl_tb.cpp:146-179           */
+	uint64_t n;			/* samples accumulated               */
+	double	max_err;		/* "MXERR": max |sin(2 pi p / 2^PW)
+					   * scale - o|                      */
+	uint64_t max_err_index;		/* sample, in feeding order, of the
+					   maximum (lowest index on ties)    */
+	uint32_t max_err_phase;		/* its PW-bit phase                  */
+	int32_t	max_val, min_val;	/* "MXVAL" / "MNVAL": both start at
+					   0, as the bench's do (:147)       */
+	double	scale;			/* 2^(OW-1) - 1                      */
+	double	tbl_err;		/* TBL_ERR of the quadratic core; 0
+					   for table cores                   */
+	double	limit;			/* |TBL_ERR| + 2 (:176); 0 when not
+					   judged                            */
+	int32_t	judged, pass;		/* judged = 0 for -t tbl / -t qtr (no
+					   reference threshold): pass is 1   */
+} cordic_sine_quality;
+
+int	cordic_quality_create_quad(const cordic_quad_config *cfg, cordic_quality **q);
+int	cordic_quality_create_table(const cordic_table_config *cfg, cordic_quality **q);
+/* outputs of cordic_quad_lookup / cordic_table_lookup: phases from an array
+ * (low PW bits taken, as the core takes them) */
+int	cordic_quality_sine(cordic_quality *q, size_t n, const uint32_t *d_phase,
+		const int32_t *d_val, void *stream);
+int	cordic_quality_sine16(cordic_quality *q, size_t n, const uint32_t *d_phase,
+		const int16_t *d_val, void *stream);
+/* outputs of cordic_*_nco / cordic_*_nco16 / a bank's job: the phases are the
+ * closed form p_i = phase0 + (index0 + i) * fcw mod 2^PW.  A d_cos array is
+ * judged by passing phase0 + 2^(PW-2). */
+int	cordic_quality_sine_nco(cordic_quality *q, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, const int32_t *d_val, void *stream);
+int	cordic_quality_sine_nco16(cordic_quality *q, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, const int16_t *d_val, void *stream);
+int	cordic_quality_sine_result(cordic_quality *q, cordic_sine_quality *out);
+
+/* ------------------------------------------ SFDR of a full sweep (fp64 FFT)
+ *
+ * The other half of the benches' report (bench/cpp/cordic_tb.cpp:340-371,
+ * bench/cpp/quadtbl_tb.cpp:185-219): the outputs of one turn of the phase
+ * ramp as a complex signal, transformed, bin 1 (the tone) against the largest
+ * other bin.  The reference does it on the host with FFTW and gives up at
+ * PW >= 26; a cordic_sfdr keeps 2^lgn complex doubles on the device, twice
+ * (workspace 2 * 16 B * 2^lgn on the device current at create, to which the
+ * handle belongs), and transforms between the two buffers: the forward DFT
+ * X[k] = sum_j x[j] e^{-2 pi i jk/N} (the sign of FFTW's -1 and of
+ * numpy.fft.fft: an ascending ramp's tone lands in bin 1), Stockham autosort,
+ * radix 4 with one radix-2 stage when lgn is odd, twiddles from fp64 sincospi
+ * of exact dyadic fractions.  No FFT library is linked.
+ *
+ * A sweep is loaded in any number of pieces, in any order, every sample
+ * exactly once (the caller's contract; the handle only counts samples), then
+ * transformed.  cordic_sfdr_run consumes the loaded samples: the next sweep is
+ * loaded in full again.  The loads are launches on `stream`; run is launched
+ * there and synchronises it.
+ *
+ * CORDIC_ERR_ARGS: NULL handle / out-pointer / array with n > 0, lgn outside
+ * 1..30, a load range beyond 2^lgn, cordic_sfdr_run unless exactly 2^lgn
+ * samples were loaded since the last run, cordic_sfdr_bins without a
+ * transform (or after a later load) or beyond 2^lgn, another device current.
+ * CORDIC_ERR_NOMEM: the workspace could not be allocated.
+ */
+typedef struct cordic_sfdr cordic_sfdr;
+typedef struct cordic_sfdr_result {
+	uint64_t n;			/* 2^lgn                             */
+	double	master;			/* |X[1]|^2                          */
+	double	spur;			/* max(|X[0]|^2, |X[k]|^2, k >= 2)   */
+	uint64_t spur_bin;		/* a bin that attains it (lowest on
+					   exact ties)                       */
+	double	sfdr_dbc;		/* 10 log10(master / spur)           */
+} cordic_sfdr_result;
+
+int	cordic_sfdr_create(int lgn, cordic_sfdr **s);
+void	cordic_sfdr_destroy(cordic_sfdr *s);
+/* samples index0 .. index0 + n - 1 of the sweep.  _iq: point k = re[k] + j
+ * im[k] (cordic_tb.cpp:349-352).  _sine: the core's own quadrature pair,
+ * im[k] = s[k] and re[(k - N/4) mod N] = s[k] (quadtbl_tb.cpp:194-197). */
+int	cordic_sfdr_load_iq(cordic_sfdr *s, size_t n, uint64_t index0,
+		const int32_t *d_re, const int32_t *d_im, void *stream);
+int	cordic_sfdr_load_sine(cordic_sfdr *s, size_t n, uint64_t index0,
+		const int32_t *d_sin, void *stream);
+/* transform + spur search (per-block maxima, finished on the host) */
+int	cordic_sfdr_run(cordic_sfdr *s, cordic_sfdr_result *out, void *stream);
+/* bins first .. first + count - 1 of the last transform as (re, im) pairs of
+ * doubles into HOST memory */
+int	cordic_sfdr_bins(cordic_sfdr *s, uint64_t first, uint64_t count,
+		double *host_re_im);
 
 /* Host-array entry points: the same calls on arrays in HOST memory -- the
  * reference bench's own containers (`int` arrays filled and read by the CPU,

@@ -1,7 +1,8 @@
 // cordic_table_bank.h -- oscillator banks: many cordic_table_nco /
 // cordic_quad_nco jobs of one core in ONE launch (include/cordic_amd.h,
-// "oscillator banks").  The tables the host cuts at create (cordic_abi.cpp) and
-// the launchers of the kernel that walks them (cordic_table_bank.hip).
+// "oscillator banks").  The tables the host cuts at create
+// (cordic_abi_table.cpp) and the launchers of the kernel that walks them
+// (cordic_table_bank.hip).
 // Host-visible types only.
 //
 // No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py

@@ -2,7 +2,7 @@
 // or quadratic core (each cordic_table_nco / cordic_quad_nco with a phase0 /
 // fcw / index0 / length / output arrays of its own) as ONE store-only launch.
 //
-// The host (cordic_abi.cpp: oscbank_create) cuts every output stream -- a job's
+// oscbank_create (cordic_abi_table.cpp) cuts every output stream -- a job's
 // d_sin is one, its d_cos another -- on its own address into [head | 16-byte
 // aligned vectors | tail], the cut cordic_table_nco.hip makes in its kernel.
 // The aligned part becomes tiles (OscTile: whole vectors of one stream), sorted

@@ -1,8 +1,9 @@
 // cordic_table_nco.h -- oscillator (phase-accumulator) forms of the table and
 // quadratic sine cores: the phase of sample i is phase0 + (index0 + i) * fcw,
 // made in the kernel, so the launch reads no sample array and only stores.
-// Launchers for cordic_abi.cpp, and (device side) the cores' sample functions
-// and table layouts, shared with the oscillator banks (cordic_table_bank.hip).
+// Launchers for cordic_abi_table.cpp, and (device side) the cores' sample
+// functions and table layouts, shared with the oscillator banks
+// (cordic_table_bank.hip).
 //
 // The sample functions RESTATE table_sample, the LDS sample of
 // table_lookup_lds, quad_sample and QuadParams of cordic_kernels.hip: that file

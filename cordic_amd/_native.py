@@ -270,6 +270,26 @@ ABI = {
     "cordic_table_nco16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
                                    C.c_uint32, C.c_uint64, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "cordic_fm_workspace": (C.c_size_t, [C.c_size_t]),
+    "cordic_phase_accumulate": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "cordic_table_fm": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "cordic_table_fm16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "cordic_quad_fm": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "cordic_quad_fm16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_void_p)]),
     "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -950,6 +970,47 @@ def _osc_nco(fn, handle, sin, cos, n, phase0, fcw, index0, stream):
                               _stream(stream)), fn)
 
 
+def fm_workspace(n):
+    """cordic_fm_workspace: bytes of device scratch a modulated oscillator
+    call of n samples needs (16-byte aligned)"""
+    return int(lib().cordic_fm_workspace(n))
+
+
+def _fm_work(work, n):
+    """The caller owns the scratch, as in the C ABI: it has to outlive the
+    call on the stream, which only the caller can see to."""
+    if work is None and n:
+        raise TypeError("work: a device buffer of fm_workspace(n) bytes")
+    return work
+
+
+def phase_accumulate(fcw, phase, pm=None, n=None, phase0=0, acc=None,
+                     work=None, stream=None):
+    """cordic_phase_accumulate: phase[i] = phase0 + acc[0] + fcw[0] + .. +
+    fcw[i-1] + pm[i] (mod 2^32); acc (a one-word device tensor, optional)
+    carries the sum from call to call; phase may be fcw itself.  work: device
+    scratch of fm_workspace(n) bytes (16-byte aligned), the caller's."""
+    n = fcw.numel() if n is None else n
+    work = _fm_work(work, n)
+    st = _stream(stream)
+    _check(lib().cordic_phase_accumulate(n, _ptr(fcw), _ptr(pm),
+                                         phase0 & 0xffffffff, _ptr(acc),
+                                         _ptr(phase), _ptr(work), st),
+           "cordic_phase_accumulate")
+
+
+def _osc_fm(fn, handle, fcw, sin, cos, pm, n, phase0, acc, work, stream):
+    n = fcw.numel() if n is None else n
+    if _is16(sin) or _is16(cos):
+        fn += "16"
+        _same16(fn, sin, cos)
+    work = _fm_work(work, n)
+    st = _stream(stream)
+    _check(getattr(lib(), fn)(handle, n, _ptr(fcw), _ptr(pm),
+                              phase0 & 0xffffffff, _ptr(acc), _ptr(sin),
+                              _ptr(cos), _ptr(work), st), fn)
+
+
 class _COscJob(C.Structure):
     """cordic_osc_job / cordic_osc_job16 (the same layout)"""
     _fields_ = [("phase0", C.c_uint32), ("fcw", C.c_uint32),
@@ -1071,6 +1132,17 @@ class Table:
         _osc_nco("cordic_table_nco", self._h, sin, cos, n, phase0, fcw, index0,
                  stream)
 
+    def fm(self, fcw, sin, cos=None, pm=None, n=None, phase0=0, acc=None,
+           work=None, stream=None):
+        """cordic_table_fm: the oscillator with one tuning word per sample,
+        sin[i] = the core at phase0 + acc[0] + fcw[0] + .. + fcw[i-1] + pm[i],
+        cos[i] a quarter turn ahead (None: sine only); acc: optional one-word
+        device tensor that carries the accumulator from call to call; int16
+        tensors take the 16-bit entry point.  work: device scratch of
+        fm_workspace(n) bytes (16-byte aligned), the caller's."""
+        _osc_fm("cordic_table_fm", self._h, fcw, sin, cos, pm, n, phase0, acc,
+                work, stream)
+
     def bank(self, jobs, i16=False):
         """cordic_table_bank_create(16): the jobs as one OscBank"""
         return OscBank(self, "cordic_table_bank_create", jobs, i16)
@@ -1150,6 +1222,12 @@ class Quad:
         """cordic_quad_nco: as Table.nco with o_sin of this core"""
         _osc_nco("cordic_quad_nco", self._h, sin, cos, n, phase0, fcw, index0,
                  stream)
+
+    def fm(self, fcw, sin, cos=None, pm=None, n=None, phase0=0, acc=None,
+           work=None, stream=None):
+        """cordic_quad_fm: as Table.fm with o_sin of this core"""
+        _osc_fm("cordic_quad_fm", self._h, fcw, sin, cos, pm, n, phase0, acc,
+                work, stream)
 
     def bank(self, jobs, i16=False):
         """cordic_quad_bank_create(16): the jobs as one OscBank"""

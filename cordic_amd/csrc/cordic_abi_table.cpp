@@ -1,7 +1,7 @@
 // cordic_abi_table.cpp -- the C ABI's table-driven sine cores on the device:
-// table and quadratic handles, their lookups and oscillators, and the
-// oscillator banks cut for them (include/cordic_amd.h; the cores' host side:
-// cordic_abi.cpp).
+// table and quadratic handles, their lookups and oscillators (the modulated
+// ones included), and the oscillator banks cut for them (include/cordic_amd.h;
+// the cores' host side: cordic_abi.cpp).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "cordic_internal.h"
 #include "cordic_queue_ring.h"
 #include "cordic_table_bank.h"
+#include "cordic_table_fm.h"
 #include "cordic_table_nco.h"
 
 using namespace cordic_amd;
@@ -179,6 +180,46 @@ int cordic_table_nco16(const cordic_table *tbl, size_t n, uint32_t phase0,
 	});
 }
 
+// The argument checks of the modulated oscillator calls of either core `h`,
+// then their two launches (cordic_table_fm.hip).  No tile queue: these calls
+// take none and count nowhere.
+template <typename H, typename F>
+static int fm_call(const H *h, size_t n, const void *d_fcw, const void *d_sin,
+		const void *d_work, bool io16, F launch)
+{
+	if (!h)
+		return CORDIC_ERR_ARGS;
+	if (io16 && h->cfg.ow > 16)
+		return CORDIC_ERR_CONTAINER;
+	if (n == 0)
+		return CORDIC_OK;
+	if (!d_fcw || !d_sin || !d_work)
+		return CORDIC_ERR_ARGS;
+	return launch();
+}
+
+int cordic_table_fm(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int32_t *d_sin,
+		int32_t *d_cos, void *d_work, void *stream)
+{
+	return fm_call(tbl, n, d_fcw, d_sin, d_work, false, [&] {
+		return launch_table_fm(tbl->cfg, tbl->d_tbl, tbl->d_lds16, tbl->lds_mode,
+				tbl->lds_entries, n, d_fcw, d_pm, phase0, d_acc, d_sin,
+				d_cos, false, d_work, stream);
+	});
+}
+
+int cordic_table_fm16(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int16_t *d_sin,
+		int16_t *d_cos, void *d_work, void *stream)
+{
+	return fm_call(tbl, n, d_fcw, d_sin, d_work, true, [&] {
+		return launch_table_fm(tbl->cfg, tbl->d_tbl, tbl->d_lds16, tbl->lds_mode,
+				tbl->lds_entries, n, d_fcw, d_pm, phase0, d_acc, d_sin,
+				d_cos, true, d_work, stream);
+	});
+}
+
 // ------------------------------------------------- quadratic sine core
 struct cordic_quad {
 	cordic_quad_config cfg;
@@ -257,6 +298,26 @@ int cordic_quad_nco16(const cordic_quad *core, size_t n, uint32_t phase0,
 	return nco_call(core, n, d_sin, true, stream, [&](uint32_t *q) {
 		return launch_quad_nco(core->cfg, core->d_tab, n, phase0, fcw, index0,
 				d_sin, d_cos, true, stream, q);
+	});
+}
+
+int cordic_quad_fm(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int32_t *d_sin,
+		int32_t *d_cos, void *d_work, void *stream)
+{
+	return fm_call(core, n, d_fcw, d_sin, d_work, false, [&] {
+		return launch_quad_fm(core->cfg, core->d_tab, n, d_fcw, d_pm, phase0,
+				d_acc, d_sin, d_cos, false, d_work, stream);
+	});
+}
+
+int cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int16_t *d_sin,
+		int16_t *d_cos, void *d_work, void *stream)
+{
+	return fm_call(core, n, d_fcw, d_sin, d_work, true, [&] {
+		return launch_quad_fm(core->cfg, core->d_tab, n, d_fcw, d_pm, phase0,
+				d_acc, d_sin, d_cos, true, d_work, stream);
 	});
 }
 

@@ -790,6 +790,78 @@ int	cordic_oscbank_run(const cordic_oscbank *bank, uint64_t index_offset,
 int	cordic_oscbank_retune(cordic_oscbank *bank, size_t first, size_t count,
 		const cordic_osc_tuning *tunings, void *stream);
 
+/* ------------------------- frequency- and phase-modulated oscillators
+ *
+ * The oscillators above make a pure tone: one tuning word per call.  These
+ * take one tuning word PER SAMPLE (FM, FSK, chirps, a loop filter driving an
+ * LO) and, optionally, one phase word per sample (PM, PSK); the phase
+ * accumulator -- a prefix sum over d_fcw -- runs on the device.  With
+ *   start = phase0 + (d_acc ? *d_acc : 0)
+ *   a_i   = start + fcw[0] + ... + fcw[i-1]          (exclusive: a_0 = start,
+ *                                            as p_0 = phase0 in cordic_nco)
+ *   p_i   = a_i + (d_pm ? pm[i] : 0)
+ * everything mod 2^32, of which a core takes the low PW bits (cordic_nco's
+ * "mod 2^PW"):
+ *   cordic_phase_accumulate  d_phase[i] = p_i, all 32 bits: the phase array
+ *                            for any *_lookup or cordic_p2r* call
+ *   cordic_table_fm / cordic_quad_fm
+ *                            d_sin[i] = the core at p_i and, unless d_cos is
+ *                            NULL, d_cos[i] = the core at p_i + 2^(PW-2):
+ *                            cordic_table_nco's quadrature pair.  Constant
+ *                            tuning words f give the bits of
+ *                            cordic_*_nco(phase0, f, index0 = 0).
+ *   cordic_table_fm16 / cordic_quad_fm16
+ *                            the same into int16_t arrays: OW <= 16
+ *                            (CORDIC_ERR_CONTAINER otherwise), the low 16 bits
+ *                            of the 32-bit form's values, as cordic_table_nco16.
+ *
+ * d_acc (optional; a device word, 4-byte aligned) carries the accumulator from
+ * call to call: after the call *d_acc = start + fcw[0] + ... + fcw[n-1] (pm is
+ * not in it).  A job cut into consecutive calls that share a d_acc -- phase0
+ * in the first, 0 in the others: phase0 is added by every call -- gives the
+ * bits of one call with no host round trip in between, and a captured call
+ * replayed k times continues the waveform k times.
+ *
+ * d_work: caller-owned device scratch of at least cordic_fm_workspace(n)
+ * bytes, 16-byte aligned (the cordic_stream_workspace idiom), not shared by
+ * calls that may run at the same time.  cordic_fm_workspace is a pure host
+ * function: 0 for n == 0, a multiple of 16, non-decreasing in n, at most
+ * n / 512 + 65536.  The library allocates, copies and synchronises nothing in
+ * these calls: they are two kernel launches on `stream` (a reduction of d_fcw,
+ * then the scan with the core behind it; no block waits for another), legal
+ * inside a stream capture.  They take no tile queue: the cordic_*_queue_info
+ * counters do not move and a captured call uses up no queue slot.
+ *
+ * d_fcw, d_pm, d_phase: any 4-byte-aligned addresses; d_sin / d_cos as for
+ * cordic_table_nco (4-byte aligned, the 16-bit forms 2-byte, each array on its
+ * own alignment).  Nothing outside [0, n) of an output is written.
+ * d_phase == d_fcw (exactly) is allowed and works in place; inputs may alias
+ * each other; any other overlap of an output -- d_acc and d_work are outputs
+ * -- with an input or another output is CORDIC_ERR_ARGS, found on the host.
+ *
+ * n == 0: CORDIC_OK, nothing touched, *d_acc unchanged.  CORDIC_ERR_ARGS: a
+ * NULL handle (also with n == 0, as cordic_table_nco), with n > 0 a NULL
+ * d_fcw, d_sin, d_phase or d_work, a misaligned pointer, an overlap as above.
+ * CORDIC_ERR_UNSUPPORTED: a quadratic core whose tables do not fit 64 KiB
+ * (cordic_quad_nco answers the same).
+ */
+size_t	cordic_fm_workspace(size_t n);
+int	cordic_phase_accumulate(size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		uint32_t *d_phase, void *d_work, void *stream);
+int	cordic_table_fm(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		int32_t *d_sin, int32_t *d_cos, void *d_work, void *stream);
+int	cordic_table_fm16(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		int16_t *d_sin, int16_t *d_cos, void *d_work, void *stream);
+int	cordic_quad_fm(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		int32_t *d_sin, int32_t *d_cos, void *d_work, void *stream);
+int	cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		int16_t *d_sin, int16_t *d_cos, void *d_work, void *stream);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with

@@ -290,6 +290,15 @@ ABI = {
                                        C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    "cordic_fm_demod_workspace": (C.c_size_t, [C.c_size_t]),
+    "cordic_fm_demod_info": (C.c_int, [_cfgp, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32)]),
+    "cordic_fm_demod": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p, C.c_void_p,
+                                  C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_fm_demod16": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p, C.c_void_p,
+                                    C.c_uint32, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_void_p)]),
     "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -1649,6 +1658,46 @@ def r2p(cfg, x, y, mag, ophase, n=None, stream=None):
         return
     _check(lib().cordic_r2p(cfg.ref, n, _ptr(x), _ptr(y), _ptr(mag),
                             _ptr(ophase), _stream(stream)), "cordic_r2p")
+
+
+def fm_demod_workspace(n):
+    """cordic_fm_demod_workspace: bytes of device scratch an fm_demod call of
+    n samples needs (16-byte aligned)"""
+    return int(lib().cordic_fm_demod_workspace(n))
+
+
+def fm_demod_info(cfg):
+    """cordic_fm_demod_info: (fused, tile) -- whether 16-byte-aligned 32-bit
+    arrays of this core run the fused kernel, and its tile in samples"""
+    fused, tile = C.c_int32(0), C.c_int32(0)
+    _check(lib().cordic_fm_demod_info(cfg.ref, C.byref(fused), C.byref(tile)),
+           "cordic_fm_demod_info")
+    return int(fused.value), int(tile.value)
+
+
+def fm_demod(cfg, x, y, mag, freq, work, n=None, phase0=0, last=None,
+             stream=None):
+    """cordic_fm_demod: mag[i] as r2p, freq[i] = the converter's phase step
+    from sample i-1 to i, sign extended from PW bits; the phase in front of
+    sample 0 is phase0 + last[0] (mod 2^PW) and last (a one-word device
+    tensor, optional) receives the phase of sample n-1.  int16 arrays select
+    cordic_fm_demod16.  work: device scratch of fm_demod_workspace(n) bytes
+    (16-byte aligned), the caller's."""
+    n = x.numel() if n is None else n
+    if work is None and n:
+        raise TypeError("work: a device buffer of fm_demod_workspace(n) bytes")
+    if hasattr(work, "numel") and hasattr(work, "element_size") \
+            and work.numel() * work.element_size() < fm_demod_workspace(n):
+        raise ValueError("work: %d bytes, fm_demod_workspace(%d) = %d"
+                         % (work.numel() * work.element_size(), n,
+                            fm_demod_workspace(n)))
+    fn = "cordic_fm_demod"
+    if any(_is16(t) for t in (x, y, mag, freq)):
+        fn += "16"
+        _same16(fn, x, y, mag, freq)
+    _check(getattr(lib(), fn)(cfg.ref, n, _ptr(x), _ptr(y),
+                              phase0 & 0xffffffff, _ptr(last), _ptr(mag),
+                              _ptr(freq), _ptr(work), _stream(stream)), fn)
 
 
 class _CHostStats(C.Structure):

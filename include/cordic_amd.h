@@ -862,6 +862,93 @@ int	cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
 		int16_t *d_sin, int16_t *d_cos, void *d_work, void *stream);
 
+/* ------------------------------------------------------- FM demodulation
+ *
+ * The receive half of the block above: the converter (cordic_r2p) with its
+ * phase differenced from sample to sample inside the kernel -- what an FM or
+ * FSK discriminator or an AFC loop wants of atan2 -- and the exact inverse of
+ * cordic_phase_accumulate.  The core is any CORDIC_R2P or CORDIC_SR2P
+ * configuration that cordic_r2p accepts; any other mode: CORDIC_ERR_MODE, as
+ * there.  With ph_i the raw PW-bit word that cordic_r2p writes to d_ophase[i]
+ * for (x_i, y_i) and M = 2^PW:
+ *   prev    = (phase0 + (d_last ? *d_last : 0)) mod M
+ *   ph_-1   = prev
+ *   freq_i  = sext_PW((ph_i - ph_(i-1)) mod M)          i = 0 .. n-1
+ *   mag_i   = exactly cordic_r2p's d_omag[i] (CORDIC_FLAG_UNIT_GAIN included)
+ *   after the call, if d_last:  *d_last = ph_(n-1)
+ * freq_i is sign extended from PW bits into the container (PW = 32: the
+ * identity): as a signed number it is the instantaneous frequency in units of
+ * 2 pi / 2^PW per sample, and its low PW bits are a tuning word in the
+ * convention of cordic_phase_accumulate --
+ * cordic_phase_accumulate(n, freq, NULL, prev, ...) gives a_(i+1) = ph_i
+ * (mod M).  d_omag is required (the kernel is bound by its arithmetic, not by
+ * its stores).
+ *
+ * d_last (optional; a device word, 4-byte aligned) is d_acc's idiom: a job cut
+ * into consecutive calls that share a d_last -- phase0 in the first, 0 in the
+ * others: phase0 is added by every call -- gives the bits of one call with no
+ * host round trip in between, and a captured call replayed k times continues
+ * k times.  Bits of phase0 and *d_last above PW are ignored.
+ *
+ * cordic_fm_demod16: the same on int16_t arrays; IW, OW, PW <= 16
+ * (CORDIC_ERR_CONTAINER otherwise, the rule of cordic_r2p16); its values are
+ * the low 16 bits of the 32-bit form's.
+ *
+ * Launch contract: the library allocates, copies and synchronises nothing; the
+ * call is a fixed, small number of kernel launches on `stream` (at most four),
+ * no block waits for another block, it is legal inside a stream capture and it
+ * takes no tile queue.  Two paths, identical bits:
+ *   fused     32-bit arrays, all four on 16-byte boundaries (a condition of
+ *             this call, not of cordic_r2p), of a core that cordic_r2p runs
+ *             on its left-justified kernel (WW <= 34, no wrap, neither
+ *             CORDIC_FLAG_NO_LJ nor CORDIC_FLAG_FORCE_GENERIC): one
+ *             kernel converts and differences -- the 16 bytes per sample of
+ *             cordic_r2p -- and, where n is no multiple of 4 or d_last is
+ *             given, a tail of at most four samples follows in two small
+ *             launches.
+ *   fallback  everything else (wider cores, cores that wrap, the two flags,
+ *             arrays off the 16-byte grid, the 16-bit form): cordic_r2p's
+ *             launches with the phases in d_ofreq, one kernel that saves the
+ *             last phase of every 4096-sample tile to d_work, one that
+ *             differences in place.
+ * cordic_fm_demod_info (a pure host function): *fused = 1 if 16-byte-aligned
+ * 32-bit arrays of this core take the fused path, else 0; *tile = the samples
+ * of output a block of the fused kernel makes at a time (a multiple of 4), 0
+ * when not fused; either pointer may be NULL.  CORDIC_ERR_MODE / _ARGS as for
+ * the call.
+ *
+ * d_work: caller-owned device scratch of at least cordic_fm_demod_workspace(n)
+ * bytes, 16-byte aligned, not shared by calls that may run at the same time.
+ * cordic_fm_demod_workspace is a pure host function: 0 for n == 0, a multiple
+ * of 16, non-decreasing in n, at most n / 256 + 65536.
+ *
+ * *d_last is read by one thread of the first launch that needs it and written
+ * by a later launch of the call (the fallback: by the same thread, behind its
+ * read), so no block can see the value the call itself writes.
+ *
+ * The arrays are 4-byte aligned (2-byte in the 16-bit form); any n; nothing
+ * outside [0, n) of an output is written.  Inputs may alias each other; any
+ * overlap of an output -- d_omag, d_ofreq, d_last, d_work -- with an input or
+ * another output is CORDIC_ERR_ARGS, found on the host.
+ *
+ * n == 0: CORDIC_OK, nothing touched, *d_last unchanged.  CORDIC_ERR_ARGS: a
+ * NULL cfg; with n > 0 a NULL d_xval, d_yval, d_omag, d_ofreq or d_work, a
+ * misaligned pointer, an overlap as above.  What cordic_last_kernel() reports
+ * after these calls is unspecified (the tail and the fallback run the
+ * converter's own launches, which record theirs).
+ */
+size_t	cordic_fm_demod_workspace(size_t n);
+int	cordic_fm_demod_info(const cordic_config *cfg, int32_t *fused,
+		int32_t *tile);
+int	cordic_fm_demod(const cordic_config *cfg, size_t n,
+		const int32_t *d_xval, const int32_t *d_yval, uint32_t phase0,
+		uint32_t *d_last, int32_t *d_omag, int32_t *d_ofreq, void *d_work,
+		void *stream);
+int	cordic_fm_demod16(const cordic_config *cfg, size_t n,
+		const int16_t *d_xval, const int16_t *d_yval, uint32_t phase0,
+		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work,
+		void *stream);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with

@@ -28,6 +28,17 @@ struct cordic_table {
 	int16_t *d_lds16 = nullptr;
 	int	lds_mode = 0, lds_entries = 0;
 	QueueRing queues;	// optional: without it the chunk-per-block sweep runs
+
+	SineCore core() const
+	{
+		SineCore c;
+		c.t = cfg;
+		c.d_tbl = d_tbl;
+		c.d_lds16 = d_lds16;
+		c.lds_mode = lds_mode;
+		c.lds_entries = lds_entries;
+		return c;
+	}
 };
 
 namespace {
@@ -140,11 +151,13 @@ int cordic_table_lookup(const cordic_table *tbl, size_t n,
 	});
 }
 
+// ---------------------------------------- oscillators on either sine core
 // The argument checks of the oscillator calls of either core `h`, then its
-// store-only launch, queued and counted like the lookup's.
-template <typename H, typename F>
-static int nco_call(const H *h, size_t n, const void *d_sin, bool io16,
-		void *stream, F launch)
+// store-only launch (cordic_table_nco.hip), queued and counted like the
+// lookup's.
+template <typename H>
+static int nco_call(const H *h, size_t n, uint32_t phase0, uint32_t fcw,
+		uint64_t index0, void *d_sin, void *d_cos, bool io16, void *stream)
 {
 	if (!h)
 		return CORDIC_ERR_ARGS;
@@ -154,38 +167,19 @@ static int nco_call(const H *h, size_t n, const void *d_sin, bool io16,
 		return CORDIC_OK;
 	if (!d_sin)
 		return CORDIC_ERR_ARGS;
-	return with_queue(h->queues, stream, launch);
-}
-
-// the table as an oscillator (cordic_table_nco.hip)
-int cordic_table_nco(const cordic_table *tbl, size_t n, uint32_t phase0,
-		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
-		void *stream)
-{
-	return nco_call(tbl, n, d_sin, false, stream, [&](uint32_t *q) {
-		return launch_table_nco(tbl->cfg, tbl->d_tbl, tbl->d_lds16,
-				tbl->lds_mode, tbl->lds_entries, n, phase0, fcw, index0,
-				d_sin, d_cos, false, stream, q);
-	});
-}
-
-int cordic_table_nco16(const cordic_table *tbl, size_t n, uint32_t phase0,
-		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
-		void *stream)
-{
-	return nco_call(tbl, n, d_sin, true, stream, [&](uint32_t *q) {
-		return launch_table_nco(tbl->cfg, tbl->d_tbl, tbl->d_lds16,
-				tbl->lds_mode, tbl->lds_entries, n, phase0, fcw, index0,
-				d_sin, d_cos, true, stream, q);
+	return with_queue(h->queues, stream, [&](uint32_t *q) {
+		return launch_sine_nco(h->core(), n, phase0, fcw, index0, d_sin, d_cos,
+				io16, stream, q);
 	});
 }
 
 // The argument checks of the modulated oscillator calls of either core `h`,
 // then their two launches (cordic_table_fm.hip).  No tile queue: these calls
 // take none and count nowhere.
-template <typename H, typename F>
-static int fm_call(const H *h, size_t n, const void *d_fcw, const void *d_sin,
-		const void *d_work, bool io16, F launch)
+template <typename H>
+static int fm_call(const H *h, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, void *d_sin,
+		void *d_cos, bool io16, void *d_work, void *stream)
 {
 	if (!h)
 		return CORDIC_ERR_ARGS;
@@ -195,29 +189,38 @@ static int fm_call(const H *h, size_t n, const void *d_fcw, const void *d_sin,
 		return CORDIC_OK;
 	if (!d_fcw || !d_sin || !d_work)
 		return CORDIC_ERR_ARGS;
-	return launch();
+	return launch_sine_fm(h->core(), n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos,
+			io16, d_work, stream);
+}
+
+int cordic_table_nco(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
+		void *stream)
+{
+	return nco_call(tbl, n, phase0, fcw, index0, d_sin, d_cos, false, stream);
+}
+
+int cordic_table_nco16(const cordic_table *tbl, size_t n, uint32_t phase0,
+		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
+		void *stream)
+{
+	return nco_call(tbl, n, phase0, fcw, index0, d_sin, d_cos, true, stream);
 }
 
 int cordic_table_fm(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int32_t *d_sin,
 		int32_t *d_cos, void *d_work, void *stream)
 {
-	return fm_call(tbl, n, d_fcw, d_sin, d_work, false, [&] {
-		return launch_table_fm(tbl->cfg, tbl->d_tbl, tbl->d_lds16, tbl->lds_mode,
-				tbl->lds_entries, n, d_fcw, d_pm, phase0, d_acc, d_sin,
-				d_cos, false, d_work, stream);
-	});
+	return fm_call(tbl, n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, false,
+			d_work, stream);
 }
 
 int cordic_table_fm16(const cordic_table *tbl, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int16_t *d_sin,
 		int16_t *d_cos, void *d_work, void *stream)
 {
-	return fm_call(tbl, n, d_fcw, d_sin, d_work, true, [&] {
-		return launch_table_fm(tbl->cfg, tbl->d_tbl, tbl->d_lds16, tbl->lds_mode,
-				tbl->lds_entries, n, d_fcw, d_pm, phase0, d_acc, d_sin,
-				d_cos, true, d_work, stream);
-	});
+	return fm_call(tbl, n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, true,
+			d_work, stream);
 }
 
 // ------------------------------------------------- quadratic sine core
@@ -225,6 +228,15 @@ struct cordic_quad {
 	cordic_quad_config cfg;
 	int32_t *d_tab = nullptr;	// entries x {C, L, Q, 0}
 	QueueRing queues;
+
+	SineCore core() const
+	{
+		SineCore c;
+		c.quad = true;
+		c.q = cfg;
+		c.d_tbl = d_tab;
+		return c;
+	}
 };
 
 int cordic_quad_create(const cordic_quad_config *cfg, cordic_quad **core)
@@ -285,40 +297,30 @@ int cordic_quad_nco(const cordic_quad *core, size_t n, uint32_t phase0,
 		uint32_t fcw, uint64_t index0, int32_t *d_sin, int32_t *d_cos,
 		void *stream)
 {
-	return nco_call(core, n, d_sin, false, stream, [&](uint32_t *q) {
-		return launch_quad_nco(core->cfg, core->d_tab, n, phase0, fcw, index0,
-				d_sin, d_cos, false, stream, q);
-	});
+	return nco_call(core, n, phase0, fcw, index0, d_sin, d_cos, false, stream);
 }
 
 int cordic_quad_nco16(const cordic_quad *core, size_t n, uint32_t phase0,
 		uint32_t fcw, uint64_t index0, int16_t *d_sin, int16_t *d_cos,
 		void *stream)
 {
-	return nco_call(core, n, d_sin, true, stream, [&](uint32_t *q) {
-		return launch_quad_nco(core->cfg, core->d_tab, n, phase0, fcw, index0,
-				d_sin, d_cos, true, stream, q);
-	});
+	return nco_call(core, n, phase0, fcw, index0, d_sin, d_cos, true, stream);
 }
 
 int cordic_quad_fm(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int32_t *d_sin,
 		int32_t *d_cos, void *d_work, void *stream)
 {
-	return fm_call(core, n, d_fcw, d_sin, d_work, false, [&] {
-		return launch_quad_fm(core->cfg, core->d_tab, n, d_fcw, d_pm, phase0,
-				d_acc, d_sin, d_cos, false, d_work, stream);
-	});
+	return fm_call(core, n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, false,
+			d_work, stream);
 }
 
 int cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, int16_t *d_sin,
 		int16_t *d_cos, void *d_work, void *stream)
 {
-	return fm_call(core, n, d_fcw, d_sin, d_work, true, [&] {
-		return launch_quad_fm(core->cfg, core->d_tab, n, d_fcw, d_pm, phase0,
-				d_acc, d_sin, d_cos, true, d_work, stream);
-	});
+	return fm_call(core, n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, true,
+			d_work, stream);
 }
 
 // ------------------------------------------------------- oscillator banks
@@ -327,8 +329,9 @@ int cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
 // The host cuts the jobs' output streams into tiles and edges once; tunings
 // stay a per-job device array that cordic_oscbank_retune rewrites in place.
 struct cordic_oscbank {
-	const cordic_table *tbl = nullptr;	// exactly one of the two
-	const cordic_quad *quad = nullptr;
+	// the core and its handle's tile queues: the handle must outlive the bank
+	SineCore core;
+	const QueueRing *queues = nullptr;
 	int	device = -1;
 	bool	io16 = false;
 	// host mirror of the device tunings, the source of retune's copy.  It is
@@ -348,22 +351,21 @@ struct cordic_oscbank {
 };
 
 namespace {
-int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njobs,
+// `core` and `queues`: those of the table or quadratic handle the bank is for
+int oscbank_create(const SineCore &core, const QueueRing *queues, size_t njobs,
 		const cordic_osc_job *jobs, cordic_oscbank **out, bool io16)
 {
-	if ((!tbl && !quad) || !out || (njobs && !jobs))
+	if (!out || (njobs && !jobs))
 		return CORDIC_ERR_ARGS;
-	const int ow = tbl ? tbl->cfg.ow : quad->cfg.ow;
-	const int pw = tbl ? tbl->cfg.pw : quad->cfg.pw;
-	if (io16 && ow > 16)
+	if (io16 && core.ow() > 16)
 		return CORDIC_ERR_CONTAINER;
-	if (quad && (size_t)quad->cfg.entries * 16 > 64 * 1024)
+	if (core.quad && core.lds_bytes() > 64 * 1024)
 		return CORDIC_ERR_UNSUPPORTED;
 	if (njobs > 0xffffffffull)
 		return CORDIC_ERR_ARGS;
 	const unsigned esize = io16 ? 2 : 4;
 	const uint64_t W = 16 / esize;
-	const uint32_t quarter = 1u << (pw - 2);
+	const uint32_t quarter = core.quarter();
 	// one output stream of a job, cut on its own address
 	struct Stream { uint64_t addr, n, head, nvec; uint32_t job, lead; };
 	std::vector<Stream> streams;
@@ -380,7 +382,7 @@ int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njob
 			Stream st;
 			st.addr = q ? c : s;
 			st.n = jb.n;
-			st.head = ((16u - (st.addr & 15u)) & 15u) / esize;
+			st.head = head_elems((uintptr_t)st.addr, esize);
 			if (st.head > st.n) st.head = st.n;
 			st.nvec = (st.n - st.head) / W;
 			st.job = (uint32_t)k;
@@ -397,8 +399,7 @@ int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njob
 	for (size_t k = 1; k < streams.size(); k++)
 		if (streams[k - 1].addr + streams[k - 1].n * esize > streams[k].addr)
 			return CORDIC_ERR_ARGS;
-	int resident = tbl ? table_bank_resident(tbl->cfg, tbl->d_lds16, tbl->lds_mode,
-			tbl->lds_entries) : quad_bank_resident(quad->cfg);
+	int resident = sine_bank_resident(core);
 	if (resident < 0) {
 		(void)hipGetLastError();
 		resident = 512;
@@ -441,8 +442,8 @@ int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njob
 	cordic_oscbank *b = new (std::nothrow) cordic_oscbank;
 	if (!b)
 		return CORDIC_ERR_NOMEM;
-	b->tbl = tbl;
-	b->quad = quad;
+	b->core = core;
+	b->queues = queues;
 	b->io16 = io16;
 	b->samples = samples;
 	b->edge_samples = (uint32_t)edge_samples;
@@ -470,7 +471,7 @@ int oscbank_create(const cordic_table *tbl, const cordic_quad *quad, size_t njob
 	return CORDIC_OK;
 }
 
-int oscbank_create16(const cordic_table *tbl, const cordic_quad *quad, size_t njobs,
+int oscbank_create16(const SineCore &core, const QueueRing *queues, size_t njobs,
 		const cordic_osc_job16 *jobs, cordic_oscbank **out)
 {
 	static_assert(sizeof(cordic_osc_job16) == sizeof(cordic_osc_job)
@@ -481,7 +482,7 @@ int oscbank_create16(const cordic_table *tbl, const cordic_quad *quad, size_t nj
 		&& offsetof(cordic_osc_job16, d_sin) == offsetof(cordic_osc_job, d_sin)
 		&& offsetof(cordic_osc_job16, d_cos) == offsetof(cordic_osc_job, d_cos),
 		"cordic_osc_job16 is cordic_osc_job with 16-bit sample pointers");
-	if ((!tbl && !quad) || !out || (njobs && !jobs))
+	if (!out || (njobs && !jobs))
 		return CORDIC_ERR_ARGS;
 	// same layout; the pointers are never dereferenced on the host and every
 	// address is computed in bytes
@@ -491,7 +492,7 @@ int oscbank_create16(const cordic_table *tbl, const cordic_quad *quad, size_t nj
 		wide[k] = cordic_osc_job{a.phase0, a.fcw, a.index0, a.n,
 			reinterpret_cast<int32_t *>(a.d_sin), reinterpret_cast<int32_t *>(a.d_cos)};
 	}
-	return oscbank_create(tbl, quad, njobs, wide.data(), out, true);
+	return oscbank_create(core, queues, njobs, wide.data(), out, true);
 }
 
 // the bank's device current?  (its tables hold device addresses)
@@ -509,25 +510,33 @@ int oscbank_device(const cordic_oscbank *bank)
 int cordic_table_bank_create(const cordic_table *tbl, size_t njobs,
 		const cordic_osc_job *jobs, cordic_oscbank **bank)
 {
-	return oscbank_create(tbl, nullptr, njobs, jobs, bank, false);
+	if (!tbl)
+		return CORDIC_ERR_ARGS;
+	return oscbank_create(tbl->core(), &tbl->queues, njobs, jobs, bank, false);
 }
 
 int cordic_table_bank_create16(const cordic_table *tbl, size_t njobs,
 		const cordic_osc_job16 *jobs, cordic_oscbank **bank)
 {
-	return oscbank_create16(tbl, nullptr, njobs, jobs, bank);
+	if (!tbl)
+		return CORDIC_ERR_ARGS;
+	return oscbank_create16(tbl->core(), &tbl->queues, njobs, jobs, bank);
 }
 
 int cordic_quad_bank_create(const cordic_quad *core, size_t njobs,
 		const cordic_osc_job *jobs, cordic_oscbank **bank)
 {
-	return oscbank_create(nullptr, core, njobs, jobs, bank, false);
+	if (!core)
+		return CORDIC_ERR_ARGS;
+	return oscbank_create(core->core(), &core->queues, njobs, jobs, bank, false);
 }
 
 int cordic_quad_bank_create16(const cordic_quad *core, size_t njobs,
 		const cordic_osc_job16 *jobs, cordic_oscbank **bank)
 {
-	return oscbank_create16(nullptr, core, njobs, jobs, bank);
+	if (!core)
+		return CORDIC_ERR_ARGS;
+	return oscbank_create16(core->core(), &core->queues, njobs, jobs, bank);
 }
 
 void cordic_oscbank_destroy(cordic_oscbank *bank)
@@ -560,17 +569,8 @@ int cordic_oscbank_run(const cordic_oscbank *bank, uint64_t index_offset,
 		return CORDIC_OK;
 	// (PW <= 32: the low 32 bits of a sample index are all that matters)
 	const uint32_t off = (uint32_t)index_offset;
-	if (bank->tbl) {
-		const cordic_table *t = bank->tbl;
-		return with_queue(t->queues, stream, [&](uint32_t *q) {
-			return launch_table_bank(t->cfg, t->d_tbl, t->d_lds16, t->lds_mode,
-					t->lds_entries, bank->tabs, off, bank->io16, stream, q);
-		});
-	}
-	const cordic_quad *c = bank->quad;
-	return with_queue(c->queues, stream, [&](uint32_t *q) {
-		return launch_quad_bank(c->cfg, c->d_tab, bank->tabs, off, bank->io16,
-				stream, q);
+	return with_queue(*bank->queues, stream, [&](uint32_t *q) {
+		return launch_sine_bank(bank->core, bank->tabs, off, bank->io16, stream, q);
 	});
 }
 

@@ -1,8 +1,8 @@
 // cordic_table_bank.h -- oscillator banks: many cordic_table_nco /
 // cordic_quad_nco jobs of one core in ONE launch (include/cordic_amd.h,
 // "oscillator banks").  The tables the host cuts at create
-// (cordic_abi_table.cpp) and the launchers of the kernel that walks them
-// (cordic_table_bank.hip).
+// (cordic_abi_table.cpp) and the launcher of the kernel that walks them
+// (cordic_table_bank.hip), on the core a SineCore (cordic_table_nco.h) names.
 // Host-visible types only.
 //
 // No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "cordic_amd.h"
+#include "cordic_table_nco.h"
 
 namespace cordic_amd {
 
@@ -50,23 +51,16 @@ struct BankTables {
 // `streams` non-empty streams on `resident` blocks; the rule is set out in
 // cordic_table_bank.hip.
 uint32_t bank_tile_shift(uint64_t total_vecs, uint64_t streams, uint64_t resident);
-// blocks of the current device that hold their table at the same time (the
-// single call's per-CU cap x its CUs); < 0: no device
-int	table_bank_resident(const cordic_table_config &t, const int16_t *d_lds16,
-		int lds_mode, int lds_entries);
-int	quad_bank_resident(const cordic_quad_config &q);
+// blocks of the current device that hold the core's table at the same time
+// (the single call's per-CU cap x its CUs); < 0: no device
+int	sine_bank_resident(const SineCore &c);
 
-// The whole bank in one launch on the layout launch_table_nco / launch_quad_nco
-// would choose.  index_offset: low 32 bits of the run-wide addend to every
-// job's index0.  queue: a tile-queue block, or NULL for one contiguous chunk of
-// tiles per block.  An empty bank launches nothing.
-int	launch_table_bank(const cordic_table_config &t, const int32_t *d_tbl,
-		const int16_t *d_lds16, int lds_mode, int lds_entries,
-		const BankTables &bank, uint32_t index_offset, bool io16, void *stream,
-		uint32_t *queue);
-int	launch_quad_bank(const cordic_quad_config &q, const int32_t *d_tables,
-		const BankTables &bank, uint32_t index_offset, bool io16, void *stream,
-		uint32_t *queue);
+// The whole bank in one launch on the layout launch_sine_nco would choose.
+// index_offset: low 32 bits of the run-wide addend to every job's index0.
+// queue: a tile-queue block, or NULL for one contiguous chunk of tiles per
+// block.  An empty bank launches nothing.
+int	launch_sine_bank(const SineCore &c, const BankTables &bank,
+		uint32_t index_offset, bool io16, void *stream, uint32_t *queue);
 
 } // namespace cordic_amd
 #endif

@@ -151,15 +151,20 @@ static BankArgs args_of(const BankTables &b, uint32_t index_offset)
 		index_offset};
 }
 
+// blocks of a CU that hold the core's table at the same time: the single
+// call's cap (cordic_table_nco.hip: launch_one); 0: the LDS copy does not fit
+static int per_cu_of(size_t lds_bytes)
+{
+	// (+ the kernel's static tile-id slots)
+	return lds_blocks_per_cu(lds_bytes + 64);
+}
+
 template <typename CORE, typename T>
-bool launch_one(const CORE &core, const BankArgs &a, size_t lds_bytes, int per_cu,
+bool launch_one(const CORE &core, const BankArgs &a, size_t lds_bytes,
 		hipStream_t st, uint32_t *queue)
 {
-	const void *kern = (const void *)table_bank<CORE, T>;
-	// (+ the kernel's static tile-id slots)
-	if (lds_bytes + 64 > 64 * 1024 && hipFuncSetAttribute(kern,
-			hipFuncAttributeMaxDynamicSharedMemorySize,
-			(int)lds_bytes + 64) != hipSuccess)
+	const int per_cu = per_cu_of(lds_bytes);
+	if (per_cu < 1 || !allow_lds((const void *)table_bank<CORE, T>, lds_bytes + 64))
 		return false;
 	const int cus = jobs_cus_now();
 	if (cus < 0)
@@ -170,42 +175,6 @@ bool launch_one(const CORE &core, const BankArgs &a, size_t lds_bytes, int per_c
 	hipLaunchKernelGGL((table_bank<CORE, T>), dim3(grid), dim3(1024), lds_bytes,
 		st, core, a, queue);
 	return true;
-}
-
-// ALLOW16: instances with int16 outputs exist only for layouts that serve
-// cores of OW <= 16
-template <typename CORE, bool ALLOW16>
-bool launch_core(const CORE &core, const BankArgs &a, bool io16, size_t lds_bytes,
-		int per_cu, hipStream_t st, uint32_t *queue)
-{
-	if constexpr (ALLOW16) {
-		if (io16)
-			return launch_one<CORE, int16_t>(core, a, lds_bytes, per_cu, st, queue);
-	}
-	if (io16)
-		return false;
-	return launch_one<CORE, int32_t>(core, a, lds_bytes, per_cu, st, queue);
-}
-
-static int finish(bool launched)
-{
-	if (!launched) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	return hipGetLastError() == hipSuccess ? CORDIC_OK : CORDIC_ERR_DEVICE;
-}
-
-// as launch_table_nco: bytes of the LDS copy and blocks per CU (0: L2 gather)
-static int table_per_cu(const int16_t *d_lds16, int lds_mode, int lds_entries,
-		size_t *bytes)
-{
-	*bytes = 0;
-	if (!(lds_mode >= 3 || (d_lds16 && lds_mode)))
-		return 0;
-	*bytes = ((size_t)lds_entries * (lds_mode >= 3 ? 4 : 2) + 15) & ~(size_t)15;
-	const int per_cu = (int)((160 * 1024) / (*bytes + 64));
-	return per_cu > 2 ? 2 : per_cu;
 }
 
 } // namespace tbank
@@ -221,87 +190,31 @@ uint32_t bank_tile_shift(uint64_t total_vecs, uint64_t streams, uint64_t residen
 	return shift;
 }
 
-int table_bank_resident(const cordic_table_config &, const int16_t *d_lds16,
-		int lds_mode, int lds_entries)
+int sine_bank_resident(const SineCore &c)
 {
-	size_t bytes;
-	const int per_cu = tbank::table_per_cu(d_lds16, lds_mode, lds_entries, &bytes);
+	// (a copy that does not fit is not staged: the L2 gather, two blocks)
+	const int per_cu = tbank::per_cu_of(c.lds_bytes());
 	const int cus = jobs_cus_now();
 	return cus < 0 ? -1 : cus * (per_cu >= 1 ? per_cu : 2);
 }
 
-int quad_bank_resident(const cordic_quad_config &)
-{
-	const int cus = jobs_cus_now();
-	return cus < 0 ? -1 : cus * 2;
-}
-
-int launch_table_bank(const cordic_table_config &t, const int32_t *d_tbl,
-		const int16_t *d_lds16, int lds_mode, int lds_entries,
-		const BankTables &bank, uint32_t index_offset, bool io16, void *stream,
-		uint32_t *queue)
+int launch_sine_bank(const SineCore &c, const BankTables &bank,
+		uint32_t index_offset, bool io16, void *stream, uint32_t *queue)
 {
 	using namespace tbank;
 	(void)hipGetLastError();	// (a stale error is not this launch's)
-	if (io16 && t.ow > 16) return CORDIC_ERR_CONTAINER;
+	if (io16 && c.ow() > 16) return CORDIC_ERR_CONTAINER;
 	if (bank.ntiles == 0 && bank.nedges == 0) return CORDIC_OK;
-	if (!d_tbl || !table_sane(t) || !bank.tunings || (bank.ntiles && !bank.tiles)
+	if (!c.sane() || !bank.tunings || (bank.ntiles && !bank.tiles)
 			|| (bank.nedges && !bank.edges) || bank.tile_shift < 6
 			|| bank.tile_shift > 10)
 		return CORDIC_ERR_ARGS;
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	const BankArgs a = args_of(bank, index_offset);
-	size_t bytes;
-	const int per_cu = table_per_cu(d_lds16, lds_mode, lds_entries, &bytes);
-	if (per_cu >= 1 && !(lds_mode >= 3 && io16)) {
-		bool done = false;
-		switch (lds_mode) {
-		case 1:
-			done = launch_core<CoreLds<1, int16_t>, true>(
-				{d_lds16, lds_entries, t.pw, t.ow}, a, io16, bytes, per_cu, st, queue);
-			break;
-		case 2:
-			done = launch_core<CoreLds<2, int16_t>, true>(
-				{d_lds16, lds_entries, t.pw, t.ow}, a, io16, bytes, per_cu, st, queue);
-			break;
-		case 3:
-			done = launch_core<CoreLds<1, int32_t>, false>(
-				{d_tbl, lds_entries, t.pw, t.ow}, a, io16, bytes, per_cu, st, queue);
-			break;
-		default:
-			done = launch_core<CoreLds<2, int32_t>, false>(
-				{d_tbl, lds_entries, t.pw, t.ow}, a, io16, bytes, per_cu, st, queue);
-			break;
-		}
-		if (done)
-			return finish(true);
-		(void)hipGetLastError();	// the L2 gather kernel below serves the table
-	}
-	const bool done = t.kind == CORDIC_QTR
-		? launch_core<CoreL2<true>, true>({d_tbl, t.pw, t.ow}, a, io16, 0, 2, st, queue)
-		: launch_core<CoreL2<false>, true>({d_tbl, t.pw, t.ow}, a, io16, 0, 2, st, queue);
-	return finish(done);
-}
-
-int launch_quad_bank(const cordic_quad_config &q, const int32_t *d_tables,
-		const BankTables &bank, uint32_t index_offset, bool io16, void *stream,
-		uint32_t *queue)
-{
-	using namespace tbank;
-	(void)hipGetLastError();
-	if (io16 && q.ow > 16) return CORDIC_ERR_CONTAINER;
-	if (bank.ntiles == 0 && bank.nedges == 0) return CORDIC_OK;
-	if (!d_tables || !quad_sane(q) || !bank.tunings || (bank.ntiles && !bank.tiles)
-			|| (bank.nedges && !bank.edges) || bank.tile_shift < 6
-			|| bank.tile_shift > 10)
-		return CORDIC_ERR_ARGS;
-	const size_t bytes = (size_t)q.entries * sizeof(i32x4);
-	if (bytes > 64 * 1024)
-		return CORDIC_ERR_UNSUPPORTED;
-	const CoreQuad core{reinterpret_cast<const i32x4 *>(d_tables),
-		{q.pw, q.ow, q.xtra, q.ww, q.lgtbl, q.dxbits, q.cbits, q.lbits}};
-	return finish(launch_core<CoreQuad, true>(core, args_of(bank, index_offset),
-		io16, bytes, 2, static_cast<hipStream_t>(stream), queue));
+	return with_layout(c, io16, [&](const auto &core, auto tag, size_t bytes) {
+		return launch_one<std::decay_t<decltype(core)>, decltype(tag)>(core, a,
+			bytes, st, queue);
+	});
 }
 
 } // namespace cordic_amd

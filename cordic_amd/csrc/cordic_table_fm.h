@@ -2,14 +2,14 @@
 // table and quadratic sine cores (cordic_table_fm / cordic_quad_fm and their
 // int16 forms), and the phase accumulator they are built on
 // (cordic_phase_accumulate): the phase of sample i is a running sum of
-// per-sample tuning words, made on the device.  Launchers for
+// per-sample tuning words, made on the device.  The launcher for
 // cordic_abi_table.cpp; the two public functions that need no handle
 // (cordic_fm_workspace, cordic_phase_accumulate) are defined in
 // cordic_table_fm.hip itself.
 //
-// The cores' layouts and sample functions are those of cordic_table_nco.h,
-// included by the kernel unit: there is one copy of them.  Neither unit holds
-// a kernel of the DESIGN section 4.4 sweep.
+// The core comes as a SineCore, and its layouts, their choice and the sample
+// functions are those of cordic_table_nco.h: there is one copy of them.
+// Neither unit holds a kernel of the DESIGN section 4.4 sweep.
 #ifndef CORDIC_TABLE_FM_H
 #define CORDIC_TABLE_FM_H
 
@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "cordic_amd.h"
+#include "cordic_table_nco.h"
 
 namespace cordic_amd {
 
@@ -34,19 +35,14 @@ constexpr size_t kFmWorkBytes = 16 + 4 * kFmMaxBlocks;
 //   d_sin[i] = core(p_i), d_cos[i] = core(p_i + 2^(PW-2))   (d_cos NULL: none)
 //   *d_acc = start + fcw[0] + .. + fcw[n-1]
 // io16: the outputs are int16_t (OW <= 16: CORDIC_ERR_CONTAINER otherwise),
-// any 2-byte-aligned address; else int32_t, 4-byte aligned.  The launchers
-// check alignment and that no output range (d_acc and d_work included)
-// overlaps anything else, and choose the layout from (d_lds16, lds_mode,
-// lds_entries) as launch_table_nco does.  n == 0: CORDIC_OK, nothing touched.
-int	launch_table_fm(const cordic_table_config &t, const int32_t *d_tbl,
-		const int16_t *d_lds16, int lds_mode, int lds_entries, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, void *d_sin, void *d_cos, bool io16, void *d_work,
-		void *stream);
-int	launch_quad_fm(const cordic_quad_config &q, const int32_t *d_tables,
-		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, void *d_sin, void *d_cos, bool io16, void *d_work,
-		void *stream);
+// any 2-byte-aligned address; else int32_t, 4-byte aligned.  The launcher
+// checks alignment and that no output range (d_acc and d_work included)
+// overlaps anything else.  The layout is the one launch_sine_nco would choose,
+// where its copy fits into LDS beside a tile's phases; else the L2 gather.
+// n == 0: CORDIC_OK, nothing touched.
+int	launch_sine_fm(const SineCore &c, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, void *d_sin,
+		void *d_cos, bool io16, void *d_work, void *stream);
 
 } // namespace cordic_amd
 #endif

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(1024) void fm_reduce(const uint32_t *d_fcw, size_t 
 	const size_t lo = (size_t)blockIdx.x * span;	// < n by the grid
 	const size_t len = (n - lo < span) ? n - lo : span;
 	const uint32_t *f = d_fcw + lo;
-	size_t head = ((16u - (size_t)(reinterpret_cast<uintptr_t>(f) & 15u)) & 15u) / 4;
+	size_t head = head_elems(reinterpret_cast<uintptr_t>(f), 4);
 	if (head > len)
 		head = len;
 	const size_t nv = (len - head) / 4;
@@ -193,8 +193,7 @@ __global__ __launch_bounds__(1024) void table_fm(CORE core, FmArgs a, T *d_sin,
 			: t0 - (size_t)(reinterpret_cast<uintptr_t>(out + t0) & 15u) / sizeof(T);
 		const size_t w1 = (t1 == hi) ? hi
 			: t1 - (size_t)(reinterpret_cast<uintptr_t>(out + t1) & 15u) / sizeof(T);
-		size_t h = ((16u - (size_t)(reinterpret_cast<uintptr_t>(out + w0) & 15u)) & 15u)
-			/ sizeof(T);
+		size_t h = head_elems(reinterpret_cast<uintptr_t>(out + w0), sizeof(T));
 		if (h > w1 - w0)
 			h = w1 - w0;
 		// At most 4096 / W vectors, so one per thread covers them.  Behind a
@@ -345,15 +344,8 @@ bool launch_one(const CORE &core, const Call &c, size_t table_bytes)
 {
 	const size_t lds = table_bytes + kPhaseBytes;
 	// (+ the kernel's static scratch)
-	int per_cu = (int)((160 * 1024) / (lds + 128));
-	if (per_cu < 1)
-		return false;
-	if (per_cu > 2)
-		per_cu = 2;
-	const void *kern = (const void *)table_fm<CORE, T>;
-	if (lds + 128 > 64 * 1024 && hipFuncSetAttribute(kern,
-			hipFuncAttributeMaxDynamicSharedMemorySize,
-			(int)lds + 128) != hipSuccess)
+	const int per_cu = lds_blocks_per_cu(lds + 128);
+	if (per_cu < 1 || !allow_lds((const void *)table_fm<CORE, T>, lds + 128))
 		return false;
 	const int cus = jobs_cus_now();
 	if (cus < 0)
@@ -375,102 +367,27 @@ bool launch_one(const CORE &core, const Call &c, size_t table_bytes)
 	return true;
 }
 
-// ALLOW16: instances with int16 outputs exist only where table_nco has them
-template <typename CORE, bool ALLOW16>
-bool launch_core(const CORE &core, const Call &c, bool io16, size_t table_bytes)
-{
-	if constexpr (ALLOW16) {
-		if (io16)
-			return launch_one<CORE, int16_t>(core, c, table_bytes);
-	}
-	if (io16)
-		return false;
-	return launch_one<CORE, int32_t>(core, c, table_bytes);
-}
-
-static int finish(bool launched)
-{
-	if (!launched) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	return hipGetLastError() == hipSuccess ? CORDIC_OK : CORDIC_ERR_DEVICE;
-}
-
 } // namespace tfm
 
-int launch_table_fm(const cordic_table_config &t, const int32_t *d_tbl,
-		const int16_t *d_lds16, int lds_mode, int lds_entries, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, void *d_sin, void *d_cos, bool io16, void *d_work,
-		void *stream)
+int launch_sine_fm(const SineCore &c, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, void *d_sin,
+		void *d_cos, bool io16, void *d_work, void *stream)
 {
 	using namespace tfm;
 	(void)hipGetLastError();	// (a stale error is not this call's)
-	if (io16 && t.ow > 16) return CORDIC_ERR_CONTAINER;
+	if (io16 && c.ow() > 16) return CORDIC_ERR_CONTAINER;
 	if (n == 0) return CORDIC_OK;
-	if (!d_tbl || !table_sane(t)) return CORDIC_ERR_ARGS;
+	if (!c.sane()) return CORDIC_ERR_ARGS;
 	if (int rc = check_call(n, d_fcw, d_pm, d_acc, d_sin, d_cos, io16 ? 2 : 4,
 			d_work, false))
 		return rc;
-	const Call c{n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, d_work,
-		1u << (t.pw - 2), static_cast<hipStream_t>(stream)};
-	if (lds_mode >= 3 || (d_lds16 && lds_mode)) {
-		// as launch_table_nco: the LDS copy where it fits beside the phases
-		const bool wide = lds_mode >= 3;
-		const size_t bytes = ((size_t)lds_entries * (wide ? 4 : 2) + 15) & ~(size_t)15;
-		bool done = false;
-		if (!(wide && io16)) {
-			switch (lds_mode) {
-			case 1:
-				done = launch_core<CoreLds<1, int16_t>, true>(
-					{d_lds16, lds_entries, t.pw, t.ow}, c, io16, bytes);
-				break;
-			case 2:
-				done = launch_core<CoreLds<2, int16_t>, true>(
-					{d_lds16, lds_entries, t.pw, t.ow}, c, io16, bytes);
-				break;
-			case 3:
-				done = launch_core<CoreLds<1, int32_t>, false>(
-					{d_tbl, lds_entries, t.pw, t.ow}, c, io16, bytes);
-				break;
-			default:
-				done = launch_core<CoreLds<2, int32_t>, false>(
-					{d_tbl, lds_entries, t.pw, t.ow}, c, io16, bytes);
-				break;
-			}
-		}
-		if (done)
-			return finish(true);
-		(void)hipGetLastError();	// the L2 gather layout below serves the table
-	}
-	const bool done = t.kind == CORDIC_QTR
-		? launch_core<CoreL2<true>, true>({d_tbl, t.pw, t.ow}, c, io16, 0)
-		: launch_core<CoreL2<false>, true>({d_tbl, t.pw, t.ow}, c, io16, 0);
-	return finish(done);
-}
-
-int launch_quad_fm(const cordic_quad_config &q, const int32_t *d_tables,
-		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, void *d_sin, void *d_cos, bool io16, void *d_work,
-		void *stream)
-{
-	using namespace tfm;
-	(void)hipGetLastError();
-	if (io16 && q.ow > 16) return CORDIC_ERR_CONTAINER;
-	if (n == 0) return CORDIC_OK;
-	if (!d_tables || !quad_sane(q)) return CORDIC_ERR_ARGS;
-	if (int rc = check_call(n, d_fcw, d_pm, d_acc, d_sin, d_cos, io16 ? 2 : 4,
-			d_work, false))
-		return rc;
-	const size_t bytes = (size_t)q.entries * sizeof(i32x4);
-	if (bytes > 64 * 1024)
-		return CORDIC_ERR_UNSUPPORTED;
-	const Call c{n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, d_work,
-		1u << (q.pw - 2), static_cast<hipStream_t>(stream)};
-	const CoreQuad core{reinterpret_cast<const i32x4 *>(d_tables),
-		{q.pw, q.ow, q.xtra, q.ww, q.lgtbl, q.dxbits, q.cbits, q.lbits}};
-	return finish(launch_core<CoreQuad, true>(core, c, io16, bytes));
+	const Call call{n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, d_work,
+		c.quarter(), static_cast<hipStream_t>(stream)};
+	// (an LDS copy that does not fit beside the phases: the L2 gather)
+	return with_layout(c, io16, [&](const auto &core, auto tag, size_t bytes) {
+		return launch_one<std::decay_t<decltype(core)>, decltype(tag)>(core, call,
+			bytes);
+	});
 }
 
 } // namespace cordic_amd

@@ -36,8 +36,7 @@ struct NcoArgs {
 template <typename T>
 __device__ __forceinline__ size_t head_of(const T *p, size_t n)
 {
-	const size_t h = ((16u - (size_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u)
-		/ sizeof(T);
+	const size_t h = head_elems(reinterpret_cast<uintptr_t>(p), sizeof(T));
 	return h < n ? h : n;
 }
 
@@ -147,13 +146,11 @@ static int check_outputs(const void *d_sin, const void *d_cos, size_t n, bool io
 
 template <typename CORE, bool COS, typename T>
 bool launch_one(const CORE &core, const NcoArgs &na, void *d_sin, void *d_cos,
-		size_t n, size_t lds_bytes, int per_cu, hipStream_t st, uint32_t *queue)
+		size_t n, size_t lds_bytes, hipStream_t st, uint32_t *queue)
 {
-	const void *kern = (const void *)table_nco<CORE, COS, T>;
 	// (+ the kernel's static tile-id slots)
-	if (lds_bytes + 64 > 64 * 1024 && hipFuncSetAttribute(kern,
-			hipFuncAttributeMaxDynamicSharedMemorySize,
-			(int)lds_bytes + 64) != hipSuccess)
+	const int per_cu = lds_blocks_per_cu(lds_bytes + 64);
+	if (per_cu < 1 || !allow_lds((const void *)table_nco<CORE, COS, T>, lds_bytes + 64))
 		return false;
 	const int grid = grid_of(n, 16 / (int)sizeof(T), per_cu);
 	if (grid < 0)
@@ -164,116 +161,28 @@ bool launch_one(const CORE &core, const NcoArgs &na, void *d_sin, void *d_cos,
 	return true;
 }
 
-// ALLOW16: instances with int16 outputs exist only for layouts that serve
-// cores of OW <= 16
-template <typename CORE, bool ALLOW16>
-bool launch_core(const CORE &core, const NcoArgs &na, void *d_sin, void *d_cos,
-		size_t n, bool io16, size_t lds_bytes, int per_cu, hipStream_t st,
-		uint32_t *queue)
-{
-	if constexpr (ALLOW16) {
-		if (io16)
-			return d_cos
-				? launch_one<CORE, true, int16_t>(core, na, d_sin, d_cos, n,
-					lds_bytes, per_cu, st, queue)
-				: launch_one<CORE, false, int16_t>(core, na, d_sin, d_cos, n,
-					lds_bytes, per_cu, st, queue);
-	}
-	if (io16)
-		return false;
-	return d_cos
-		? launch_one<CORE, true, int32_t>(core, na, d_sin, d_cos, n, lds_bytes,
-			per_cu, st, queue)
-		: launch_one<CORE, false, int32_t>(core, na, d_sin, d_cos, n, lds_bytes,
-			per_cu, st, queue);
-}
-
-static int finish(bool launched)
-{
-	if (!launched) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	return hipGetLastError() == hipSuccess ? CORDIC_OK : CORDIC_ERR_DEVICE;
-}
-
 } // namespace tnco
 
-int launch_table_nco(const cordic_table_config &t, const int32_t *d_tbl,
-		const int16_t *d_lds16, int lds_mode, int lds_entries, size_t n,
-		uint32_t phase0, uint32_t fcw, uint64_t index0, void *d_sin,
-		void *d_cos, bool io16, void *stream, uint32_t *queue)
+int launch_sine_nco(const SineCore &c, size_t n, uint32_t phase0, uint32_t fcw,
+		uint64_t index0, void *d_sin, void *d_cos, bool io16, void *stream,
+		uint32_t *queue)
 {
 	using namespace tnco;
 	(void)hipGetLastError();	// (a stale error is not this launch's)
-	if (io16 && t.ow > 16) return CORDIC_ERR_CONTAINER;
+	if (io16 && c.ow() > 16) return CORDIC_ERR_CONTAINER;
 	if (n == 0) return CORDIC_OK;
-	if (!d_tbl || !table_sane(t)) return CORDIC_ERR_ARGS;
+	if (!c.sane()) return CORDIC_ERR_ARGS;
 	if (int rc = check_outputs(d_sin, d_cos, n, io16)) return rc;
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	// (PW <= 32: the low 32 bits of the sample index are all that matters)
-	const NcoArgs na{phase0 + (uint32_t)index0 * fcw, fcw, 1u << (t.pw - 2)};
-	if (lds_mode >= 3 || (d_lds16 && lds_mode)) {
-		// as launch_table_lookup: the LDS copy, two blocks per CU where two fit
-		const bool wide = lds_mode >= 3;
-		const size_t bytes = ((size_t)lds_entries * (wide ? 4 : 2) + 15) & ~(size_t)15;
-		int per_cu = (int)((160 * 1024) / (bytes + 64));
-		if (per_cu > 2) per_cu = 2;
-		bool done = false;
-		if (per_cu >= 1 && !(wide && io16)) {
-			switch (lds_mode) {
-			case 1:
-				done = launch_core<CoreLds<1, int16_t>, true>(
-					{d_lds16, lds_entries, t.pw, t.ow}, na, d_sin, d_cos, n,
-					io16, bytes, per_cu, st, queue);
-				break;
-			case 2:
-				done = launch_core<CoreLds<2, int16_t>, true>(
-					{d_lds16, lds_entries, t.pw, t.ow}, na, d_sin, d_cos, n,
-					io16, bytes, per_cu, st, queue);
-				break;
-			case 3:
-				done = launch_core<CoreLds<1, int32_t>, false>(
-					{d_tbl, lds_entries, t.pw, t.ow}, na, d_sin, d_cos, n,
-					io16, bytes, per_cu, st, queue);
-				break;
-			default:
-				done = launch_core<CoreLds<2, int32_t>, false>(
-					{d_tbl, lds_entries, t.pw, t.ow}, na, d_sin, d_cos, n,
-					io16, bytes, per_cu, st, queue);
-				break;
-			}
-		}
-		if (done)
-			return finish(true);
-		(void)hipGetLastError();	// the L2 gather kernel below serves the table
-	}
-	const bool done = t.kind == CORDIC_QTR
-		? launch_core<CoreL2<true>, true>({d_tbl, t.pw, t.ow}, na, d_sin, d_cos,
-			n, io16, 0, 2, st, queue)
-		: launch_core<CoreL2<false>, true>({d_tbl, t.pw, t.ow}, na, d_sin, d_cos,
-			n, io16, 0, 2, st, queue);
-	return finish(done);
-}
-
-int launch_quad_nco(const cordic_quad_config &q, const int32_t *d_tables,
-		size_t n, uint32_t phase0, uint32_t fcw, uint64_t index0,
-		void *d_sin, void *d_cos, bool io16, void *stream, uint32_t *queue)
-{
-	using namespace tnco;
-	(void)hipGetLastError();
-	if (io16 && q.ow > 16) return CORDIC_ERR_CONTAINER;
-	if (n == 0) return CORDIC_OK;
-	if (!d_tables || !quad_sane(q)) return CORDIC_ERR_ARGS;
-	if (int rc = check_outputs(d_sin, d_cos, n, io16)) return rc;
-	const size_t bytes = (size_t)q.entries * sizeof(i32x4);
-	if (bytes > 64 * 1024)
-		return CORDIC_ERR_UNSUPPORTED;
-	const NcoArgs na{phase0 + (uint32_t)index0 * fcw, fcw, 1u << (q.pw - 2)};
-	const CoreQuad core{reinterpret_cast<const i32x4 *>(d_tables),
-		{q.pw, q.ow, q.xtra, q.ww, q.lgtbl, q.dxbits, q.cbits, q.lbits}};
-	return finish(launch_core<CoreQuad, true>(core, na, d_sin, d_cos, n, io16,
-		bytes, 2, static_cast<hipStream_t>(stream), queue));
+	const NcoArgs na{phase0 + (uint32_t)index0 * fcw, fcw, c.quarter()};
+	return with_layout(c, io16, [&](const auto &core, auto tag, size_t bytes) {
+		typedef std::decay_t<decltype(core)> CORE;
+		typedef decltype(tag) T;
+		return d_cos
+			? launch_one<CORE, true, T>(core, na, d_sin, d_cos, n, bytes, st, queue)
+			: launch_one<CORE, false, T>(core, na, d_sin, d_cos, n, bytes, st, queue);
+	});
 }
 
 } // namespace cordic_amd

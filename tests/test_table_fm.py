@@ -77,7 +77,8 @@ def test_the_binding_asks_the_caller_for_the_scratch():
 # ---------------------------------------------------------------- GPU
 
 TABLES = [(ca.TBL, -1, 13, 17), (ca.QTR, -1, 24, 18), (ca.TBL, -1, 8, 6),
-          (ca.QTR, -1, 16, 17), (ca.QTR, -1, 24, 17), (ca.TBL, -1, 24, 17)]
+          (ca.QTR, -1, 16, 17), (ca.QTR, -1, 24, 17), (ca.TBL, -1, 24, 17),
+          (ca.TBL, -1, 12, 18)]
 QUADS = ["rtl_quadtbl", "o20x4p24"]        # of test_quadtbl's GOOD; OW 13, 20
 # (n, element offset of the sine array; the cosine sits at 3 * that)
 SIZES = [(0, 0), (1, 1), (5, 2), (4095, 3), (4096, 0), (4097, 1),

@@ -47,7 +47,7 @@ def test_a_null_handle_is_refused(name):
 
 TABLES = [(ca.TBL, -1, 13, 17), (ca.QTR, -1, 24, 18), (ca.TBL, -1, 8, 6),
           (ca.QTR, -1, 16, 17), (ca.QTR, -1, 24, 17), (ca.TBL, -1, 24, 17),
-          (ca.QTR, -1, 30, 20), (ca.QTR, -1, 9, 5)]
+          (ca.QTR, -1, 30, 20), (ca.QTR, -1, 9, 5), (ca.TBL, -1, 12, 18)]
 # (phase0, fcw, index0); with n = 2^20 the first is every phase of every core
 # with PW <= 20; in the last the sample index crosses 2^32 inside the call
 CASES = [(0, 1, 0), (0x12345, 0, 7), (0xdeadbeef, 0x9e3779b1, 0),

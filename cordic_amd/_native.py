@@ -299,6 +299,13 @@ ABI = {
     "cordic_fm_demod16": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_mix_workspace": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "cordic_plan_fm_mix_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32)]),
+    "cordic_plan_fm_mix": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                     C.c_void_p, C.c_uint32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_void_p)]),
     "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -544,6 +551,40 @@ class Plan:
                                      fcw & 0xffffffff, index0, _ptr(x), _ptr(y),
                                      _ptr(ox), _ptr(oy), _stream(stream)),
                "cordic_plan_mix")
+
+    def fm_mix_workspace(self, n):
+        """cordic_plan_fm_mix_workspace: bytes of device scratch an fm_mix
+        call of n samples needs on this plan (16-byte aligned)"""
+        return int(lib().cordic_plan_fm_mix_workspace(self._h, n))
+
+    def fm_mix_info(self):
+        """cordic_plan_fm_mix_info: (fused, tile) -- whether fm_mix runs the
+        fused kernel on this plan, and the samples a block makes per pass"""
+        fused, tile = C.c_int32(0), C.c_int32(0)
+        _check(lib().cordic_plan_fm_mix_info(self._h, C.byref(fused),
+                                             C.byref(tile)),
+               "cordic_plan_fm_mix_info")
+        return int(fused.value), int(tile.value)
+
+    def fm_mix(self, fcw, x, y, ox, oy, work=None, pm=None, n=None, phase0=0,
+               acc=None, stream=None):
+        """cordic_plan_fm_mix: (x, y) rotated by the running sum of the
+        per-sample tuning words, phase[i] = phase0 + acc[0] + fcw[0] + .. +
+        fcw[i-1] (+ pm[i]); acc (a one-word device tensor, optional) is left
+        at the sum behind sample n-1.  work: device scratch of
+        fm_mix_workspace(n) bytes (16-byte aligned), the caller's."""
+        n = x.numel() if n is None else n
+        if work is None and n:
+            raise TypeError("work: a device buffer of fm_mix_workspace(n) bytes")
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and work.numel() * work.element_size() < self.fm_mix_workspace(n):
+            raise ValueError("work: %d bytes, fm_mix_workspace(%d) = %d"
+                             % (work.numel() * work.element_size(), n,
+                                self.fm_mix_workspace(n)))
+        _check(lib().cordic_plan_fm_mix(
+            self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
+            _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
+            "cordic_plan_fm_mix")
 
     @property
     def queue_info(self):

@@ -13,6 +13,7 @@
 
 #include "cordic_amd.h"
 #include "cordic_devmem.h"
+#include "cordic_fm_mix.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_queue_ring.h"
@@ -129,6 +130,67 @@ int cordic_plan_mix(const cordic_plan *plan, size_t n, uint32_t phase0,
 	j.ox = d_oxval; j.oy = d_oyval; j.n = n;
 	attach_dirs(plan, j);
 	return launch_rotator(plan->cfg, Feed::PhaseArray_XYArray, j, stream);
+}
+
+// ---- the FM mixer: per-sample tuning words accumulated inside the rotator
+// (cordic_fm_mix.h)
+static int fm_mix_plan_ok(const cordic_plan *plan)
+{
+	if (!plan)
+		return CORDIC_ERR_ARGS;
+	if (plan->cfg.mode != CORDIC_P2R && plan->cfg.mode != CORDIC_SP2R)
+		return CORDIC_ERR_MODE;
+	return config_sane(plan->cfg) ? CORDIC_OK : CORDIC_ERR_ARGS;
+}
+
+static bool fm_mix_fused(const cordic_plan *plan)
+{
+	return fmx_is_fused(plan->cfg, plan->d_dir, plan->dx);
+}
+
+size_t cordic_plan_fm_mix_workspace(const cordic_plan *plan, size_t n)
+{
+	if (fm_mix_plan_ok(plan) != CORDIC_OK)
+		return 0;
+	return fmx_work_bytes(fm_mix_fused(plan), n);
+}
+
+int cordic_plan_fm_mix_info(const cordic_plan *plan, int32_t *fused, int32_t *tile)
+{
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	const bool f = fm_mix_fused(plan);
+	if (fused)
+		*fused = f ? 1 : 0;
+	if (tile)
+		*tile = f ? (int32_t)kFmxPass : 0;
+	return CORDIC_OK;
+}
+
+int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval, int32_t *d_oxval,
+		int32_t *d_oyval, void *d_work, void *stream)
+{
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	if (n == 0)
+		return CORDIC_OK;
+	const bool fused = fm_mix_fused(plan);
+	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval,
+			d_oyval, d_work, fmx_work_bytes(fused, n)))
+		return rc;
+	if (fused)
+		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm,
+			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, d_work, stream);
+	// the fallback: the phases into the workspace, behind the accumulator's own
+	// scratch, and the rotator on them
+	uint32_t *ph = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_work)
+			+ kFmxPhaseAt);
+	if (int rc = cordic_phase_accumulate(n, d_fcw, d_pm, phase0, d_acc, ph, d_work,
+			stream))
+		return rc;
+	return cordic_plan_p2r(plan, n, d_xval, d_yval, ph, d_oxval, d_oyval, stream);
 }
 
 int cordic_plan_queue_info(const cordic_plan *plan, cordic_queue_info *info)

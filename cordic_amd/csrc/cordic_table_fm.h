@@ -44,5 +44,12 @@ int	launch_sine_fm(const SineCore &c, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, void *d_sin,
 		void *d_cos, bool io16, void *d_work, void *stream);
 
+// Launch 1 alone, for the other scan over per-sample tuning words
+// (cordic_fm_mix.hip): `grid` blocks, block b sums [b * span, (b + 1) * span)
+// of d_fcw cut at n into work[4 + b] (grid <= (n + span - 1) / span), and
+// block 0 latches work[0] = phase0 + (d_acc ? *d_acc : 0).
+void	launch_fm_reduce(unsigned grid, const uint32_t *d_fcw, size_t n, size_t span,
+		uint32_t phase0, const uint32_t *d_acc, uint32_t *work, void *stream);
+
 } // namespace cordic_amd
 #endif

@@ -328,6 +328,17 @@ static int check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 	return CORDIC_OK;
 }
 
+} // namespace tfm
+
+void launch_fm_reduce(unsigned grid, const uint32_t *d_fcw, size_t n, size_t span,
+		uint32_t phase0, const uint32_t *d_acc, uint32_t *work, void *stream)
+{
+	hipLaunchKernelGGL(tfm::fm_reduce, dim3(grid), dim3(1024), 0,
+		static_cast<hipStream_t>(stream), d_fcw, n, span, phase0, d_acc, work);
+}
+
+namespace tfm {
+
 struct Call {
 	size_t	n;
 	const uint32_t *d_fcw, *d_pm;
@@ -358,8 +369,7 @@ bool launch_one(const CORE &core, const Call &c, size_t table_bytes)
 	const size_t span = per_block * kFmTile;
 	const unsigned grid = (unsigned)((ntiles + per_block - 1) / per_block);
 	uint32_t *work = static_cast<uint32_t *>(c.d_work);
-	hipLaunchKernelGGL(fm_reduce, dim3(grid), dim3(1024), 0, c.st, c.d_fcw, c.n,
-		span, c.phase0, (const uint32_t *)c.d_acc, work);
+	launch_fm_reduce(grid, c.d_fcw, c.n, span, c.phase0, c.d_acc, work, c.st);
 	const FmArgs a{c.d_fcw, c.d_pm, c.d_acc, work, c.n, span, c.quarter,
 		(uint32_t)table_bytes};
 	hipLaunchKernelGGL((table_fm<CORE, T>), dim3(grid), dim3(1024), lds, c.st,

@@ -949,6 +949,85 @@ int	cordic_fm_demod16(const cordic_config *cfg, size_t n,
 		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work,
 		void *stream);
 
+/* -------------------------------------------------------------- FM mixer
+ *
+ * cordic_plan_mix with one tuning word PER SAMPLE: the rotator multiplies the
+ * sample stream (d_xval, d_yval) by an oscillator whose phase is the running
+ * sum of d_fcw, made inside the kernel -- the LO of an AFC or Costas loop, the
+ * de-chirp of a radar or LoRa sweep, an FSK / FM modulator on complex baseband,
+ * Doppler correction.  The plan's mode must be CORDIC_P2R or CORDIC_SP2R
+ * (CORDIC_ERR_MODE otherwise).  With p_i exactly the word that
+ * cordic_phase_accumulate(n, d_fcw, d_pm, phase0, d_acc, ...) writes to
+ * d_phase[i],
+ *   start = phase0 + (d_acc ? *d_acc : 0)
+ *   a_i   = start + fcw[0] + .. + fcw[i-1]              (exclusive)
+ *   p_i   = a_i + (d_pm ? pm[i] : 0)                    all mod 2^32
+ * (d_oxval[i], d_oyval[i]) are exactly what cordic_p2r writes for (d_xval[i],
+ * d_yval[i], phase = p_i) on the plan's core: the inputs are taken modulo IW
+ * and PW (the low PW bits of p_i count), the outputs are sign-extended OW-bit
+ * values.  After the call, if d_acc is given, *d_acc = start + fcw[0] + .. +
+ * fcw[n-1]: pm is not in it, and all 32 bits are kept.  Hence
+ *   - constant tuning words f give the bits of cordic_plan_mix(phase0, f,
+ *     index0 = 0, ...);
+ *   - a job cut into consecutive calls that share a d_acc -- phase0 in the
+ *     first, 0 in the others -- gives the bits of one call, and a captured
+ *     call replayed k times continues k times.
+ *
+ * Launch contract (that of the two blocks above): the library allocates,
+ * copies and synchronises nothing; the call is a fixed, small number of kernel
+ * launches on `stream`; no block waits for another block and the call takes no
+ * tile queue; *d_acc is read in the first launch only and written in a later
+ * one.  Two paths, identical bits:
+ *   fused     the cores that cordic_plan_p2r runs with looked-up directions,
+ *             minus that path's batch-size threshold -- every n >= 1: the plan
+ *             holds direction tables (cordic_plan_dir_info), WW <= 35, no wrap,
+ *             1 .. 30 zeros appended below the inputs, none of
+ *             CORDIC_FLAG_UNIT_GAIN, _NO_TAILS, _NO_LJ, _FORCE_GENERIC, tables
+ *             within 64 KiB of LDS, and 13, 16, 19, 20, 24, 27 or 29 live
+ *             stages.  Two launches: a reduction of d_fcw into per-block
+ *             partial sums, then the scan with the rotator behind it -- 24
+ *             bytes per sample (28 with d_pm).  Legal inside a stream capture;
+ *             d_work holds only the latched start and the partials.
+ *   fallback  everything else: cordic_phase_accumulate's two launches with the
+ *             phases written into d_work, then cordic_plan_p2r's launches on
+ *             them (32 bytes per sample, 36 with d_pm).
+ * cordic_plan_fm_mix_info (a pure host function): *fused = 1 or 0; *tile = the
+ * samples a block of the fused kernel makes per pass (a multiple of 4), 0 when
+ * not fused; either pointer may be NULL.  CORDIC_ERR_ARGS / _MODE as for the
+ * call.
+ *
+ * d_work: caller-owned device scratch of at least
+ * cordic_plan_fm_mix_workspace(plan, n) bytes, 16-byte aligned, not shared by
+ * calls that may run at the same time.  cordic_plan_fm_mix_workspace is a pure
+ * host function: 0 for n == 0 or a NULL plan, a multiple of 16, non-decreasing
+ * in n; at most n / 256 + 65536 for a fused plan, else at most 4 n + 65536 +
+ * 16 (the phase array and the accumulator's own scratch).
+ *
+ * Every array may sit at any 4-byte-aligned address, for any n; nothing
+ * outside [0, n) of an output is written.  Inputs may alias each other; any
+ * overlap of an output -- d_oxval, d_oyval, d_acc, d_work -- with an input or
+ * another output is CORDIC_ERR_ARGS, found on the host with nothing written
+ * (so there is no in-place form).
+ *
+ * n == 0: CORDIC_OK, nothing touched, *d_acc unchanged.  CORDIC_ERR_ARGS: a
+ * NULL plan (also with n == 0); with n > 0 a NULL d_fcw, d_xval, d_yval,
+ * d_oxval, d_oyval or d_work, a sample pointer or d_acc off the 4-byte grid,
+ * d_work off the 16-byte grid, an overlap as above.  What
+ * cordic_last_kernel() reports after the call is unspecified.
+ *
+ * There is no int16 form, no cordic_config-level twin and no job-set kind: the
+ * direction tables live in the plan, and the int16 rotators have no
+ * looked-up-direction kernel.
+ */
+size_t	cordic_plan_fm_mix_workspace(const cordic_plan *plan, size_t n);
+int	cordic_plan_fm_mix_info(const cordic_plan *plan, int32_t *fused,
+		int32_t *tile);
+int	cordic_plan_fm_mix(const cordic_plan *plan, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval,
+		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with

@@ -299,6 +299,15 @@ ABI = {
     "cordic_fm_demod16": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_demodbank_create": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_void_p)]),
+    "cordic_demodbank_destroy": (None, [C.c_void_p]),
+    "cordic_demodbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32)]),
+    "cordic_demodbank_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cordic_plan_fm_mix_workspace": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "cordic_plan_fm_mix_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32)]),
@@ -1739,6 +1748,67 @@ def fm_demod(cfg, x, y, mag, freq, work, n=None, phase0=0, last=None,
     _check(getattr(lib(), fn)(cfg.ref, n, _ptr(x), _ptr(y),
                               phase0 & 0xffffffff, _ptr(last), _ptr(mag),
                               _ptr(freq), _ptr(work), _stream(stream)), fn)
+
+
+class _CDemodJob(C.Structure):
+    """cordic_demod_job"""
+    _fields_ = [("d_xval", C.c_void_p), ("d_yval", C.c_void_p),
+                ("d_omag", C.c_void_p), ("d_ofreq", C.c_void_p),
+                ("d_last", C.c_void_p), ("n", C.c_uint64),
+                ("phase0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_DEMOD_KEYS = ("x", "y", "mag", "freq", "n", "phase0", "last")
+
+
+class DemodBank:
+    """cordic_demodbank: many fm_demod jobs of one r2p / sr2p core, cut once
+    and run in at most two launches.  jobs: tuples (x, y, mag, freq, n, phase0,
+    last) or dicts with those keys; x, y, mag, freq are int32 tensors or device
+    addresses, last a one-word device tensor or None; n None: x.numel()."""
+
+    def __init__(self, cfg, jobs):
+        jobs = [tuple(jb.get(k) for k in _DEMOD_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = jobs          # the tensors behind the addresses
+        arr = (_CDemodJob * max(1, len(jobs)))()
+        for k, (x, y, mag, freq, n, phase0, last) in enumerate(jobs):
+            arr[k].d_xval = _ptr(x)
+            arr[k].d_yval = _ptr(y)
+            arr[k].d_omag = _ptr(mag)
+            arr[k].d_ofreq = _ptr(freq)
+            arr[k].d_last = _ptr(last)
+            arr[k].n = x.numel() if n is None else n
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+        h = C.c_void_p()
+        _check(lib().cordic_demodbank_create(cfg.ref, len(jobs), arr,
+                                             C.byref(h)),
+               "cordic_demodbank_create")
+        self._h = h
+
+    def info(self):
+        a, b, c = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        d, e = C.c_int32(), C.c_int32()
+        _check(lib().cordic_demodbank_info(self._h, C.byref(a), C.byref(b),
+                                           C.byref(c), C.byref(d), C.byref(e)),
+               "cordic_demodbank_info")
+        return dict(samples=a.value, tiles=b.value, tail_jobs=c.value,
+                    fused=d.value, tile=e.value)
+
+    def run(self, stream=None):
+        _check(lib().cordic_demodbank_run(self._h, _stream(stream)),
+               "cordic_demodbank_run")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cordic_demodbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class _CHostStats(C.Structure):

@@ -74,78 +74,7 @@ namespace fmd {
 
 using namespace dev;
 
-// One vector through the converter: the per-vector body of topolar_lj_sweep
-// (cordic_device.h:2287-2360) restated, because the sweep stores what it
-// computes.  Built from the same pieces in the same order; rm, rp are the words
-// the sweep would store to omag[g], oph[g].
-template <int NLIVE, bool DYN, bool UG, bool PLAIN>
-__device__ __forceinline__ void pol_lj_vector(const CoreParams &kp, const PolLjRegs &c,
-		const uint32_t rbw, const int up, const int down, const i32x4 tx,
-		const i32x4 ty, i32x4 &rm, u32x4 &rp)
-{
-	int64_t x[kVec], y[kVec], p[kVec];
-#pragma unroll
-	for (int v = 0; v < kVec; v++) {
-		// cordic_device.h:2290-2313: the ports, the fold, the quadrant phase
-		const int32_t ex = (int32_t)((uint32_t)tx[v] << up) >> down;
-		const int32_t ey = (int32_t)((uint32_t)ty[v] << up) >> down;
-		const int32_t mx = (int32_t)op_and_or((uint32_t)ex, c.p30, c.sign);
-		const int32_t my = (int32_t)op_and_or((uint32_t)ey, c.p30, c.sign);
-		const int32_t nmy = (int32_t)((uint32_t)my ^ c.sign);
-		x[v] = op_mul(ex, mx);
-		op_mad(x[v], ey, my);
-		y[v] = op_mul(ey, mx);
-		op_mad(y[v], ex, nmy);
-		const uint32_t l = ((uint32_t)mx ^ c.sign) >> 1;
-		p[v] = op_mul(nmy, (int32_t)l);
-	}
-	if (PLAIN || down >= 2) {	// :2315-2323, stage 1
-#pragma unroll
-		for (int v = 0; v < kVec; v++)
-			pol_stage1_lj(x[v], y[v], p[v], kp.angle[0], c);
-	} else {
-#pragma unroll
-		for (int v = 0; v < kVec; v++)
-			pol_stage1_lj_early(x[v], y[v], p[v], kp.angle[0], c);
-	}
-
-	PolTmp m[kVec];
-#if CORDIC_STAGE_YIELD
-#pragma unroll
-	for (int v = 0; v < kVec; v++)
-		asm volatile("" : "=v"(m[v].t), "=v"(m[v].nt), "=v"(m[v].sy), "=v"(m[v].sx),
-				"=s"(m[v].cc));
-#endif
-	PolChainLJ<NLIVE, 1, DYN>::run(x, y, p, c, kp, m);
-
-	if (PLAIN || (kp.r >= 2 && kp.r <= 31)) {	// :2336-2353, rounding
-#pragma unroll
-		for (int v = 0; v < kVec; v++) {
-			const uint32_t xh = (uint32_t)((uint64_t)x[v] >> 32);
-			uint32_t b;
-			asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(b)
-				: "v"(xh), "s"(kp.r - 2), "v"(rbw));
-			op_mad_s(x[v], 0x40000000u, (int32_t)(b + (uint32_t)kp.round_base));
-			rm[v] = (int32_t)((uint64_t)x[v] >> 32) >> (kp.r - 2);
-		}
-	} else {
-#pragma unroll
-		for (int v = 0; v < kVec; v++)
-			rm[v] = round_to_ow<int64_t>(x[v] >> 30, kp);
-	}
-#pragma unroll
-	for (int v = 0; v < kVec; v++) {		// :2354-2359
-		const uint32_t acc = (uint32_t)((uint64_t)p[v] >> 30);
-		rp[v] = (acc + 0x80000000u) >> kp.pw_shl;
-	}
-	apply_unit_gain<UG>(rm, kp);
-}
-
-// sext_PW((a - b) mod 2^PW) with sh = 32 - PW
-__device__ __forceinline__ int32_t step_of(uint32_t a, uint32_t b, int sh)
-{
-	return (int32_t)((a - b) << sh) >> sh;
-}
+// (pol_lj_vector and step_of: cordic_fm_demod.h, shared with the bank's kernels)
 
 // Tile t is the vectors [t * kFmdTileVecs, (t + 1) * kFmdTileVecs) cut at nvec;
 // thread tid converts vector t * kFmdTileVecs - 1 + 256 * k + tid in pass k.

@@ -1,0 +1,160 @@
+// cordic_fm_demod_bank.h -- FM demodulation banks: many cordic_fm_demod jobs of
+// one r2p / sr2p core in at most TWO launches (include/cordic_amd.h, "FM
+// demodulation banks").  The descriptors the host cuts at create, the cutter
+// itself -- plain C++ that touches no device, so that a stand-alone program can
+// run it under a sanitizer -- and the launchers of the two kernels that walk
+// the descriptors (cordic_fm_demod_bank.hip).  Host-visible types only.
+//
+// No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
+// does not hash this unit.
+#ifndef CORDIC_FM_DEMOD_BANK_H
+#define CORDIC_FM_DEMOD_BANK_H
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "cordic_amd.h"
+
+namespace cordic_amd {
+
+// A run of whole vectors (4 samples) of ONE job, never across the job's end:
+// at most P * 256 - 1 of them (P = 1, 2, 4, 8 passes of a 256-thread block, one
+// lane of which converts the halo -- the vector in front of the run -- again).
+struct DemodTile {
+	uint64_t x, y;		// addresses of the run's first input vector
+	uint64_t mag, freq;	// ... and of its first output vector
+	uint64_t last;		// first == 1: the job's d_last, or 0
+	uint32_t nvec;		// vectors: 1 .. P * 256 - 1
+	uint32_t phase0;	// first == 1: the job's
+	uint32_t first;		// 1: the run starts at sample 0 of its job, the
+	uint32_t pad;		//    halo is (phase0 + *last) mod 2^PW
+};				// 56 bytes
+
+// What the second launch does for a job whose length is no multiple of 4 or
+// that has a d_last: `count` samples from sample s0 = (n / 4 ? n / 4 * 4 - 1
+// : 0) on -- the ones behind the last whole vector and, when first == 0, the
+// one in front of them, which only lends its phase.
+struct DemodTail {
+	uint64_t x, y, mag, freq;	// addresses of sample s0 in the four arrays
+	uint64_t last;			// the job's d_last, or 0
+	uint32_t count;			// 1 .. 4
+	uint32_t phase0;
+	uint32_t first;			// 1: s0 is sample 0 of the job (no whole
+	uint32_t pad;			//    vector): the lane reads *last itself
+};					// 56 bytes
+
+constexpr uint32_t kFmdBankPassVecs = 256;
+// vectors of a full tile of P passes
+constexpr uint32_t fmd_bank_tile_vecs(int passes)
+{
+	return (uint32_t)passes * kFmdBankPassVecs - 1;
+}
+
+// P for a bank of `total_vecs` whole vectors on a device of `cus` CUs: the
+// rule of the data-fed job sets (xy_tile_vecs, cordic_abi.cpp) -- the longest
+// tile that still gives every resident block (8 per CU) four of them -- in the
+// steps 1, 2, 4, 8.
+inline int fmd_bank_passes(uint64_t total_vecs, int cus)
+{
+	const uint64_t per = total_vecs / ((uint64_t)(cus > 0 ? cus : 256) * 8u * 4u);
+	int p = 8;
+	while (p > 1 && (uint64_t)p * kFmdBankPassVecs > per)
+		p >>= 1;
+	return p;
+}
+
+// The argument checks of cordic_demodbank_create that need no device: every
+// job with n > 0 has four non-NULL, 4-byte-aligned sample pointers, an aligned
+// d_last, reserved == 0 and a length within SIZE_MAX >> 4; no output range
+// (d_omag, d_ofreq, the word at d_last) overlaps another output range or any
+// input range of the bank.  Found by sorting the ranges by address: a range
+// that begins inside an earlier one is an overlap, which is refused unless
+// both are inputs.
+inline bool fmd_bank_jobs_valid(size_t njobs, const cordic_demod_job *jobs)
+{
+	struct Range { uint64_t lo, hi; bool out; };
+	std::vector<Range> r;
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_demod_job &jb = jobs[k];
+		if (jb.n == 0)
+			continue;
+		const uintptr_t p[4] = {(uintptr_t)jb.d_xval, (uintptr_t)jb.d_yval,
+			(uintptr_t)jb.d_omag, (uintptr_t)jb.d_ofreq};
+		const uintptr_t l = (uintptr_t)jb.d_last;
+		if (!p[0] || !p[1] || !p[2] || !p[3] || ((p[0] | p[1] | p[2] | p[3] | l) & 3u)
+				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
+			return false;
+		const uint64_t bytes = jb.n * 4;
+		for (int i = 0; i < 4; i++) {
+			if (bytes > ~(uint64_t)0 - p[i])
+				return false;
+			r.push_back(Range{p[i], p[i] + bytes, i >= 2});
+		}
+		if (l)
+			r.push_back(Range{l, (uint64_t)l + 4, true});
+	}
+	std::sort(r.begin(), r.end(),
+		[](const Range &a, const Range &b) { return a.lo < b.lo; });
+	uint64_t any_end = 0, out_end = 0;	// ends of the ranges in front
+	for (const Range &a : r) {
+		if (a.lo < (a.out ? any_end : out_end))
+			return false;
+		any_end = std::max(any_end, a.hi);
+		if (a.out)
+			out_end = std::max(out_end, a.hi);
+	}
+	return true;
+}
+
+// tiles of `tile_vecs` vectors the jobs cut into (saturating at 2^63)
+inline uint64_t fmd_bank_count_tiles(size_t njobs, const cordic_demod_job *jobs,
+		uint32_t tile_vecs)
+{
+	uint64_t t = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		t += (jobs[k].n / 4 + tile_vecs - 1) / tile_vecs;
+		if (t >> 63)
+			break;
+	}
+	return t;
+}
+
+// Cuts valid jobs (fmd_bank_jobs_valid) into tiles, in the jobs' order, and
+// tails, one per job that needs the second launch.
+inline void fmd_bank_cut(size_t njobs, const cordic_demod_job *jobs,
+		uint32_t tile_vecs, std::vector<DemodTile> *tiles,
+		std::vector<DemodTail> *tails)
+{
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_demod_job &jb = jobs[k];
+		if (jb.n == 0)
+			continue;
+		const uint64_t x = (uintptr_t)jb.d_xval, y = (uintptr_t)jb.d_yval,
+			m = (uintptr_t)jb.d_omag, f = (uintptr_t)jb.d_ofreq,
+			l = (uintptr_t)jb.d_last;
+		const uint64_t nvec = jb.n / 4;
+		for (uint64_t v0 = 0; v0 < nvec; v0 += tile_vecs) {
+			const uint64_t live = nvec - v0 < tile_vecs ? nvec - v0 : tile_vecs;
+			const uint64_t at = v0 * 16;
+			tiles->push_back(DemodTile{x + at, y + at, m + at, f + at,
+				v0 ? 0 : l, (uint32_t)live, v0 ? 0u : jb.phase0,
+				v0 ? 0u : 1u, 0u});
+		}
+		if (nvec * 4 == jb.n && !l)
+			continue;
+		const uint64_t s0 = nvec ? nvec * 4 - 1 : 0, at = s0 * 4;
+		tails->push_back(DemodTail{x + at, y + at, m + at, f + at, l,
+			(uint32_t)(jb.n - s0), jb.phase0, nvec ? 0u : 1u, 0u});
+	}
+}
+
+// The two launches.  grid: blocks of the main kernel (1 .. ntiles).  An empty
+// table launches nothing.  CORDIC_OK or CORDIC_ERR_DEVICE.
+int	launch_fmd_bank(const cordic_config &cfg, const DemodTile *d_tiles,
+		uint32_t ntiles, int grid, const DemodTail *d_tails, uint32_t ntails,
+		void *stream);
+
+} // namespace cordic_amd
+#endif

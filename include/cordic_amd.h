@@ -949,6 +949,77 @@ int	cordic_fm_demod16(const cordic_config *cfg, size_t n,
 		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work,
 		void *stream);
 
+/* FM demodulation banks: many discriminator jobs in one launch.
+ *
+ * What job sets are to the CORDIC cores and oscillator banks to the table
+ * cores, for cordic_fm_demod: the block that ends a channeliser's receive chain
+ * when the channels carry FM or FSK or feed an AFC loop.  Hundreds or thousands
+ * of SHORT blocks, each with its own arrays, length, phase0 and d_last, are
+ * described once; one cordic_demodbank_run then gives, for every job, bit for
+ * bit what
+ *   cordic_fm_demod(cfg, n, d_xval, d_yval, phase0, d_last, d_omag, d_ofreq, ..)
+ * gives -- *d_last afterwards, CORDIC_FLAG_UNIT_GAIN and the rule that phase0
+ * is added by every run included.  So a bank whose jobs have a d_last and
+ * phase0 == 0, run k times on new data in the same arrays, demodulates k
+ * consecutive blocks per channel with no host work in between, and a captured
+ * run replayed k times continues k times.
+ *
+ * Create is host work with blocking uploads: CORDIC_ERR_UNSUPPORTED while the
+ * legacy stream is being captured.  It copies the configuration.
+ * CORDIC_ERR_MODE for a rotator; CORDIC_ERR_ARGS for a NULL cfg or bank, NULL
+ * jobs with njobs > 0, 2^28 or more jobs, 2^32 or more tiles, and for a job
+ * with n > 0 (a zero-length job's pointers are not looked at): a NULL or not
+ * 4-byte-aligned sample pointer, a misaligned d_last, reserved != 0, n beyond
+ * SIZE_MAX >> 4.  No output range of the bank -- every job's d_omag, d_ofreq
+ * and the 4 bytes at its d_last -- may overlap another output range or any
+ * job's input range (CORDIC_ERR_ARGS, found by sorting the ranges; two jobs
+ * sharing a d_last is such an overlap); inputs may alias each other.
+ * njobs == 0 or all-empty jobs give a valid bank whose run launches nothing.
+ * The bank belongs to the device that was current at create: CORDIC_ERR_ARGS
+ * from run on another device.
+ *
+ * Two paths, identical bits, chosen at create and told by cordic_demodbank_info:
+ *   fused       the cores for which cordic_fm_demod_info answers 1.  The whole
+ *               bank is at most TWO kernel launches on `stream`: the fused
+ *               kernel of cordic_fm_demod reading tile descriptors -- every
+ *               job's whole vectors cut into tiles of (P * 256 - 1) * 4
+ *               samples, P = 1, 2, 4 or 8 by the bank's size, never across a
+ *               job's end -- and, when a job's length is no multiple of 4 or
+ *               it has a d_last, one small launch with a lane per such job.
+ *               ANY 4-byte-aligned arrays are served here (the 16-byte
+ *               condition of the single call does not carry over).  Nothing is
+ *               allocated, copied or synchronised, no block waits for another,
+ *               no tile queue is taken; legal inside a stream capture.  Every
+ *               *d_last is read in the first launch (a job shorter than 4: by
+ *               the lane that writes it) and written only by the second.
+ *   one by one  every other core (WW >= 35, wrap, CORDIC_FLAG_NO_LJ /
+ *               _FORCE_GENERIC): run loops cordic_fm_demod over the jobs on
+ *               `stream`, with a scratch area the bank allocated at create for
+ *               its longest job; legal inside a capture as well.
+ * There is no 16-bit form: cordic_fm_demod16 has no fused kernel that a bank
+ * could be the tile form of.
+ *
+ * cordic_demodbank_info (any pointer may be NULL): *samples = the samples of
+ * all jobs; *tiles = the tiles the main kernel walks; *tail_jobs = the jobs
+ * the second launch has work for (both 0 one by one); *fused = 1 / 0; *tile =
+ * the output samples of a full tile, (P * 256 - 1) * 4, 0 one by one.
+ */
+typedef struct cordic_demod_job {
+	const int32_t *d_xval, *d_yval;	/* n words each                          */
+	int32_t	*d_omag, *d_ofreq;	/* n words each                          */
+	uint32_t *d_last;		/* optional device word (NULL: none)     */
+	uint64_t n;			/* samples; 0 allowed                    */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                     */
+} cordic_demod_job;			/* 56 bytes                              */
+typedef struct cordic_demodbank cordic_demodbank;
+int	cordic_demodbank_create(const cordic_config *cfg, size_t njobs,
+		const cordic_demod_job *jobs, cordic_demodbank **bank);
+void	cordic_demodbank_destroy(cordic_demodbank *bank);
+int	cordic_demodbank_info(const cordic_demodbank *bank, uint64_t *samples,
+		uint32_t *tiles, uint32_t *tail_jobs, int32_t *fused, int32_t *tile);
+int	cordic_demodbank_run(const cordic_demodbank *bank, void *stream);
+
 /* -------------------------------------------------------------- FM mixer
  *
  * cordic_plan_mix with one tuning word PER SAMPLE: the rotator multiplies the

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import cordic_amd as ca
+from test_xydir_matrix import split, tie_folded
 
 CASES = [((ca.P2R, 32, 32, 2, 32, 16), [5, 5, 5]),
          ((ca.P2R, 32, 32, 2, 32, 24), [4, 4, 5, 5, 5]),
@@ -15,6 +16,13 @@ CASES = [((ca.P2R, 32, 32, 2, 32, 16), [5, 5, 5]),
          ((ca.P2R, 16, 16, 2, -1, -1), [4, 4, 5, 5]),
          ((ca.SP2R, 32, 32, 2, 32, 16), [4, 4, 5]),
          ((ca.P2R, 13, 13, 2, -1, -1), None)]
+# every instance of the kernel: left-justified by 29 (WW 35) and by 30 (WW 34),
+# 13 .. 29 stages, and the 24-bit ports (WW 27) up to their 27; then the two
+# narrow-phase cores of tests/test_xydir_matrix.py
+MATRIX = ([(ca.P2R, 32, 32, 2, 32, n) for n in range(13, 30)]
+          + [(ca.P2R, 31, 31, 2, 32, n) for n in range(13, 30)]
+          + [(ca.P2R, 24, 24, 2, 32, n) for n in range(13, 28)]
+          + [(ca.P2R, 24, 24, 2, 20, 20), (ca.P2R, 16, 16, 2, 16, 16)])
 
 
 def parse(words):
@@ -32,9 +40,10 @@ def parse(words):
     return bias0, bias_last, groups
 
 
-def chain_errors(cfg, words, sizes=None, nrandom=300000):
+def chain_errors(cfg, words, sizes=None, nrandom=300000, ties=None):
     """number of phases on which the chain of lookups disagrees with the
-    recurrence (directions of a group, or the residual behind the last one)"""
+    recurrence (directions of a group, or the residual behind the last one);
+    ties: folded phases in 32-bit units to try next to the random ones"""
     bias0, bias_last, groups = parse(words)
     if sizes is not None:
         assert [g[0] for g in groups] == sizes
@@ -52,6 +61,9 @@ def chain_errors(cfg, words, sizes=None, nrandom=300000):
     brk = (brk[:, None] + np.arange(-2, 3)[None, :]).ravel()
     brk = brk[(brk >= -(1 << 29)) & (brk < (1 << 29))]
     p0 = np.concatenate([p0, brk, [-(1 << 29), (1 << 29) - 1, 0, -1]])
+    if ties is not None:
+        assert ties.min() >= -(1 << 29) and ties.max() < 1 << 29
+        p0 = np.concatenate([p0, ties])
     # stage 1 is the fold's
     pos = p0 >= 0
     p = np.where(pos, p0 - ang[0], p0 + ang[0])
@@ -90,6 +102,29 @@ def test_lookup_chain_matches_the_recurrence(args, sizes):
     # LDS the kernel needs: fold rows + per group buckets and leaf entries
     lds = 128 + sum(nb * 8 + nl * 48 for _, _, nb, nl, _, _ in groups)
     assert lds < 60 * 1024
+
+
+@pytest.mark.parametrize("args", MATRIX,
+                         ids=["%d-%d-pw%d-n%d" % (a[1], a[2], a[4], a[5]) for a in MATRIX])
+def test_lookup_chain_of_every_instance_on_the_ties_of_every_stage(args):
+    """the group split restated from the stage count alone, and next to the
+    random phases those that put a residual of -2 .. 2 in front of every
+    looked-up stage (tests/test_xydir_matrix.py: tie_folded), not of 12"""
+    cfg = ca.Config.from_cli(*args)
+    if args[4] == 32:
+        assert cfg.nlive == args[5] and cfg.pw == 32
+    assert cfg.ww <= 35 and not cfg.needs_wrap and cfg.ww - cfg.iw - 1 == 2
+    words = ca.dir_table(cfg)
+    assert words is not None
+    ties = tie_folded(cfg.angles, cfg.pw, cfg.nlive) << (32 - cfg.pw)
+    assert ties.size > 3 * 64 * 5 * cfg.nlive // 4
+    errors, groups, pmax = chain_errors(cfg, words, split(cfg.nlive), nrandom=100000,
+                                        ties=ties)
+    assert errors == 0
+    if cfg.nlive > 25:
+        assert pmax < 1 << 28
+    lds = 128 + sum(nb * 8 + nl * 48 for _, _, nb, nl, _, _ in groups)
+    assert lds < 10 * 1024
 
 
 def test_the_chain_check_discriminates():

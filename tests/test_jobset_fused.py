@@ -74,12 +74,13 @@ def _scaled(a, k):
     return a if k is None else ((a.astype(np.int64) * k) >> 32).astype(np.int32)
 
 
-def _ragged_set(kind, cfg, seed):
-    """RAGGED jobs at odd offsets of shared arrays with guard words around:
-    (jobs, host inputs, output views, big output arrays)"""
+def _ragged_set(kind, cfg, seed, sizes=None):
+    """RAGGED jobs (or jobs of the given sizes) at odd offsets of shared arrays
+    with guard words around: (jobs, host inputs, output views, big output
+    arrays)"""
     torch, DEV, dev_i32, to_np, RAGGED, _iq, both, carve = _gpu()
     rng = np.random.RandomState(seed)
-    sizes = RAGGED
+    sizes = RAGGED if sizes is None else sizes
     offs = [int(v) for v in rng.randint(0, 4, len(sizes))]
     total = sum(sizes) + 32 * len(sizes)
     xv, _ = carve(total, sizes, offs)

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "cordic_amd.h"
+#include "cordic_fm_demod.h"
 
 namespace cordic_amd {
 
@@ -32,18 +33,8 @@ struct DemodTile {
 	uint32_t pad;		//    halo is (phase0 + *last) mod 2^PW
 };				// 56 bytes
 
-// What the second launch does for a job whose length is no multiple of 4 or
-// that has a d_last: `count` samples from sample s0 = (n / 4 ? n / 4 * 4 - 1
-// : 0) on -- the ones behind the last whole vector and, when first == 0, the
-// one in front of them, which only lends its phase.
-struct DemodTail {
-	uint64_t x, y, mag, freq;	// addresses of sample s0 in the four arrays
-	uint64_t last;			// the job's d_last, or 0
-	uint32_t count;			// 1 .. 4
-	uint32_t phase0;
-	uint32_t first;			// 1: s0 is sample 0 of the job (no whole
-	uint32_t pad;			//    vector): the lane reads *last itself
-};					// 56 bytes
+// (What the second launch does for a job whose length is no multiple of 4 or
+// that has a d_last: DemodTail, cordic_fm_demod.h -- the single call's tail.)
 
 constexpr uint32_t kFmdBankPassVecs = 256;
 // vectors of a full tile of P passes
@@ -51,6 +42,8 @@ constexpr uint32_t fmd_bank_tile_vecs(int passes)
 {
 	return (uint32_t)passes * kFmdBankPassVecs - 1;
 }
+static_assert(kFmdTileVecs == fmd_bank_tile_vecs(kFmdPasses),
+	"a tile of the single call is a bank's tile of 8 passes");
 
 // P for a bank of `total_vecs` whole vectors on a device of `cus` CUs: the
 // rule of the data-fed job sets (xy_tile_vecs, cordic_abi.cpp) -- the longest

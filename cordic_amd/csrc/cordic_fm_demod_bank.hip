@@ -10,23 +10,14 @@
 //       job's whole vectors into tiles of at most P * 256 - 1 vectors, never
 //       across a job's end; block b sweeps tiles b, b + gridDim.x, ... in the
 //       table's order, which is the jobs' own.  Per tile the descriptor arrives
-//       as scalar loads; lane j of the sweep (j = 256 * pass + thread) converts
-//       vector j - 1 of the tile, so lane 0 converts the halo -- the vector in
-//       front of the tile, which belongs to the same job -- and stores nothing.
-//       In a job's first tile there is no such vector: lane 0 loads nothing and
-//       holds (phase0 + *d_last) mod 2^PW instead.  The predecessor travels as
-//       in fm_demod_lj: one DPP move inside a wave, one LDS word per wave
-//       between waves and passes, double-buffered by pass, ONE barrier per pass
-//       (the argument there holds from tile to tile as well: the parity simply
-//       keeps alternating, and pass 0 of a tile uses no word of the pass in
-//       front).  A tile of nvec vectors takes nvec / 256 + 1 passes, the same
-//       for all threads of the block, so the kernel does not need P.
+//       as scalar loads and goes to sweep_tile (cordic_fm_demod.h), which
+//       fm_demod_lj runs as well: the halo lane, the way the predecessor travels
+//       and the ONE barrier per pass are written there.  A tile of nvec vectors
+//       takes nvec / 256 + 1 passes, so the kernel does not need P.
 //   fm_demod_bank_tails   one lane per job whose length is no multiple of 4 or
-//       that has a d_last (DemodTail): the samples behind the last whole vector
-//       and the one in front of them, at most 4, gathered into one zero-padded
-//       vector, converted by the same pol_lj_vector instance, differenced,
-//       stored; then *d_last.  A job without a whole vector reads its *d_last
-//       here, in the same lane, before writing it.
+//       that has a d_last (DemodTail), by tail_of (cordic_fm_demod.h), the
+//       single call's tail as well: at most 4 samples converted by the same
+//       pol_lj_vector instance, differenced, stored; then *d_last.
 // Every *d_last is read in the first launch or by the lane that writes it, and
 // written only in the second launch, which follows in stream order: no block
 // can see a value the same run writes.  Nothing is allocated, copied or
@@ -39,8 +30,8 @@
 // run, as cordic_fm_demod does).  The bits depend on neither.
 //
 // Registers (.vgpr_count / scratch bytes of the gfx950 code objects, -O3,
-// --save-temps), next to the table in cordic_fm_demod.hip (fm_demod_lj 54 / 93,
-// topolar_lj_jobs 57 / 97):
+// --save-temps; profiles/r14/fm_refactor_isa.txt), next to the table in
+// cordic_fm_demod.hip (fm_demod_lj 56 / 94, topolar_lj_jobs 57 / 97):
 //                               fm_demod_lj_bank   fm_demod_bank_tails
 //   20 stages, PLAIN               46 / 0            40 / 0
 //   29 stages, PLAIN               46 / 0            40 / 0
@@ -48,9 +39,10 @@
 //   dynamic exit, unit gain        85 / 0            76 / 0
 // With 512 registers per lane of a SIMD, allocated in eights: 48 -> 8 waves (the
 // most a SIMD holds) for the static instances and 88 -> 5 waves for the dynamic
-// ones, the steps fm_demod_lj stands on (56 and 96); the 32-bit indices inside
-// a tile cost fewer registers than its 64-bit ones.  No instance spills.  32
-// bytes of LDS per block of the main kernel, none in the tail kernel.
+// ones, one step of eight below fm_demod_lj's 56 and 96 at the same numbers of
+// waves: it keeps its index inside a tile in 32 bits and one scalar pointer per
+// array, where the single call carries a 64-bit index per lane.  No instance
+// spills.  32 bytes of LDS per block of the main kernel, none in the tail kernel.
 //
 // ONE BY ONE (every other core: WW >= 35, wrap, CORDIC_FLAG_NO_LJ /
 // _FORCE_GENERIC): run loops cordic_fm_demod over the jobs on the stream, with
@@ -66,7 +58,8 @@
 #include "cordic_launch.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_devmem.h"
-#include "cordic_fm_demod.h"
+#include "cordic_table_nco.h"
+#include "cordic_hostargs.h"
 #include "cordic_fm_demod_bank.h"
 
 namespace cordic_amd {
@@ -80,78 +73,18 @@ __global__ __launch_bounds__(kBlock) void fm_demod_lj_bank(CoreParams kp,
 		const DemodTile *__restrict__ tiles, uint32_t ntiles)
 {
 	__shared__ uint32_t edge[2][kBlock / 64];
-	const unsigned tid = threadIdx.x, lane = tid & 63u;
-	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-	PolLjRegs c;
-	c.sign = vgpr_const(0x80000000u);
-	c.p30 = vgpr_const(0x40000000u);
-	const uint32_t rbw = vgpr_const(kp.round_bit);
-	const int up = 32 - kp.iw;
-	const int down = up - kp.in_shl;
-	const int sh = kp.pw_shl;
-
+	const LaneConsts ln(kp);
 	unsigned par = 0;
 	for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
 		const DemodTile d = tiles[t];
-		// lane j's vector is element j of these: element 0 is the halo
-		const i32x4g *xin = reinterpret_cast<const i32x4g *>((uintptr_t)d.x) - 1;
-		const i32x4g *yin = reinterpret_cast<const i32x4g *>((uintptr_t)d.y) - 1;
-		i32x4g *omag = reinterpret_cast<i32x4g *>((uintptr_t)d.mag) - 1;
-		i32x4g *ofreq = reinterpret_cast<i32x4g *>((uintptr_t)d.freq) - 1;
-		const uint32_t nvec = d.nvec;
-		const bool first = d.first != 0;
-
-		uint32_t prev = 0;	// the lane in front of sample 0 alone needs it
-		if (first && tid == 0) {
-			const uint32_t *lp = reinterpret_cast<const uint32_t *>((uintptr_t)d.last);
-			prev = (d.phase0 + (lp ? *lp : 0u)) & (0xffffffffu >> sh);
-		}
-		uint32_t j = tid;
-		i32x4g nx{}, ny{};	// software prefetch, afresh per tile
-		if (j <= nvec && !(first && j == 0)) {
-			nx = CORDIC_LOAD_IN(&xin[j]);
-			ny = CORDIC_LOAD_IN(&yin[j]);
-		}
-		// (thread 0's vector is behind the end: so is everyone's)
-		for (uint32_t k0 = 0; k0 <= nvec; k0 += kBlock, j += kBlock) {
-			const i32x4 tx = nx, ty = ny;
-			const uint32_t jn = j + kBlock;
-			if (jn <= nvec) {
-				nx = CORDIC_LOAD_IN(&xin[jn]);
-				ny = CORDIC_LOAD_IN(&yin[jn]);
-			}
-			i32x4 rm;
-			u32x4 rp;
-			pol_lj_vector<NLIVE, DYN, UG, PLAIN>(kp, c, rbw, up, down, tx, ty,
-				rm, rp);
-
-			uint32_t last = rp[3];
-			if (first && j == 0)	// in front of sample 0
-				last = prev;
-			if (lane == 63)
-				edge[par][wave] = last;
-			uint32_t front = 0;
-			if (wave == 0)		// (pass 0: the halo lane's, unused)
-				front = edge[par ^ 1][kBlock / 64 - 1];
-			__syncthreads();
-			if (wave != 0)
-				front = edge[par][wave - 1];
-			par ^= 1;
-			// wave_shr:1 -- lane l gets lane l - 1's `last`, lane 0 keeps
-			// `front`
-			const uint32_t before = (uint32_t)__builtin_amdgcn_update_dpp(
-				(int)front, (int)last, 0x138, 0xf, 0xf, false);
-			i32x4 rf;
-			rf[0] = step_of(rp[0], before, sh);
-#pragma unroll
-			for (int v = 1; v < kVec; v++)
-				rf[v] = step_of(rp[v], rp[v - 1], sh);
-			if (j != 0 && j <= nvec) {	// (not the halo)
-				CORDIC_STORE_OUT(true, &omag[j], rm);
-				CORDIC_STORE_OUT(true, &ofreq[j], rf);
-			}
-		}
+		// element 0 of these is the halo
+		sweep_tile<NLIVE, DYN, UG, PLAIN>(kp, ln,
+			reinterpret_cast<const i32x4g *>((uintptr_t)d.x) - 1,
+			reinterpret_cast<const i32x4g *>((uintptr_t)d.y) - 1,
+			reinterpret_cast<i32x4g *>((uintptr_t)d.mag) - 1,
+			reinterpret_cast<i32x4g *>((uintptr_t)d.freq) - 1, (uint32_t)0, d.nvec,
+			d.first != 0, d.phase0,
+			reinterpret_cast<const uint32_t *>((uintptr_t)d.last), edge, par);
 	}
 }
 
@@ -165,56 +98,11 @@ __global__ __launch_bounds__(kTailBlock) void fm_demod_bank_tails(CoreParams kp,
 	if (i >= ntails)
 		return;
 	const DemodTail d = tails[i];
-	PolLjRegs c;
-	c.sign = vgpr_const(0x80000000u);
-	c.p30 = vgpr_const(0x40000000u);
-	const uint32_t rbw = vgpr_const(kp.round_bit);
-	const int up = 32 - kp.iw;
-	const int down = up - kp.in_shl;
-	const int sh = kp.pw_shl;
-
-	const int32_t *x = reinterpret_cast<const int32_t *>((uintptr_t)d.x);
-	const int32_t *y = reinterpret_cast<const int32_t *>((uintptr_t)d.y);
-	int32_t *omag = reinterpret_cast<int32_t *>((uintptr_t)d.mag);
-	int32_t *ofreq = reinterpret_cast<int32_t *>((uintptr_t)d.freq);
-	uint32_t *lp = reinterpret_cast<uint32_t *>((uintptr_t)d.last);
-	i32x4 tx{}, ty{};
-#pragma unroll
-	for (int v = 0; v < kVec; v++)
-		if ((uint32_t)v < d.count) {
-			tx[v] = x[v];
-			ty[v] = y[v];
-		}
-	i32x4 rm;
-	u32x4 rp;
-	pol_lj_vector<NLIVE, DYN, UG, PLAIN>(kp, c, rbw, up, down, tx, ty, rm, rp);
-	// element 0 only lends its phase when a whole vector was in front
-	uint32_t p = rp[0];
-	if (d.first) {
-		p = (d.phase0 + (lp ? *lp : 0u)) & (0xffffffffu >> sh);
-		omag[0] = rm[0];
-		ofreq[0] = step_of(rp[0], p, sh);
-		p = rp[0];
-	}
-#pragma unroll
-	for (int v = 1; v < kVec; v++)
-		if ((uint32_t)v < d.count) {
-			omag[v] = rm[v];
-			ofreq[v] = step_of(rp[v], p, sh);
-			p = rp[v];
-		}
-	if (lp)
-		*lp = p;
-}
-
-static int check_launch()
-{
-	return hipGetLastError() == hipSuccess ? CORDIC_OK : CORDIC_ERR_DEVICE;
+	tail_of<NLIVE, DYN, UG, PLAIN>(kp, d);
 }
 
 } // namespace fmd
 
-// the instance choice of launch_lj (cordic_fm_demod.hip), for both kernels
 int launch_fmd_bank(const cordic_config &cfg, const DemodTile *d_tiles,
 		uint32_t ntiles, int grid, const DemodTail *d_tails, uint32_t ntails,
 		void *stream)
@@ -224,26 +112,16 @@ int launch_fmd_bank(const cordic_config &cfg, const DemodTile *d_tiles,
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	const CoreParams kp = make_params_jobs(cfg);
 	const int tgrid = (int)((ntails + kTailBlock - 1) / kTailBlock);
-#define FMD_BANK_LAUNCH(...) do { \
-	if (ntiles) \
-		hipLaunchKernelGGL((fm_demod_lj_bank<__VA_ARGS__>), dim3(grid), \
-			dim3(kBlock), 0, st, kp, d_tiles, ntiles); \
-	if (ntails) \
-		hipLaunchKernelGGL((fm_demod_bank_tails<__VA_ARGS__>), dim3(tgrid), \
-			dim3(kTailBlock), 0, st, kp, d_tails, ntails); \
-	} while (0)
-	const bool plain = (32 - kp.iw) - kp.in_shl >= 2 && kp.r >= 2 && kp.r <= 31;
-	if (kp.post_mul != 0) {		// CORDIC_FLAG_UNIT_GAIN
-		FMD_BANK_LAUNCH(kDynStages, true, true, false);
-	} else if (plain && cfg.nlive == 20) {
-		FMD_BANK_LAUNCH(20, false, false, true);
-	} else if (plain && cfg.nlive == 29) {
-		FMD_BANK_LAUNCH(29, false, false, true);
-	} else {
-		FMD_BANK_LAUNCH(kDynStages, true, false, false);
-	}
-#undef FMD_BANK_LAUNCH
-	return check_launch();
+	with_instance(cfg, kp, [&](auto inst) {
+		typedef decltype(inst) I;
+		if (ntiles)
+			hipLaunchKernelGGL((fm_demod_lj_bank<I::nlive, I::dyn, I::ug, I::plain>),
+				dim3(grid), dim3(kBlock), 0, st, kp, d_tiles, ntiles);
+		if (ntails)
+			hipLaunchKernelGGL((fm_demod_bank_tails<I::nlive, I::dyn, I::ug, I::plain>),
+				dim3(tgrid), dim3(kTailBlock), 0, st, kp, d_tails, ntails);
+	});
+	return tnco::finish(true);
 }
 
 } // namespace cordic_amd
@@ -268,12 +146,11 @@ int cordic_demodbank_create(const cordic_config *cfg, size_t njobs,
 		const cordic_demod_job *jobs, cordic_demodbank **bank)
 {
 	using namespace cordic_amd;
-	if (!cfg || !bank || (njobs && !jobs))
+	if (!bank || (njobs && !jobs))
 		return CORDIC_ERR_ARGS;
-	if (cfg->mode != CORDIC_R2P && cfg->mode != CORDIC_SR2P)
-		return CORDIC_ERR_MODE;
-	if (!config_sane(*cfg) || njobs >= ((size_t)1 << 28)
-			|| !fmd_bank_jobs_valid(njobs, jobs))
+	if (int rc = fmd_check_core(cfg))
+		return rc;
+	if (njobs >= ((size_t)1 << 28) || !fmd_bank_jobs_valid(njobs, jobs))
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();	// (a stale error is not this call's)
 	// blocking uploads below: not while the legacy stream is being captured
@@ -391,12 +268,8 @@ int cordic_demodbank_run(const cordic_demodbank *bank, void *stream)
 	}
 	if (!bank->ntiles && !bank->ntails)
 		return CORDIC_OK;
-	size_t cap = (size_t)bank->cus * 8;	// resident blocks
-	if (const char *e = std::getenv("CORDIC_FMD_MAX_BLOCKS")) {
-		const long v = std::strtol(e, nullptr, 10);
-		if (v >= 1 && (size_t)v < cap)
-			cap = (size_t)v;
-	}
+	// resident blocks
+	const size_t cap = env_block_cap("CORDIC_FMD_MAX_BLOCKS", (size_t)bank->cus * 8);
 	const int grid = (int)(bank->ntiles < cap ? bank->ntiles : cap);
 	return launch_fmd_bank(bank->cfg, bank->d_tiles, bank->ntiles, grid,
 		bank->d_tails, bank->ntails, stream);

@@ -62,11 +62,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 
 #include "cordic_xydir.h"
 #include "cordic_launch.h"
 #include "cordic_jobs_fused.h"
+#include "cordic_hostargs.h"
 #include "cordic_fm_mix.h"
 
 namespace cordic_amd {
@@ -441,21 +441,6 @@ __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da
 }
 
 // ---------------------------------------------------------------- host side
-struct Range {
-	uintptr_t lo;
-	size_t	bytes;
-};
-
-static Range range_of(const void *p, size_t bytes)
-{
-	return Range{reinterpret_cast<uintptr_t>(p), p ? bytes : 0};
-}
-
-static bool hits(const Range &a, const Range &b)
-{
-	return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
-}
-
 // the tables and the exchange words behind them
 static size_t lds_bytes(const DxInfo &dx, uint32_t *xw)
 {
@@ -531,15 +516,7 @@ int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		range_of(d_acc, 4), range_of(d_work, work_bytes)};
 	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
 		range_of(d_xval, n * 4), range_of(d_yval, n * 4)};
-	for (int i = 0; i < 4; i++) {
-		for (int j = i + 1; j < 4; j++)
-			if (hits(out[i], out[j]))
-				return CORDIC_ERR_ARGS;
-		for (int j = 0; j < 4; j++)
-			if (hits(out[i], in[j]))
-				return CORDIC_ERR_ARGS;
-	}
-	return CORDIC_OK;
+	return outputs_overlap(out, in) ? CORDIC_ERR_ARGS : CORDIC_OK;
 }
 
 int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
@@ -567,11 +544,7 @@ int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 	size_t cap = (size_t)cus * per_cu;
 	if (cap > kFmxMaxBlocks)
 		cap = kFmxMaxBlocks;
-	if (const char *e = std::getenv("CORDIC_FMX_MAX_BLOCKS")) {
-		const long v = std::strtol(e, nullptr, 10);
-		if (v >= 1 && (size_t)v < cap)
-			cap = (size_t)v;
-	}
+	cap = env_block_cap("CORDIC_FMX_MAX_BLOCKS", cap);
 	const size_t npass = (n + kFmxPass - 1) / kFmxPass;
 	const size_t per_block = (npass + cap - 1) / cap;
 	const size_t span = per_block * kFmxPass;

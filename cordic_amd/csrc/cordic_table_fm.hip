@@ -44,6 +44,7 @@
 #include "cordic_table_fm.h"
 #include "cordic_table_nco.h"
 #include "cordic_jobs_fused.h"
+#include "cordic_hostargs.h"
 
 namespace cordic_amd {
 
@@ -283,21 +284,6 @@ __global__ __launch_bounds__(1024) void table_fm(CORE core, FmArgs a, T *d_sin,
 }
 
 // ---------------------------------------------------------------- host side
-struct Range {
-	uintptr_t lo;
-	size_t	bytes;
-};
-
-static Range range_of(const void *p, size_t bytes)
-{
-	return Range{reinterpret_cast<uintptr_t>(p), p ? bytes : 0};
-}
-
-static bool hits(const Range &a, const Range &b)
-{
-	return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
-}
-
 // Alignment, and no output range over anything else.  out0 == d_fcw exactly is
 // the in-place form where `inplace` allows it.
 static int check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
@@ -316,16 +302,7 @@ static int check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 	const Range out[4] = {range_of(out0, n * esize), range_of(out1, n * esize),
 		range_of(d_acc, 4), range_of(d_work, kFmWorkBytes)};
 	const Range in[2] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4)};
-	for (int i = 0; i < 4; i++) {
-		for (int j = i + 1; j < 4; j++)
-			if (hits(out[i], out[j]))
-				return CORDIC_ERR_ARGS;
-		for (int j = 0; j < 2; j++)
-			if (hits(out[i], in[j]) && !(inplace && i == 0 && j == 0
-					&& out[0].lo == in[0].lo))
-				return CORDIC_ERR_ARGS;
-	}
-	return CORDIC_OK;
+	return outputs_overlap(out, in, inplace) ? CORDIC_ERR_ARGS : CORDIC_OK;
 }
 
 } // namespace tfm

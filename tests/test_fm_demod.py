@@ -32,7 +32,10 @@ CORES = {
     "wrap32": ((ca.R2P, 24, 1, 2, 32, -1), 0),
     "cfg3_no_lj": ((ca.R2P, 24, 24, 2, -1, 20), ca.FLAG_NO_LJ),
     "cfg3_generic": ((ca.R2P, 24, 24, 2, -1, 20), ca.FLAG_FORCE_GENERIC),
-    "pw20": ((ca.R2P, 16, 16, 2, 20, -1), 0),
+    "pw20": ((ca.R2P, 16, 16, 2, 20, -1), 0),              # 17 live stages
+    # fused cores on the dynamic-exit instance without unit gain
+    "ww33": ((ca.R2P, 25, 25, 2, 32, -1), 0),              # 29 live stages
+    "ww34_ow2": ((ca.R2P, 26, 2, 2, 32, 20), 0),
     "io16": ((ca.R2P, 16, 16, 2, 16, -1), 0),
 }
 FUSED = ("cfg3", "natr2p24", "ug_lj", "sr2p")
@@ -99,7 +102,8 @@ def test_the_workspace_size_is_small_aligned_and_monotonic():
 
 @pytest.mark.parametrize("name,fused", [
     ("cfg3", 1), ("natr2p24", 1), ("ug_lj", 1), ("sr2p", 1), ("r2p35", 0),
-    ("r2p32", 0), ("wrap32", 0), ("cfg3_no_lj", 0), ("cfg3_generic", 0)])
+    ("r2p32", 0), ("wrap32", 0), ("cfg3_no_lj", 0), ("cfg3_generic", 0),
+    ("ww33", 1), ("ww34_ow2", 1), ("pw20", 1)])
 def test_the_path_query_names_the_fused_cores(name, fused):
     cfg = both(name)[0]
     got, tile = ca.fm_demod_info(cfg)
@@ -336,6 +340,64 @@ def test_gpu_fused_on_one_three_and_seven_blocks(name, monkeypatch):
         assert tiles_of(cfg, n) >= 3 * cap
         monkeypatch.setenv("CORDIC_FMD_MAX_BLOCKS", str(cap))
         check(torch, name, x, y, work, tag=cap)
+
+
+def bank_run(torch, cfg, x, y, phase0, last):
+    """the same call as run(), as the one job of a DemodBank"""
+    n = x.size
+    dx, dy = Padded(torch, n, 4, src=x), Padded(torch, n, 4, src=y)
+    dm, df = Padded(torch, n, 4), Padded(torch, n, 4)
+    bank = ca.DemodBank(cfg, [(dx.view, dy.view, dm.view, df.view, n, phase0, last)])
+    info = bank.info()
+    assert info["fused"] == 1 and info["samples"] == n
+    bank.run()
+    torch.cuda.synchronize()
+    bank.close()
+    assert np.array_equal(dx.get(), x) and np.array_equal(dy.get(), y)
+    return dm.get(), df.get()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["ww33", "ww34_ow2", "pw20"])
+def test_gpu_fused_instances_the_other_cores_do_not_reach(name, monkeypatch):
+    """The dynamic-exit instance without unit gain, on the three forms the
+    cores of FUSED leave out: stage 1 for WW 33 and for WW 34, the rounding
+    outside 2 <= r <= 31 (a 2-bit output) and a PW below 32.  n = 1 is a tail
+    without a whole vector, 5 a tail behind one, T + 2 a tile's edge, 2 T + 5 a
+    second tile; with and without a d_last word; the grid left alone and capped
+    at one block; the single call and a bank of that one job, each against the
+    oracle and so against each other."""
+    import torch
+    cfg, ocfg, gain = both(name)
+    assert (cfg.ww, cfg.nlive, cfg.ow, cfg.pw) == {
+        "ww33": (33, 29, 25, 32), "ww34_ow2": (34, 20, 2, 32),
+        "pw20": (24, 17, 16, 20)}[name]
+    fused, T = ca.fm_demod_info(cfg)
+    assert (fused, T) == (1, 8188)
+    work = work_buffer(torch, 2 * T + 5)
+    rng = np.random.default_rng(22)
+    phase0, preset = 0x9e3779b1, 0x7f4a7c15
+    for n in (1, 5, T + 2, 2 * T + 5):
+        x, y = hard_points(rng, n, cfg.iw) if n > T else iq(rng, n, cfg.iw)
+        for with_last in (True, False):
+            wm, wf, wl = expected(ocfg, gain, cfg.pw, x, y,
+                                  phase0 + (preset if with_last else 0))
+            for cap in (None, 1):
+                if cap is None:
+                    monkeypatch.delenv("CORDIC_FMD_MAX_BLOCKS", raising=False)
+                else:
+                    monkeypatch.setenv("CORDIC_FMD_MAX_BLOCKS", str(cap))
+                for path in ("call", "bank"):
+                    tag = (name, n, with_last, cap, path)
+                    last = last_word(torch, preset) if with_last else None
+                    if path == "call":
+                        m, f = run(torch, cfg, work, x, y, phase0, last)
+                    else:
+                        m, f = bank_run(torch, cfg, x, y, phase0, last)
+                    assert np.array_equal(m, wm), tag
+                    assert np.array_equal(f, wf), tag
+                    if with_last:
+                        assert last_value(last) == wl, tag
 
 
 FALLBACK_SIZES = (1, 5, 255, 256, 257, 4099, (1 << 20) + 3)

@@ -315,6 +315,14 @@ ABI = {
                                      C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_mixbank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
+    "cordic_mixbank_destroy": (None, [C.c_void_p]),
+    "cordic_mixbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32)]),
+    "cordic_mixbank_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_void_p)]),
     "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -1802,6 +1810,71 @@ class DemodBank:
     def close(self):
         if getattr(self, "_h", None):
             lib().cordic_demodbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _CFmMixJob(C.Structure):
+    """cordic_fmmix_job"""
+    _fields_ = [("d_fcw", C.c_void_p), ("d_pm", C.c_void_p),
+                ("d_xval", C.c_void_p), ("d_yval", C.c_void_p),
+                ("d_oxval", C.c_void_p), ("d_oyval", C.c_void_p),
+                ("d_acc", C.c_void_p), ("n", C.c_uint64),
+                ("phase0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_FMMIX_KEYS = ("fcw", "pm", "x", "y", "ox", "oy", "n", "phase0", "acc")
+
+
+class MixBank:
+    """cordic_mixbank: many fm_mix jobs of one p2r / sp2r plan, cut once and
+    run in two launches.  jobs: tuples (fcw, pm, x, y, ox, oy, n, phase0, acc)
+    or dicts with those keys; fcw, x, y, ox, oy are int32 tensors or device
+    addresses, pm one more or None, acc a one-word device tensor or None; n
+    None: fcw.numel().  The plan must stay open as long as the bank."""
+
+    def __init__(self, plan, jobs):
+        jobs = [tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
+        arr = (_CFmMixJob * max(1, len(jobs)))()
+        for k, (fcw, pm, x, y, ox, oy, n, phase0, acc) in enumerate(jobs):
+            arr[k].d_fcw = _ptr(fcw)
+            arr[k].d_pm = _ptr(pm)
+            arr[k].d_xval = _ptr(x)
+            arr[k].d_yval = _ptr(y)
+            arr[k].d_oxval = _ptr(ox)
+            arr[k].d_oyval = _ptr(oy)
+            arr[k].d_acc = _ptr(acc)
+            arr[k].n = fcw.numel() if n is None else n
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+        h = C.c_void_p()
+        _check(lib().cordic_mixbank_create(getattr(plan, "_h", plan), len(jobs),
+                                           arr, C.byref(h)),
+               "cordic_mixbank_create")
+        self._h = h
+
+    def info(self):
+        a, b = C.c_uint64(), C.c_uint32()
+        c, d = C.c_int32(), C.c_int32()
+        _check(lib().cordic_mixbank_info(self._h, C.byref(a), C.byref(b),
+                                         C.byref(c), C.byref(d)),
+               "cordic_mixbank_info")
+        return dict(samples=a.value, spans=b.value, fused=c.value,
+                    tile=d.value)
+
+    def run(self, stream=None):
+        _check(lib().cordic_mixbank_run(self._h, _stream(stream)),
+               "cordic_mixbank_run")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cordic_mixbank_destroy(self._h)
             self._h = None
 
     def __del__(self):

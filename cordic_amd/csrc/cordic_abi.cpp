@@ -1,8 +1,9 @@
 // cordic_abi.cpp -- the extern "C" surface declared in include/cordic_amd.h:
-// plans, job sets, the int16 calls, the config and stateless wrappers.  (Table,
-// quadratic and bank handles: cordic_abi_table.cpp; the clocked views:
-// cordic_abi_clocked.cpp.)  Thin by design: argument checks, then the host
-// layer (cordic_config.cpp) or the device launchers (cordic_kernels.hip).
+// plans, job sets, FM mixer banks, the int16 calls, the config and stateless
+// wrappers.  (Table, quadratic and oscillator-bank handles:
+// cordic_abi_table.cpp; the clocked views: cordic_abi_clocked.cpp.)  Thin by
+// design: argument checks, then the host layer (cordic_config.cpp) or the
+// device launchers (cordic_kernels.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
@@ -14,6 +15,7 @@
 #include "cordic_amd.h"
 #include "cordic_devmem.h"
 #include "cordic_fm_mix.h"
+#include "cordic_fm_mix_bank.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_queue_ring.h"
@@ -191,6 +193,143 @@ int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
 			stream))
 		return rc;
 	return cordic_plan_p2r(plan, n, d_xval, d_yval, ph, d_oxval, d_oyval, stream);
+}
+
+// ---- FM mixer banks: many of those jobs in two launches
+// (cordic_fm_mix_bank.h)
+struct cordic_mixbank {
+	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
+	int	device = -1;
+	bool	fused = false;
+	uint32_t passes = 0;
+	int	cus = 0;
+	uint64_t samples = 0;
+	// fused: the span table and the workspace, [start words | partials]
+	MixSpan	*d_spans = nullptr;
+	uint32_t *d_words = nullptr;
+	uint32_t nspans = 0, nstarts = 0;
+	// one by one: the non-empty jobs and the workspace of the longest
+	std::vector<cordic_fmmix_job> jobs;
+	void	*d_work = nullptr;
+};
+
+int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
+{
+	if (!bank || (njobs && !jobs))
+		return CORDIC_ERR_ARGS;
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	if (njobs >= ((size_t)1 << 28) || !fmxb_jobs_valid(njobs, jobs))
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	// blocking uploads below: not while the legacy stream is being captured
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	const hipError_t ce = hipStreamIsCapturing(nullptr, &cs);
+	(void)hipGetLastError();
+	if (ce == hipErrorStreamCaptureImplicit
+			|| (ce == hipSuccess && cs != hipStreamCaptureStatusNone))
+		return CORDIC_ERR_UNSUPPORTED;
+
+	uint64_t samples = 0, passes = 0;
+	size_t longest = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		samples += jobs[k].n;
+		passes += fmxb_passes_of(jobs[k].n);
+		if (jobs[k].n > longest)
+			longest = (size_t)jobs[k].n;
+	}
+	cordic_mixbank *b = new (std::nothrow) cordic_mixbank;
+	if (!b)
+		return CORDIC_ERR_NOMEM;
+	b->plan = plan;
+	b->samples = samples;
+	b->fused = fm_mix_fused(plan);
+	if (hipGetDevice(&b->device) != hipSuccess) {
+		(void)hipGetLastError();
+		b->device = -1;
+	}
+	if (!b->fused) {
+		for (size_t k = 0; k < njobs; k++)
+			if (jobs[k].n)
+				b->jobs.push_back(jobs[k]);
+		if (!dev_zalloc(&b->d_work, fmx_work_bytes(false, longest))) {
+			cordic_mixbank_destroy(b);
+			return CORDIC_ERR_DEVICE;
+		}
+		*bank = b;
+		return CORDIC_OK;
+	}
+	b->cus = jobs_cus_now();
+	if (b->cus <= 0) {
+		(void)hipGetLastError();
+		b->cus = 256;
+	}
+	b->passes = fmxb_forced_passes(std::getenv("CORDIC_FMXB_PASSES"),
+			fmxb_passes(passes, b->cus));
+	const uint32_t cap = fmxb_forced_cap(std::getenv("CORDIC_FMXB_MAX_SPANS"));
+	if (fmxb_count_spans(njobs, jobs, b->passes, cap) > 0xffffffffull) {
+		delete b;
+		return CORDIC_ERR_ARGS;
+	}
+	std::vector<MixSpan> spans;
+	fmxb_cut(njobs, jobs, b->passes, cap, &spans, &b->nstarts);
+	b->nspans = (uint32_t)spans.size();
+	if (!dev_upload(spans.data(), spans.size() * sizeof(MixSpan), &b->d_spans)
+			|| !dev_zalloc(&b->d_words,
+				((size_t)b->nstarts + b->nspans) * sizeof(uint32_t))) {
+		cordic_mixbank_destroy(b);
+		return CORDIC_ERR_DEVICE;
+	}
+	*bank = b;
+	return CORDIC_OK;
+}
+
+void cordic_mixbank_destroy(cordic_mixbank *bank)
+{
+	if (!bank)
+		return;
+	dev_free(bank->d_spans, bank->d_words, bank->d_work);
+	delete bank;
+}
+
+int cordic_mixbank_info(const cordic_mixbank *bank, uint64_t *samples,
+		uint32_t *spans, int32_t *fused, int32_t *tile)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	if (samples) *samples = bank->samples;
+	if (spans) *spans = bank->nspans;
+	if (fused) *fused = bank->fused ? 1 : 0;
+	if (tile) *tile = bank->fused ? (int32_t)(bank->passes * kFmxbPass) : 0;
+	return CORDIC_OK;
+}
+
+int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();
+	int dev = -1;
+	if (hipGetDevice(&dev) != hipSuccess) {
+		(void)hipGetLastError();
+		return CORDIC_ERR_DEVICE;
+	}
+	// (the tables hold device addresses)
+	if (dev != bank->device)
+		return CORDIC_ERR_ARGS;
+	const cordic_plan *plan = bank->plan;
+	if (!bank->fused) {
+		for (const cordic_fmmix_job &jb : bank->jobs)
+			if (int rc = cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm,
+					jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval,
+					jb.d_oyval, bank->d_work, stream))
+				return rc;
+		return CORDIC_OK;
+	}
+	return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_spans,
+		bank->nspans, bank->d_words, bank->d_words + bank->nstarts, bank->cus,
+		stream);
 }
 
 int cordic_plan_queue_info(const cordic_plan *plan, cordic_queue_info *info)

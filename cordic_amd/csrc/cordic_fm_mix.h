@@ -6,7 +6,9 @@
 //   (ox_i, oy_i) = cordic_p2r(x_i, y_i, p_i).
 // The launcher and the host checks for cordic_abi.cpp, where the plan and with
 // it the three entry points live; the fallback (cordic_phase_accumulate into
-// the workspace, then cordic_plan_p2r) is put together there.
+// the workspace, then cordic_plan_p2r) is put together there.  Behind them, for
+// hipcc only, the device functions that the kernel of this call and the kernel
+// of the FM mixer banks (cordic_fm_mix_bank.hip) share.
 //
 // Neither unit holds a kernel of the DESIGN section 4.4 sweep (no swept
 // workload has per-sample tuning words), so tools/build_stamp.py does not hash
@@ -63,4 +65,403 @@ int	launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
 
 } // namespace cordic_amd
+
+#ifdef __HIPCC__
+// ---- device side: what fm_mix_xydir (cordic_fm_mix.hip) and the bank's
+// fm_mixbank_xydir (cordic_fm_mix_bank.hip) are both made of -- the staging of
+// the direction tables, the per-vector body of the rotator, the wave scan and
+// the pass loop over a contiguous run of samples.
+#include "cordic_xydir.h"
+
+namespace cordic_amd {
+namespace fmx {
+
+using namespace dev;
+
+typedef const __attribute__((address_space(3))) u32x4 lds_entry;
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(3))) u32x2 lds_bucket;
+
+// One vector through the rotator: the per-vector body of rotator_xydir's sweep
+// (cordic_xydir.h:188-194 and 208-355) restated, because the sweep reads the
+// phases it rotates by and stores what it computes.  Built from the same
+// pieces in the same order; pb is the biased, left-justified phase of
+// :204-205, rx / ry are the words the sweep would store to ox[g], oy[g]; ljc,
+// maskv, bk_base and full_ports are the kernel's constants of :93-94 and
+// :149-158.
+template <int LJ, int NLIVE>
+__device__ __forceinline__ void xydir_vector(const CoreParams &kp, const DirArgs &da,
+		const LjRegs &ljc, const uint32_t (&maskv)[kDxMaxLevels],
+		const uint32_t (&bk_base)[kDxMaxLevels], const bool full_ports, i32x4 tx,
+		i32x4 ty, const uint32_t (&pb)[kVec], i32x4 &rx, i32x4 &ry)
+{
+	constexpr int kN = dx_levels(NLIVE);
+	if (!full_ports) {		// :188-194, the ports
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			tx[v] = sext32(tx[v], kp.iw);
+			ty[v] = sext32(ty[v], kp.iw);
+		}
+	}
+	int64_t x[kVec], y[kVec];
+	uint32_t u[kVec];
+	u32x4 m[kVec];
+#pragma unroll
+	for (int v = 0; v < kVec; v++)		// :211-215, the fold's row
+		m[v] = *(lds_entry *)(uintptr_t)((pb[v] >> 25) & 0x70u);
+#pragma unroll
+	for (int v = 0; v < kVec; v++) {	// :216-225, fold and stage 1
+		int64_t fx = op_mul(ty[v], (int32_t)m[v][2]);	// -B * i_y
+		op_mad(fx, tx[v], (int32_t)m[v][0]);		// + A * i_x
+		int64_t fy = op_mul(ty[v], (int32_t)m[v][0]);	//  A * i_y
+		op_mad(fy, tx[v], (int32_t)m[v][1]);		// + B * i_x
+		x[v] = (int64_t)((uint64_t)fx << LJ);
+		y[v] = (int64_t)((uint64_t)fy << LJ);
+		u[v] = (pb[v] & 0x3fffffffu) + m[v][3];
+	}
+
+	auto group = [&](auto G_) {		// :227-316, a group of looked-up stages
+		constexpr int G = decltype(G_)::value;
+		constexpr int T = dx_size(NLIVE, G);
+		constexpr int K0 = dx_first(NLIVE, G);		// stages done
+		constexpr bool more = (G + 1 < kN) || dx_rest(NLIVE) > 0;
+		const uint32_t sh3 = (uint32_t)da.dx.lv[G].shift - 3u;
+		u32x2 b2[kVec];
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			uint32_t a;
+			asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a)
+				: "v"(u[v] >> sh3), "v"(maskv[G]), "s"(bk_base[G]));
+			b2[v] = *(lds_bucket *)(uintptr_t)a;
+		}
+		constexpr int W = 2 * T + (more ? 1 : 0);	// dwords used
+		constexpr int kStride = dt_entry_dwords(T) * 4;
+		static_assert(dt_entry_dwords(T) >= 2 * T + 1, "entry stride");
+		uint32_t ea[kVec];
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			const uint32_t cc = (b2[v][0] - u[v]) >> 31;	// u >= bound
+			if constexpr ((kStride & (kStride - 1)) == 0)
+				asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(ea[v])
+					: "v"(cc), "n"(__builtin_ctz(kStride)), "v"(b2[v][1]));
+			else if constexpr (kStride <= 64)
+				asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(ea[v])
+					: "v"(cc), "n"(kStride), "v"(b2[v][1]));
+			else
+				asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(ea[v])
+					: "v"(cc), "s"(kStride), "v"(b2[v][1]));
+		}
+		uint32_t en[kVec][12];
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+#pragma unroll
+			for (int at = 0; at < W; at += 4) {
+				if (W - at >= 4) {
+					const u32x4 t4 = *(lds_entry *)(uintptr_t)(ea[v] + 4u * at);
+					en[v][at] = t4[0]; en[v][at + 1] = t4[1];
+					en[v][at + 2] = t4[2]; en[v][at + 3] = t4[3];
+				} else if (W - at == 3) {
+					// (ds_read_b96, as the sweep reads them)
+					typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+					const u32x3 t4 = *(const __attribute__((address_space(3)))
+						u32x3 *)(uintptr_t)(ea[v] + 4u * at);
+					en[v][at] = t4[0]; en[v][at + 1] = t4[1];
+					en[v][at + 2] = t4[2];
+				} else if (W - at == 2) {
+					const u32x2 t2 = *(lds_bucket *)(uintptr_t)(ea[v] + 4u * at);
+					en[v][at] = t2[0]; en[v][at + 1] = t2[1];
+				} else {
+					en[v][at] = *(const __attribute__((address_space(3)))
+						uint32_t *)(uintptr_t)(ea[v] + 4u * at);
+				}
+			}
+		}
+		auto stage = [&](auto J_) {
+			constexpr int J = decltype(J_)::value;
+			if constexpr (J < T) {
+				constexpr int K = K0 + J + 1;	// this stage's shift
+#pragma unroll
+				for (int v = 0; v < kVec; v++) {
+					const int32_t ns_ = (int32_t)en[v][2 * J];
+					const int32_t s_ = (int32_t)en[v][2 * J + 1];
+					if constexpr (K < LjConst<LJ>::first)
+						rot_stage_lj_early_dir<LJ, K>(x[v], y[v], ns_, s_);
+					else
+						rot_stage_lj_dir<LJ, K>(x[v], y[v], ns_, s_);
+				}
+			}
+		};
+		stage(std::integral_constant<int, 0>{});
+		stage(std::integral_constant<int, 1>{});
+		stage(std::integral_constant<int, 2>{});
+		stage(std::integral_constant<int, 3>{});
+		stage(std::integral_constant<int, 4>{});
+		if constexpr (more) {
+#pragma unroll
+			for (int v = 0; v < kVec; v++)
+				u[v] -= en[v][2 * T];
+		}
+	};
+	if constexpr (kN > 0) group(std::integral_constant<int, 0>{});
+	if constexpr (kN > 1) group(std::integral_constant<int, 1>{});
+	if constexpr (kN > 2) group(std::integral_constant<int, 2>{});
+	if constexpr (kN > 3) group(std::integral_constant<int, 3>{});
+	if constexpr (kN > 4) group(std::integral_constant<int, 4>{});
+	constexpr int kRest = dx_rest(NLIVE);
+	if constexpr (kRest > 0) {		// :322-333, the residual stages
+		int64_t p[kVec];
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			const int32_t r = (int32_t)(u[v] - da.dx.bias_last);
+			p[v] = (int64_t)(((uint64_t)(uint32_t)(r >> 1) << 32)
+					| ((uint32_t)r << 31));
+		}
+		RotChainLJ<LJ, NLIVE, NLIVE - kRest, false>::run(x, y, p, kp, ljc);
+	}
+
+	if (kp.r_lj == 32) {			// :335-355, rounding
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			rx[v] = round_to_ow_lj32<LJ>(x[v], kp);
+			ry[v] = round_to_ow_lj32<LJ>(y[v], kp);
+		}
+	} else if (kp.r_lj > 32 && kp.r < 31) {
+		const uint32_t sh = (uint32_t)kp.r_lj - 32u;
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			rx[v] = round_to_ow_lj_hi<LJ>(x[v], kp, sh);
+			ry[v] = round_to_ow_lj_hi<LJ>(y[v], kp, sh);
+		}
+	} else {
+#pragma unroll
+		for (int v = 0; v < kVec; v++) {
+			rx[v] = round_to_ow_lj<LJ>(x[v], kp);
+			ry[v] = round_to_ow_lj<LJ>(y[v], kp);
+		}
+	}
+}
+
+// v + the v of every lane in front, over the wave's 64 lanes: four shifts
+// inside the rows of 16, then row 0's and 2's last lane to the row behind, then
+// lane 31 to the upper half.  A lane without a source adds 0.
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
+{
+#define FMX_DPP(ctrl, rows) \
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xf, false)
+	FMX_DPP(0x111, 0xf);	// row_shr:1
+	FMX_DPP(0x112, 0xf);	// row_shr:2
+	FMX_DPP(0x114, 0xf);	// row_shr:4
+	FMX_DPP(0x118, 0xf);	// row_shr:8
+	FMX_DPP(0x142, 0xa);	// row_bcast:15 into rows 1 and 3
+	FMX_DPP(0x143, 0xc);	// row_bcast:31 into rows 2 and 3
+#undef FMX_DPP
+	return v;
+}
+
+// The block's prologue: the fold's rows and the groups' tables into LDS
+// (cordic_xydir.h:97-139).  The caller's barrier follows.
+template <int LJ, int NLIVE>
+__device__ __forceinline__ void stage_tables(const CoreParams &kp, const DirArgs &da,
+		uint32_t *lds, const uint32_t (&bk_base)[kDxMaxLevels],
+		const uint32_t (&lf_base)[kDxMaxLevels], const unsigned tid)
+{
+	constexpr int kN = dx_levels(NLIVE);
+	if (tid < 8) {
+		const int q = tid >> 1;
+		const int32_t dir = (tid & 1) ? 1 : -1;	// phase >= 0 : < 0
+		const int32_t k = (int32_t)(1u << (kp.in_shl & 31));
+		const int32_t cs = (q == 0) ? k : (q == 2) ? -k : 0;
+		const int32_t sn = (q == 1) ? k : (q == 3) ? -k : 0;
+		int32_t *row = reinterpret_cast<int32_t *>(lds) + tid * 4;
+		const int32_t ra = cs - dir * (sn / 2), rb = sn + dir * (cs / 2);
+		row[0] = ra;
+		row[1] = rb;
+		row[2] = -rb;
+		row[3] = (int32_t)(da.dx.bias0 - 0x20000000u
+				- (uint32_t)(dir * (int32_t)kp.angle[0]));
+	}
+#pragma unroll
+	for (int g = 0; g < kN; g++) {
+		const DtLevel lv = da.dx.lv[g];
+		const uint32_t *src = da.table + lv.word;
+		uint32_t *bk = lds + bk_base[g] / 4u;
+		const uint32_t stride = (uint32_t)dt_entry_dwords(lv.t) * 4u;
+		for (int i = tid; i < lv.nb * 2; i += kBlock) {
+			const uint32_t w = src[i];
+			bk[i] = (i & 1) ? lf_base[g] + w * stride : w;
+		}
+		const uint32_t *lsrc = src + (size_t)lv.nb * 2;
+		uint32_t *lf = lds + lf_base[g] / 4u;
+		for (int e = tid; e < lv.nl; e += kBlock) {
+			const uint32_t pat = lsrc[2 * e];
+			uint32_t *d = lf + (size_t)e * dt_entry_dwords(lv.t);
+			for (int jj = 0; jj < lv.t; jj++) {
+				// bit set: residual >= 0 at that stage, s = +1
+				const bool pos = (pat >> (lv.t - 1 - jj)) & 1u;
+				const uint32_t plus = LjConst<LJ>::bit;
+				const uint32_t minus = LjConst<LJ>::mask | LjConst<LJ>::bit;
+				d[2 * jj + 0] = pos ? minus : plus;	// -s 2^LJ (x)
+				d[2 * jj + 1] = pos ? plus : minus;	//  s 2^LJ (y)
+			}
+			d[2 * lv.t] = lsrc[2 * e + 1];		// u_next = u - this
+		}
+	}
+}
+
+// the sum of work[0 .. count) over the block, in four shares: ex[8 + wave].
+// The caller's barrier follows; ex[8] + .. + ex[11] is the sum.
+__device__ __forceinline__ void front_sum(const uint32_t *work, unsigned count,
+		uint32_t *ex, const unsigned tid, const unsigned wave)
+{
+	uint32_t s = 0;
+	for (unsigned j = tid; j < count; j += kBlock)
+		s += work[j];
+#pragma unroll
+	for (int d = 32; d; d >>= 1)
+		s += __shfl_xor(s, d);
+	if ((tid & 63u) == 0)
+		ex[8 + wave] = s;
+}
+
+// the rotator's constants that live in registers for the whole kernel
+struct RotRegs {
+	LjRegs	ljc;
+	uint32_t maskv[kDxMaxLevels];
+	uint32_t k45;
+	bool	full_ports;	// wave-uniform: no sign extension
+};
+
+template <int LJ, int NLIVE>
+__device__ __forceinline__ RotRegs rot_regs(const CoreParams &kp, const DirArgs &da)
+{
+	RotRegs r{};
+	r.ljc.mask = vgpr_const(LjConst<LJ>::mask);
+	r.ljc.bit = vgpr_const(LjConst<LJ>::bit);
+	r.ljc.maskbit = vgpr_const(LjConst<LJ>::mask | LjConst<LJ>::bit);
+#pragma unroll
+	for (int g = 0; g < dx_levels(NLIVE); g++)
+		r.maskv[g] = vgpr_const(((uint32_t)da.dx.lv[g].nb - 1u) << 3);
+	r.k45 = vgpr_const(0x20000000u);
+	r.full_ports = kp.iw == 32;
+	return r;
+}
+
+// The pass loop: samples [lo, hi) of the six arrays, 1024 per pass, 4 per lane.
+// carry: in, the phase of sample lo without its pm; out, that of sample hi.
+// par: the parity of the exchange words ex[0 .. 8), which are double-buffered
+// by pass, so that a pass has ONE barrier; it runs on from call to call.
+// pm may be NULL (wave-uniform).  Nothing at or behind hi is read or written.
+template <int LJ, int NLIVE>
+__device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &da,
+		const RotRegs &rr, const uint32_t (&bk_base)[kDxMaxLevels],
+		const uint32_t *fcw, const uint32_t *pm, const int32_t *ax,
+		const int32_t *ay, int32_t *aox, int32_t *aoy, const size_t lo,
+		const size_t hi, uint32_t &carry, unsigned &par, uint32_t *ex,
+		const unsigned tid, const unsigned wave)
+{
+	// this lane's 4 samples of the pass at t0; nothing at or behind hi is read,
+	// and a tuning word that is not there counts 0
+	auto load_pass = [&](size_t t0, u32x4 &f, u32x4 &m, i32x4 &x, i32x4 &y) {
+		const size_t i = t0 + (size_t)kVec * tid;
+		f = u32x4{};
+		m = u32x4{};
+		x = i32x4{};
+		y = i32x4{};
+		if (i + kVec <= hi) {
+			f = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(fcw + i));
+			if (pm)	// (wave-uniform)
+				m = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(pm + i));
+			x = CORDIC_LOAD_IN(reinterpret_cast<const i32x4g *>(ax + i));
+			y = CORDIC_LOAD_IN(reinterpret_cast<const i32x4g *>(ay + i));
+		} else if (i < hi) {	// the last, partial vector: one lane of the job
+#pragma unroll
+			for (int v = 0; v < kVec; v++) {
+				if (i + v < hi) {
+					f[v] = fcw[i + v];
+					if (pm)
+						m[v] = pm[i + v];
+					x[v] = ax[i + v];
+					y[v] = ay[i + v];
+				}
+			}
+		}
+	};
+
+	u32x4 nf, nm;
+	i32x4 nx, ny;
+	load_pass(lo, nf, nm, nx, ny);
+	for (size_t t0 = lo; t0 < hi; t0 += kFmxPass) {
+		const u32x4 f = nf, m = nm;
+		const i32x4 tx = nx, ty = ny;
+		// the next pass's words are on their way while this one is rotated
+		if (t0 + kFmxPass < hi)
+			load_pass(t0 + kFmxPass, nf, nm, nx, ny);
+
+		// inclusive sums: in the lane, then over the wave's lanes
+		const uint32_t s0 = f[0], s1 = s0 + f[1], s2 = s1 + f[2], s3 = s2 + f[3];
+		const uint32_t incl = wave_scan(s3);
+		if ((tid & 63u) == 63u)
+			ex[par * 4 + wave] = incl;
+		__syncthreads();
+		const u32x4 w = *reinterpret_cast<const u32x4 *>(ex + par * 4);
+		par ^= 1;
+		// the waves in front of this one, and the pass's total
+		const uint32_t front = (wave > 0 ? w[0] : 0u) + (wave > 1 ? w[1] : 0u)
+			+ (wave > 2 ? w[2] : 0u);
+		const uint32_t excl = carry + front + incl - s3;
+		carry += w[0] + w[1] + w[2] + w[3];
+
+		const uint32_t ph[kVec] = {excl + m[0], excl + s0 + m[1], excl + s1 + m[2],
+			excl + s2 + m[3]};
+		uint32_t pb[kVec];
+#pragma unroll
+		for (int v = 0; v < kVec; v++)	// cordic_xydir.h:202-205
+			asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(pb[v])
+				: "v"(ph[v]), "s"(kp.pw_shl), "v"(rr.k45));
+
+		i32x4 rx, ry;
+		xydir_vector<LJ, NLIVE>(kp, da, rr.ljc, rr.maskv, bk_base, rr.full_ports, tx,
+			ty, pb, rx, ry);
+
+		const size_t i = t0 + (size_t)kVec * tid;
+		if (i + kVec <= hi) {
+			CORDIC_STORE_OUT(true, reinterpret_cast<i32x4g *>(aox + i), rx);
+			CORDIC_STORE_OUT(true, reinterpret_cast<i32x4g *>(aoy + i), ry);
+		} else if (i < hi) {
+#pragma unroll
+			for (int v = 0; v < kVec; v++) {
+				if (i + v < hi) {
+					aox[i + v] = rx[v];
+					aoy[i + v] = ry[v];
+				}
+			}
+		}
+	}
+}
+
+// ---- host side of both units
+// the tables and the 12 exchange words behind them
+inline size_t lds_bytes(const DxInfo &dx, uint32_t *xw)
+{
+	const uint32_t at = (dx_lds_layout(dx, nullptr, nullptr) + 15u) & ~15u;
+	if (xw)
+		*xw = at;
+	return (size_t)at + 12 * 4;
+}
+
+// resident blocks per CU: 4 waves of a SIMD by the registers (see the heads of
+// the two units), fewer where the tables fill the CU's 160 KiB sooner
+inline size_t blocks_per_cu(size_t lds)
+{
+	const size_t per_cu = (160 * 1024) / lds;
+	return per_cu > kFmxBlocksPerCu ? kFmxBlocksPerCu : per_cu;
+}
+
+// the stage counts the job-set instances of rotator_xydir carry
+// (cordic_jobs_xydir.hip)
+#define FMX_STAGES(X) X(13) X(16) X(19) X(20) X(24) X(27) X(29)
+
+} // namespace fmx
+} // namespace cordic_amd
+#endif // __HIPCC__
 #endif

@@ -1,0 +1,199 @@
+// cordic_fm_mix_bank.h -- FM mixer banks: many cordic_plan_fm_mix jobs of one
+// p2r / sp2r plan in TWO launches (include/cordic_amd.h, "FM mixer banks").  The
+// span descriptors the host cuts at create, the cutter itself -- plain C++ that
+// touches no device, so that a stand-alone program can run it under a
+// sanitizer -- and the launcher of the two kernels that walk the descriptors
+// (cordic_fm_mix_bank.hip).  Host-visible types only; the handle and its four
+// entry points live with the plan, in cordic_abi.cpp.
+//
+// No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
+// does not hash this unit.
+#ifndef CORDIC_FM_MIX_BANK_H
+#define CORDIC_FM_MIX_BANK_H
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+#include "cordic_amd.h"
+
+namespace cordic_amd {
+
+// A run of whole passes (1024 samples, kFmxPass) of ONE job, never across the
+// job's end; only a job's last span may end in a partial pass.
+struct MixSpan {
+	uint64_t fcw, pm;	// addresses at the span's first sample (pm 0: none)
+	uint64_t x, y, ox, oy;
+	uint64_t acc;		// the job's d_acc, or 0
+	uint64_t n;		// samples: >= 1
+	uint32_t start;		// index of the job's start word
+	uint32_t part0;		// index of the job's first partial sum
+	uint32_t idx;		// this span's index within its job
+	uint32_t flags;		// kMixSpanFirst | kMixSpanLast
+	uint32_t phase0;	// the job's (the first span latches the start)
+	uint32_t pad;
+};				// 88 bytes
+constexpr uint32_t kMixSpanFirst = 1, kMixSpanLast = 2;
+
+constexpr uint64_t kFmxbPass = 1024;		// = kFmxPass
+constexpr uint32_t kFmxbMaxSpans = 4096;	// per job; = kFmxMaxBlocks
+constexpr uint32_t kFmxbMaxPasses = 1u << 20;	// a base span's: 2^30 samples
+constexpr int	   kFmxbBlocksPerCu = 4;	// = kFmxBlocksPerCu
+
+inline uint64_t fmxb_passes_of(uint64_t n)
+{
+	return n / kFmxbPass + (n % kFmxbPass ? 1 : 0);
+}
+
+// P, the passes of a base span, for a bank of `total_passes` on a device of
+// `cus` CUs: the rule of the data-fed job sets and of fmd_bank_passes -- the
+// longest span that still gives every resident block (4 per CU) four of them
+// -- in the steps 1, 2, 4, 8, 16, ...
+inline uint32_t fmxb_passes(uint64_t total_passes, int cus)
+{
+	const uint64_t per = total_passes
+		/ ((uint64_t)(cus > 0 ? cus : 256) * kFmxbBlocksPerCu * 4u);
+	uint32_t p = 1;
+	while (p < kFmxbMaxPasses && (uint64_t)p * 2 <= per)
+		p <<= 1;
+	return p;
+}
+
+// CORDIC_FMXB_PASSES / CORDIC_FMXB_MAX_SPANS (read at create): a power of two
+// within 1 .. 2^20 replaces P; a value within 1 .. 4095 lowers the span cap.
+inline uint32_t fmxb_forced_passes(const char *e, uint32_t p)
+{
+	if (!e)
+		return p;
+	const long v = std::strtol(e, nullptr, 10);
+	return (v >= 1 && v <= (long)kFmxbMaxPasses && !(v & (v - 1))) ? (uint32_t)v : p;
+}
+inline uint32_t fmxb_forced_cap(const char *e)
+{
+	if (!e)
+		return kFmxbMaxSpans;
+	const long v = std::strtol(e, nullptr, 10);
+	return (v >= 1 && v < (long)kFmxbMaxSpans) ? (uint32_t)v : kFmxbMaxSpans;
+}
+
+// passes per span of ONE job of n samples: P, doubled until the job has at
+// most `cap` spans -- the single call's bound on what a span sums in front of
+// itself
+inline uint64_t fmxb_job_passes(uint64_t n, uint32_t passes, uint32_t cap)
+{
+	const uint64_t np = fmxb_passes_of(n);
+	uint64_t pj = passes;
+	while ((np + pj - 1) / pj > cap)
+		pj *= 2;
+	return pj;
+}
+
+// The argument checks of cordic_mixbank_create that need no device: every job
+// with n > 0 has non-NULL d_fcw, d_xval, d_yval, d_oxval, d_oyval, all seven
+// pointers on the 4-byte grid, reserved == 0 and a length within SIZE_MAX >> 4;
+// no output range (d_oxval, d_oyval, the word at d_acc) overlaps another output
+// range or any input range of the bank.  Found by sorting the ranges by
+// address, as fmd_bank_jobs_valid does: a range that begins inside an earlier
+// one is an overlap, which is refused unless both are inputs.
+inline bool fmxb_jobs_valid(size_t njobs, const cordic_fmmix_job *jobs)
+{
+	struct Range { uint64_t lo, hi; bool out; };
+	std::vector<Range> r;
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_fmmix_job &jb = jobs[k];
+		if (jb.n == 0)
+			continue;
+		// inputs, then outputs; pm is optional
+		const uintptr_t p[6] = {(uintptr_t)jb.d_fcw, (uintptr_t)jb.d_xval,
+			(uintptr_t)jb.d_yval, (uintptr_t)jb.d_pm, (uintptr_t)jb.d_oxval,
+			(uintptr_t)jb.d_oyval};
+		const uintptr_t a = (uintptr_t)jb.d_acc;
+		if (!p[0] || !p[1] || !p[2] || !p[4] || !p[5]
+				|| ((p[0] | p[1] | p[2] | p[3] | p[4] | p[5] | a) & 3u)
+				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
+			return false;
+		const uint64_t bytes = jb.n * 4;
+		for (int i = 0; i < 6; i++) {
+			if (!p[i])
+				continue;
+			if (bytes > ~(uint64_t)0 - p[i])
+				return false;
+			r.push_back(Range{p[i], p[i] + bytes, i >= 4});
+		}
+		if (a)
+			r.push_back(Range{a, (uint64_t)a + 4, true});
+	}
+	std::sort(r.begin(), r.end(),
+		[](const Range &a, const Range &b) { return a.lo < b.lo; });
+	uint64_t any_end = 0, out_end = 0;	// ends of the ranges in front
+	for (const Range &a : r) {
+		if (a.lo < (a.out ? any_end : out_end))
+			return false;
+		any_end = std::max(any_end, a.hi);
+		if (a.out)
+			out_end = std::max(out_end, a.hi);
+	}
+	return true;
+}
+
+// spans the jobs cut into (saturating at 2^63)
+inline uint64_t fmxb_count_spans(size_t njobs, const cordic_fmmix_job *jobs,
+		uint32_t passes, uint32_t cap)
+{
+	uint64_t t = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		if (!jobs[k].n)
+			continue;
+		const uint64_t pj = fmxb_job_passes(jobs[k].n, passes, cap);
+		t += (fmxb_passes_of(jobs[k].n) + pj - 1) / pj;
+		if (t >> 63)
+			break;
+	}
+	return t;
+}
+
+// Cuts valid jobs (fmxb_jobs_valid; fewer than 2^32 spans) into spans, in the
+// jobs' order.  Start words are numbered by non-empty job, partial sums by
+// span: the workspace of the run has *njobs_live + spans->size() words.
+inline void fmxb_cut(size_t njobs, const cordic_fmmix_job *jobs, uint32_t passes,
+		uint32_t cap, std::vector<MixSpan> *spans, uint32_t *njobs_live)
+{
+	uint32_t live = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		const cordic_fmmix_job &jb = jobs[k];
+		if (jb.n == 0)
+			continue;
+		const uint64_t len = fmxb_job_passes(jb.n, passes, cap) * kFmxbPass;
+		const uint32_t part0 = (uint32_t)spans->size();
+		uint32_t idx = 0;
+		for (uint64_t s0 = 0; s0 < jb.n; s0 += len, idx++) {
+			const uint64_t cnt = jb.n - s0 < len ? jb.n - s0 : len;
+			const uint64_t at = s0 * 4;
+			spans->push_back(MixSpan{(uintptr_t)jb.d_fcw + at,
+				jb.d_pm ? (uintptr_t)jb.d_pm + at : 0,
+				(uintptr_t)jb.d_xval + at, (uintptr_t)jb.d_yval + at,
+				(uintptr_t)jb.d_oxval + at, (uintptr_t)jb.d_oyval + at,
+				(uintptr_t)jb.d_acc, cnt, live, part0, idx,
+				(s0 ? 0u : kMixSpanFirst)
+					| (s0 + cnt == jb.n ? kMixSpanLast : 0u),
+				jb.phase0, 0u});
+		}
+		live++;
+	}
+	if (njobs_live)
+		*njobs_live = live;
+}
+
+// The two launches, for a plan of which fmx_is_fused (cordic_fm_mix.h) is true.
+// d_start / d_part: the bank's workspace (one word per non-empty job, one per
+// span).  cus: the device's, at create.  An empty table launches nothing.
+// CORDIC_OK or CORDIC_ERR_DEVICE.
+struct DxInfo;		// (cordic_internal.h)
+int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
+		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
+		uint32_t *d_part, int cus, void *stream);
+
+} // namespace cordic_amd
+#endif

@@ -1,0 +1,231 @@
+// cordic_fm_mix_bank.hip -- FM mixer banks (cordic_mixbank_create, _destroy,
+// _info, _run; include/cordic_amd.h): many cordic_plan_fm_mix jobs of one plan,
+// each with its own arrays, length, phase0 and d_acc, in TWO launches.  The
+// single call's reduce-then-scan (cordic_fm_mix.hip) reading span descriptors
+// (MixSpan, cordic_fm_mix_bank.h): the host has cut every job into spans of
+// whole 1024-sample passes, never across a job's end, a job into at most 4096.
+//   1. fm_mixbank_reduce: block b sums the tuning words of spans b, b + grid,
+//      ... into one workspace word per span (a span of one pass is one pass of
+//      one block: 256 lanes, one 16-byte load each); a job's first span latches
+//      phase0 + *d_acc into the job's start word.
+//   2. fm_mixbank_xydir<LJ, NLIVE>: at most the resident blocks.  A block
+//      stages the plan's direction tables ONCE, then walks spans b, b + grid,
+//      ... in the table's order, which is the jobs' own.  Per span the
+//      descriptor arrives as scalar loads; the block adds the job's partials in
+//      front of the span to the job's start word (front_sum, as the single
+//      call's prologue; skipped for a job's first span) and runs pass_loop
+//      (cordic_fm_mix.h), the loop fm_mix_xydir runs as well: 16-byte accesses
+//      at any 4-byte alignment, lane sums / DPP wave scan / four LDS words with
+//      ONE barrier per pass, the carry in a register, the next pass's loads in
+//      flight, the n % 4 trailing samples by one lane.  The job's last span
+//      writes *d_acc.
+// Every *d_acc is read in launch 1 only and written in launch 2 only, which
+// follows in stream order; the workspace is written in launch 1 only.  No block
+// waits for another, nothing is allocated, copied or synchronised at run, no
+// tile queue.  Nothing outside [0, n) of an output is written: a span's hi is
+// its own sample count and pass_loop touches nothing at or behind it.
+//
+// LDS words across spans.  The parity `par` of the exchange words ex[0 .. 8)
+// is CARRIED ON from span to span, so a block's passes form one sequence,
+// whatever jobs they belong to, and the single call's argument holds as it
+// stands: the four words written in pass i are read behind barrier i and in
+// front of barrier i + 1, and written again in pass i + 2, which a wave reaches
+// only through barrier i + 1 -- when every wave has its reads of pass i behind
+// it.  (A barrier between spans would do too, but a job's first span has none
+// to offer: it skips the prologue.)  The shares ex[8 .. 12) of a span's
+// prologue are written in front of the prologue's barrier and read behind it,
+// in front of the span's first pass barrier; the next prologue writes them only
+// behind that pass barrier (every span has a pass), so no share is overwritten
+// while a slower wave still reads it.  The carry is set anew per span from the
+// job's start word and partials: nothing of the span before survives in it.
+//
+// The base span is P passes, chosen at create -- fmxb_passes: the longest span,
+// in the steps 1, 2, 4, 8, 16, ..., that still gives every resident block four
+// -- or forced by CORDIC_FMXB_PASSES; a job that would have more than 4096 spans
+// (CORDIC_FMXB_MAX_SPANS lowers that; both read at create) gets spans twice,
+// four times, ... as long, that job alone.  Launch 2's grid is min(spans, CUs *
+// resident blocks per CU), capped further by CORDIC_FMXB_MAX_BLOCKS (read at
+// every run).  The bits depend on none of the three.
+//
+// Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
+// .private_segment_fixed_size is 0 for every instance: nothing spills), next to
+// the single call's, before and after pass_loop became a shared function:
+//   live stages                 13   16   19   20   24   27   29
+//   fm_mix_xydir<29, N> before  98  100   98   98  104  108  108
+//   fm_mix_xydir<29, N> after   98  100   98   98  104  108  108
+//   fm_mixbank_xydir<29, N>    114  120  114  114  115  122  122
+//   fm_mix_xydir<30, N> before  92   98   95   95  102  103  103
+//   fm_mix_xydir<30, N> after   92   98   95   95  102  103  103
+//   fm_mixbank_xydir<30, N>    115  117  116  116  115  124  124
+//   fm_mixbank_reduce           42 (32 bytes of static LDS)
+// The single call's counts did not move.  The bank's kernel takes 12 .. 23
+// more: six array addresses, the sample count and the indices arrive per span
+// where the single call has them as kernel arguments, and the lane's element
+// offsets are made from them anew.  Up to 128 registers hold 4 waves per SIMD,
+// the single call's occupancy: no step is crossed, and the grid is sized for 4
+// blocks per CU; LDS (the tables, at most 64 KiB, and 12 words) decides where
+// it admits fewer, exactly as in launch_fm_mix.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "cordic_xydir.h"
+#include "cordic_launch.h"
+#include "cordic_jobs_fused.h"
+#include "cordic_hostargs.h"
+#include "cordic_fm_mix.h"
+#include "cordic_fm_mix_bank.h"
+
+namespace cordic_amd {
+
+static_assert(kFmxbPass == kFmxPass && kFmxbMaxSpans == kFmxMaxBlocks
+	&& (size_t)kFmxbBlocksPerCu == kFmxBlocksPerCu, "the single call's geometry");
+static_assert(sizeof(MixSpan) == 88, "the descriptor is read as scalar words");
+
+namespace fmx {
+
+// launch 1: part[d.part0 + d.idx] = the sum of the span's tuning words;
+// start[d.start] = phase0 + *d_acc for a job's first span.  The two words of
+// wsum are double-buffered by span, as the exchange words of pass_loop are by
+// pass: one barrier per span.
+__global__ __launch_bounds__(kBlock) void fm_mixbank_reduce(
+		const MixSpan *__restrict__ spans, uint32_t nspans,
+		uint32_t *__restrict__ start, uint32_t *__restrict__ part)
+{
+	__shared__ uint32_t wsum[2][kBlock / 64];
+	const unsigned tid = threadIdx.x;
+	unsigned par = 0;
+	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
+		const MixSpan d = spans[t];
+		const uint32_t *f = reinterpret_cast<const uint32_t *>((uintptr_t)d.fcw);
+		const u32x4g *fv = reinterpret_cast<const u32x4g *>(f);
+		const uint64_t nv = d.n / kVec;
+		uint32_t s = 0;
+#pragma unroll 4
+		for (uint64_t g = tid; g < nv; g += kBlock) {
+			const u32x4 q = fv[g];
+			s += q[0] + q[1] + q[2] + q[3];
+		}
+		const uint64_t r = nv * kVec + tid;	// fewer than 4 behind the vectors
+		if (r < d.n)
+			s += f[r];
+#pragma unroll
+		for (int k = 32; k; k >>= 1)
+			s += __shfl_xor(s, k);
+		if ((tid & 63u) == 0)
+			wsum[par][tid >> 6] = s;
+		__syncthreads();
+		if (tid == 0) {
+			part[d.part0 + d.idx] = wsum[par][0] + wsum[par][1] + wsum[par][2]
+				+ wsum[par][3];
+			if (d.flags & kMixSpanFirst) {
+				const uint32_t *acc
+					= reinterpret_cast<const uint32_t *>((uintptr_t)d.acc);
+				start[d.start] = d.phase0 + (acc ? *acc : 0u);
+			}
+		}
+		par ^= 1;
+	}
+}
+
+// launch 2 (see the head of this file)
+template <int LJ, int NLIVE>
+__global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArgs da,
+		const MixSpan *__restrict__ spans, uint32_t nspans,
+		const uint32_t *__restrict__ start, const uint32_t *__restrict__ part,
+		uint32_t xw)
+{
+	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
+	constexpr int kN = dx_levels(NLIVE);
+	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
+	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+	const unsigned tid = threadIdx.x;
+	// (the same in all of a wave's lanes: said so, it stays in a scalar)
+	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
+	dx_lds_layout(da.dx, bk_base, lf_base);
+	stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	uint32_t *ex = lds + xw / 4u;
+	__syncthreads();
+
+	// LDS is addressed by byte offset from 0: no static LDS in this kernel
+	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
+		__builtin_trap();
+
+	const RotRegs rr = rot_regs<LJ, NLIVE>(kp, da);
+	unsigned par = 0;
+	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
+		const MixSpan d = spans[t];
+		// the phase of the span's first sample, without its pm
+		uint32_t carry = start[d.start];
+		if (d.idx) {		// (block-uniform)
+			front_sum(part + d.part0, d.idx, ex, tid, wave);
+			__syncthreads();
+			carry += ex[8] + ex[9] + ex[10] + ex[11];
+		}
+		pass_loop<LJ, NLIVE>(kp, da, rr, bk_base,
+			reinterpret_cast<const uint32_t *>((uintptr_t)d.fcw),
+			reinterpret_cast<const uint32_t *>((uintptr_t)d.pm),
+			reinterpret_cast<const int32_t *>((uintptr_t)d.x),
+			reinterpret_cast<const int32_t *>((uintptr_t)d.y),
+			reinterpret_cast<int32_t *>((uintptr_t)d.ox),
+			reinterpret_cast<int32_t *>((uintptr_t)d.oy), (size_t)0, (size_t)d.n,
+			carry, par, ex, tid, wave);
+		if ((d.flags & kMixSpanLast) && d.acc && tid == 0)
+			*reinterpret_cast<uint32_t *>((uintptr_t)d.acc) = carry;
+	}
+}
+
+template <int LJ>
+static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const MixSpan *spans,
+		uint32_t nspans, const uint32_t *start, const uint32_t *part, uint32_t xw)
+{
+	switch (nlive) {
+#define X(N) case N: \
+	if (da.dx.n != dx_levels(N)) \
+		return false; \
+	hipLaunchKernelGGL((fm_mixbank_xydir<LJ, N>), dim3(grid), dim3(kBlock), lds, st, \
+		kp, da, spans, nspans, start, part, xw); \
+	return true;
+	FMX_STAGES(X)
+#undef X
+	default:
+		return false;
+	}
+}
+
+} // namespace fmx
+
+int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
+		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
+		uint32_t *d_part, int cus, void *stream)
+{
+	using namespace fmx;
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	if (nspans == 0)
+		return CORDIC_OK;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	uint32_t xw = 0;
+	const size_t lds = lds_bytes(dx, &xw);
+	// launch 1 has 8 waves a SIMD (few registers, 32 bytes of LDS)
+	size_t rgrid = (size_t)cus * 8;
+	if (rgrid > nspans)
+		rgrid = nspans;
+	hipLaunchKernelGGL(fm_mixbank_reduce, dim3((unsigned)rgrid), dim3(kBlock), 0, st,
+		d_spans, nspans, d_start, d_part);
+	size_t cap = (size_t)cus * blocks_per_cu(lds);
+	cap = env_block_cap("CORDIC_FMXB_MAX_BLOCKS", cap);
+	const unsigned grid = (unsigned)(nspans < cap ? nspans : cap);
+	const DirArgs da{d_dir, dx};
+	const CoreParams kp = make_params_jobs(cfg);
+	const bool done = cfg.ww == 35
+		? launch_bank_lj<29>(cfg.nlive, grid, lds, st, kp, da, d_spans, nspans,
+			d_start, d_part, xw)
+		: launch_bank_lj<30>(cfg.nlive, grid, lds, st, kp, da, d_spans, nspans,
+			d_start, d_part, xw);
+	return tnco::finish(done);
+}
+
+} // namespace cordic_amd

@@ -1086,9 +1086,9 @@ int	cordic_demodbank_run(const cordic_demodbank *bank, void *stream);
  * d_work off the 16-byte grid, an overlap as above.  What
  * cordic_last_kernel() reports after the call is unspecified.
  *
- * There is no int16 form, no cordic_config-level twin and no job-set kind: the
- * direction tables live in the plan, and the int16 rotators have no
- * looked-up-direction kernel.
+ * There is no int16 form and no cordic_config-level twin: the direction tables
+ * live in the plan, and the int16 rotators have no looked-up-direction kernel.
+ * Many short jobs of one plan go into an FM mixer bank (below).
  */
 size_t	cordic_plan_fm_mix_workspace(const cordic_plan *plan, size_t n);
 int	cordic_plan_fm_mix_info(const cordic_plan *plan, int32_t *fused,
@@ -1098,6 +1098,82 @@ int	cordic_plan_fm_mix(const cordic_plan *plan, size_t n,
 		uint32_t *d_acc,
 		const int32_t *d_xval, const int32_t *d_yval,
 		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
+
+/* FM mixer banks: many per-sample-tuned mixer jobs in two launches.
+ *
+ * What FM demodulation banks are to cordic_fm_demod, for cordic_plan_fm_mix:
+ * the per-channel AFC or Costas LO, Doppler correction or de-chirp of a
+ * channelised receiver.  Hundreds or thousands of SHORT blocks, each with its
+ * own arrays, length, phase0 and d_acc, are described once; one
+ * cordic_mixbank_run then gives, for every job with n > 0, bit for bit what
+ *   cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+ *                      d_oxval, d_oyval, work, stream)
+ * gives -- *d_acc afterwards (all 32 bits, pm not in it), the rule that phase0
+ * is added by every run, and inputs taken modulo IW and PW included.  So a
+ * bank whose jobs have a d_acc and phase0 == 0, run k times on new data in the
+ * same arrays, continues every channel k times with no host work in between,
+ * and a captured run replayed k times continues k times.
+ *
+ * Create is host work with blocking uploads: CORDIC_ERR_UNSUPPORTED while the
+ * legacy stream is being captured.  The bank REFERS to the plan: the plan must
+ * outlive the bank.  CORDIC_ERR_MODE for a plan that is not P2R / SP2R;
+ * CORDIC_ERR_ARGS for a NULL plan or bank, NULL jobs with njobs > 0, 2^28 or
+ * more jobs, 2^32 or more spans, and for a job with n > 0 (a zero-length job's
+ * pointers are not looked at): a NULL d_fcw, d_xval, d_yval, d_oxval or
+ * d_oyval, any pointer off the 4-byte grid (d_pm and d_acc included), reserved
+ * != 0, n beyond SIZE_MAX >> 4.  No output range of the bank -- every job's
+ * d_oxval, d_oyval and the 4 bytes at its d_acc -- may overlap another output
+ * range or any job's input range (CORDIC_ERR_ARGS, found by sorting the
+ * ranges; two jobs sharing a d_acc is such an overlap); inputs may alias each
+ * other.  njobs == 0 or all-empty jobs give a valid bank whose run launches
+ * nothing.  The bank belongs to the device that was current at create:
+ * CORDIC_ERR_ARGS from run on another device.
+ *
+ * The bank owns its device memory, allocated at create: the descriptor tables
+ * and a small workspace.  Run allocates, copies and synchronises nothing.  Two
+ * runs of ONE bank must not be in flight at the same time (the workspace is
+ * the d_work of the single call: not shared by calls that may run at once).
+ *
+ * Two paths, identical bits, chosen at create and told by cordic_mixbank_info:
+ *   fused       the plans for which cordic_plan_fm_mix_info answers 1.  The
+ *               whole bank is exactly TWO kernel launches on `stream`: every
+ *               job is cut into spans of whole 1024-sample passes, never across
+ *               a job's end -- P passes by the bank's size, P = 1, 2, 4, 8, 16,
+ *               ...; a job that would have more than 4096 spans gets longer
+ *               ones -- then a reduction of the tuning words per span, and the
+ *               scan with the rotator behind it walking the spans.  ANY
+ *               4-byte-aligned arrays are served.  No block waits for another,
+ *               no tile queue is taken; legal inside a stream capture.  Every
+ *               *d_acc is read in the first launch only and written in the
+ *               second only.
+ *   one by one  every other plan: run loops cordic_plan_fm_mix over the jobs on
+ *               `stream`, with a workspace the bank allocated at create for its
+ *               longest job; legal inside a capture as well.
+ * Nothing outside [0, n) of any output is written.
+ *
+ * cordic_mixbank_info (any pointer may be NULL): *samples = the samples of all
+ * jobs; *spans = the spans the second launch walks (0 one by one); *fused = 1 /
+ * 0; *tile = the samples of a full span of the bank's base size, P * 1024, 0
+ * one by one.  cordic_mixbank_info and _run return CORDIC_ERR_ARGS for a NULL
+ * bank; cordic_mixbank_destroy(NULL) does nothing.
+ */
+typedef struct cordic_fmmix_job {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	const int32_t *d_xval, *d_yval;	/* n words each                         */
+	int32_t	*d_oxval, *d_oyval;	/* n words each                         */
+	uint32_t *d_acc;		/* optional device word (NULL: none)    */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                    */
+} cordic_fmmix_job;			/* 72 bytes                             */
+typedef struct cordic_mixbank cordic_mixbank;
+int	cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job *jobs, cordic_mixbank **bank);
+void	cordic_mixbank_destroy(cordic_mixbank *bank);
+int	cordic_mixbank_info(const cordic_mixbank *bank, uint64_t *samples,
+		uint32_t *spans, int32_t *fused, int32_t *tile);
+int	cordic_mixbank_run(const cordic_mixbank *bank, void *stream);
 
 /* ------------------------------------------- clocked view (streaming shim)
  *

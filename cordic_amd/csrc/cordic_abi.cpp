@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "cordic_amd.h"
+#include "cordic_bank_host.h"
 #include "cordic_devmem.h"
 #include "cordic_fm_mix.h"
 #include "cordic_fm_mix_bank.h"
@@ -197,20 +198,13 @@ int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
 
 // ---- FM mixer banks: many of those jobs in two launches
 // (cordic_fm_mix_bank.h)
-struct cordic_mixbank {
+struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
-	int	device = -1;
-	bool	fused = false;
 	uint32_t passes = 0;
-	int	cus = 0;
-	uint64_t samples = 0;
 	// fused: the span table and the workspace, [start words | partials]
 	MixSpan	*d_spans = nullptr;
 	uint32_t *d_words = nullptr;
 	uint32_t nspans = 0, nstarts = 0;
-	// one by one: the non-empty jobs and the workspace of the longest
-	std::vector<cordic_fmmix_job> jobs;
-	void	*d_work = nullptr;
 };
 
 int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
@@ -223,48 +217,18 @@ int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
 	if (njobs >= ((size_t)1 << 28) || !fmxb_jobs_valid(njobs, jobs))
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();	// (a stale error is not this call's)
-	// blocking uploads below: not while the legacy stream is being captured
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	const hipError_t ce = hipStreamIsCapturing(nullptr, &cs);
-	(void)hipGetLastError();
-	if (ce == hipErrorStreamCaptureImplicit
-			|| (ce == hipSuccess && cs != hipStreamCaptureStatusNone))
-		return CORDIC_ERR_UNSUPPORTED;
-
-	uint64_t samples = 0, passes = 0;
-	size_t longest = 0;
-	for (size_t k = 0; k < njobs; k++) {
-		samples += jobs[k].n;
-		passes += fmxb_passes_of(jobs[k].n);
-		if (jobs[k].n > longest)
-			longest = (size_t)jobs[k].n;
-	}
-	cordic_mixbank *b = new (std::nothrow) cordic_mixbank;
-	if (!b)
-		return CORDIC_ERR_NOMEM;
+	cordic_mixbank *b = nullptr;
+	if (int rc = bank_begin(njobs, jobs, fm_mix_fused(plan),
+			[](size_t n) { return fmx_work_bytes(false, n); }, &b))
+		return rc;
 	b->plan = plan;
-	b->samples = samples;
-	b->fused = fm_mix_fused(plan);
-	if (hipGetDevice(&b->device) != hipSuccess) {
-		(void)hipGetLastError();
-		b->device = -1;
-	}
 	if (!b->fused) {
-		for (size_t k = 0; k < njobs; k++)
-			if (jobs[k].n)
-				b->jobs.push_back(jobs[k]);
-		if (!dev_zalloc(&b->d_work, fmx_work_bytes(false, longest))) {
-			cordic_mixbank_destroy(b);
-			return CORDIC_ERR_DEVICE;
-		}
 		*bank = b;
 		return CORDIC_OK;
 	}
-	b->cus = jobs_cus_now();
-	if (b->cus <= 0) {
-		(void)hipGetLastError();
-		b->cus = 256;
-	}
+	uint64_t passes = 0;
+	for (size_t k = 0; k < njobs; k++)
+		passes += fmxb_passes_of(jobs[k].n);
 	b->passes = fmxb_forced_passes(std::getenv("CORDIC_FMXB_PASSES"),
 			fmxb_passes(passes, b->cus));
 	const uint32_t cap = fmxb_forced_cap(std::getenv("CORDIC_FMXB_MAX_SPANS"));
@@ -310,26 +274,16 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 	if (!bank)
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	// (the tables hold device addresses)
-	if (dev != bank->device)
-		return CORDIC_ERR_ARGS;
 	const cordic_plan *plan = bank->plan;
-	if (!bank->fused) {
-		for (const cordic_fmmix_job &jb : bank->jobs)
-			if (int rc = cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm,
-					jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval,
-					jb.d_oyval, bank->d_work, stream))
-				return rc;
-		return CORDIC_OK;
-	}
-	return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_spans,
-		bank->nspans, bank->d_words, bank->d_words + bank->nstarts, bank->cus,
-		stream);
+	return bank_run(*bank, [&] {
+		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_spans,
+			bank->nspans, bank->d_words, bank->d_words + bank->nstarts, bank->cus,
+			stream);
+	}, [&](const cordic_fmmix_job &jb) {
+		return cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
+			jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval, bank->d_work,
+			stream);
+	});
 }
 
 int cordic_plan_queue_info(const cordic_plan *plan, cordic_queue_info *info)
@@ -507,21 +461,13 @@ bool same_core(const cordic_config &a, const cordic_config &b)
 }
 
 // Tile length (vectors) of the data-fed kinds: whole passes of a 256-thread
-// block, as long as the seeded kernels' tiles where the set is big enough to
-// give every resident block (8 per CU) four of them, shorter below.
+// block, as long as the seeded kernels' tiles where the tile-length rule
+// (cordic_bank_host.h; 8 resident blocks per CU) allows, shorter below.
 uint32_t xy_tile_vecs(uint64_t total_vecs)
 {
-	int cus = 0, dev = 0;
-	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus,
-			hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-		(void)hipGetLastError();
-		cus = 256;
-	}
-	const uint64_t per = total_vecs / ((uint64_t)cus * 8u * 4u);
-	uint64_t v = per / kJobPassVecs * kJobPassVecs;
-	if (v < kJobPassVecs) v = kJobPassVecs;
-	if (v > kJobTileVecs) v = kJobTileVecs;
-	return (uint32_t)v;
+	const uint64_t per = bank_tile_room(total_vecs, cus_or_256(), 8);
+	return (uint32_t)std::min<uint64_t>(kJobTileVecs,
+		std::max<uint64_t>(kJobPassVecs, per / kJobPassVecs * kJobPassVecs));
 }
 
 // esize: bytes per sample of every array of the jobs -- 4, or 2 for the sets of
@@ -624,10 +570,7 @@ int jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 	set->cfg = plan->cfg;
 	set->io16 = esize == 2;
 	set->jobs.assign(jobs, jobs + njobs);
-	if (hipGetDevice(&set->device) != hipSuccess) {
-		(void)hipGetLastError();
-		set->device = -1;
-	}
+	set->device = current_device();
 	const bool up = xy
 		? dev_upload(xtiles.data(), xtiles.size() * sizeof(TileDescXY), &set->d_tiles)
 			&& dev_upload(xtails.data(), xtails.size() * sizeof(TileDescXY), &set->d_tails)
@@ -760,12 +703,9 @@ int cordic_plan_run_jobs(const cordic_plan *plan, const cordic_jobset *set,
 		return CORDIC_ERR_ARGS;
 	// cut for this core (the tile table holds PW-scaled phase words) and for
 	// this device (it holds device addresses)?
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	if (!same_core(set->cfg, plan->cfg) || dev != set->device)
+	if (int rc = device_is_current(set->device))
+		return rc;
+	if (!same_core(set->cfg, plan->cfg))
 		return CORDIC_ERR_ARGS;
 	const int kind = set->kind;
 	// a data-fed job through the single call of its kind (taken where that

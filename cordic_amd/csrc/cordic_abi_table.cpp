@@ -450,10 +450,7 @@ int oscbank_create(const SineCore &core, const QueueRing *queues, size_t njobs,
 	b->tunings.resize(njobs);
 	for (size_t k = 0; k < njobs; k++)
 		b->tunings[k] = cordic_osc_tuning{jobs[k].phase0, jobs[k].fcw, jobs[k].index0};
-	if (hipGetDevice(&b->device) != hipSuccess) {
-		(void)hipGetLastError();
-		b->device = -1;
-	}
+	b->device = current_device();
 	if (!dev_upload(tiles.data(), tiles.size() * sizeof(OscTile), &b->d_tiles)
 			|| !dev_upload(edges.data(), edges.size() * sizeof(OscEdge), &b->d_edges)
 			|| !dev_upload(b->tunings.data(), njobs * sizeof(cordic_osc_tuning),
@@ -495,16 +492,6 @@ int oscbank_create16(const SineCore &core, const QueueRing *queues, size_t njobs
 	return oscbank_create(core, queues, njobs, wide.data(), out, true);
 }
 
-// the bank's device current?  (its tables hold device addresses)
-int oscbank_device(const cordic_oscbank *bank)
-{
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	return dev == bank->device ? CORDIC_OK : CORDIC_ERR_ARGS;
-}
 } // namespace
 
 int cordic_table_bank_create(const cordic_table *tbl, size_t njobs,
@@ -563,7 +550,7 @@ int cordic_oscbank_run(const cordic_oscbank *bank, uint64_t index_offset,
 {
 	if (!bank)
 		return CORDIC_ERR_ARGS;
-	if (int rc = oscbank_device(bank))
+	if (int rc = device_is_current(bank->device))
 		return rc;
 	if (bank->samples == 0)
 		return CORDIC_OK;
@@ -580,7 +567,7 @@ int cordic_oscbank_retune(cordic_oscbank *bank, size_t first, size_t count,
 	if (!bank || first > bank->tunings.size()
 			|| count > bank->tunings.size() - first || (count && !tunings))
 		return CORDIC_ERR_ARGS;
-	if (int rc = oscbank_device(bank))
+	if (int rc = device_is_current(bank->device))
 		return rc;
 	bool query_failed = false;
 	const bool capturing = stream_capturing(stream, &query_failed);

@@ -1,10 +1,16 @@
-// cordic_devmem.h -- host-only helpers of the C ABI units (cordic_abi*.cpp):
-// device memory of the handles, and the one stream-capture query.  The handles
+// cordic_devmem.h -- host-only helpers of the C ABI units (cordic_abi*.cpp,
+// cordic_fm_demod_bank.hip): device memory of the handles, the stream-capture
+// queries, a handle's device, the skeleton of the two FM bank handles.  Handles
 // are C structs that their *_destroy functions free; nothing here owns memory.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "cordic_amd.h"
 
 // frees the non-null ones of its pointers, then nulls them
 template <typename... T> static void dev_free(T *&...p)
@@ -64,4 +70,97 @@ static inline bool stream_capturing(void *stream, bool *query_failed)
 	if (query_failed)
 		*query_failed = failed;
 	return !failed && cs != hipStreamCaptureStatusNone;
+}
+
+// The legacy (null) stream, whose capture a create's blocking uploads may not
+// enter.  This one does ask the null stream; the runtime says yes by the status
+// or, where another stream's capture makes the legacy stream unusable, by the
+// error below.  Any other failure is "not capturing": the uploads report it.
+static inline bool legacy_stream_capturing()
+{
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	const hipError_t ce = hipStreamIsCapturing(nullptr, &cs);
+	(void)hipGetLastError();
+	return ce == hipErrorStreamCaptureImplicit
+		|| (ce == hipSuccess && cs != hipStreamCaptureStatusNone);
+}
+
+// the current device, for a handle to record; -1 and no sticky error: none
+static inline int current_device()
+{
+	int dev = -1;
+	return hipGetDevice(&dev) == hipSuccess ? dev : ((void)hipGetLastError(), -1);
+}
+
+// Is the device that a handle recorded current?  (Its tables hold device
+// addresses.)  CORDIC_ERR_DEVICE: none is, CORDIC_ERR_ARGS: another one is.
+static inline int device_is_current(int device)
+{
+	const int dev = current_device();
+	return dev < 0 ? CORDIC_ERR_DEVICE : dev == device ? CORDIC_OK : CORDIC_ERR_ARGS;
+}
+
+// the CUs of the current device (cordic_jobs_fused.hip), or 256 and no sticky error
+namespace cordic_amd { int jobs_cus_now(); }
+static inline int cus_or_256()
+{
+	const int cus = cordic_amd::jobs_cus_now();
+	return cus > 0 ? cus : ((void)hipGetLastError(), 256);
+}
+
+// ---- What cordic_demodbank (cordic_fm_demod_bank.hip) and cordic_mixbank
+// (cordic_abi.cpp) share: a bank runs FUSED, from descriptor tables that its
+// create cuts and uploads, or ONE BY ONE through the single call of its kind.
+template <typename Job> struct BankHandle {
+	bool	fused = false;
+	int	device = -1, cus = 0;	// (cus: of a fused bank's device, at create)
+	uint64_t samples = 0;
+	// one by one: the non-empty jobs and the workspace of the longest
+	std::vector<Job> jobs;
+	void	*d_work = nullptr;
+};
+
+// The head of a create, behind the argument checks: makes the handle B (a
+// BankHandle<Job>) and finishes one that runs one by one (work_bytes(n): the
+// single call's workspace).  A fused one the caller cuts for, or frees.
+template <typename B, typename Job, typename WorkBytes>
+static int bank_begin(size_t njobs, const Job *jobs, bool fused,
+		WorkBytes work_bytes, B **out)
+{
+	if (legacy_stream_capturing())	// (blocking uploads below)
+		return CORDIC_ERR_UNSUPPORTED;
+	B *b = new (std::nothrow) B;
+	if (!b)
+		return CORDIC_ERR_NOMEM;
+	b->fused = fused;
+	b->device = current_device();
+	size_t longest = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		b->samples += jobs[k].n;
+		if (jobs[k].n > longest)
+			longest = (size_t)jobs[k].n;
+		if (!fused && jobs[k].n)
+			b->jobs.push_back(jobs[k]);
+	}
+	b->cus = fused ? cus_or_256() : 0;
+	if (!fused && !dev_zalloc(&b->d_work, work_bytes(longest))) {
+		delete b;
+		return CORDIC_ERR_DEVICE;
+	}
+	*out = b;
+	return CORDIC_OK;
+}
+
+// A run: on the handle's device, the fused launches or the kept jobs through `each`
+template <typename Job, typename Fused, typename Each>
+static int bank_run(const BankHandle<Job> &b, Fused fused, Each each)
+{
+	if (int rc = device_is_current(b.device))
+		return rc;
+	if (b.fused)
+		return fused();
+	for (const Job &jb : b.jobs)
+		if (int rc = each(jb))
+			return rc;
+	return CORDIC_OK;
 }

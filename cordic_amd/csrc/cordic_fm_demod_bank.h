@@ -10,12 +10,12 @@
 #ifndef CORDIC_FM_DEMOD_BANK_H
 #define CORDIC_FM_DEMOD_BANK_H
 
-#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 #include "cordic_amd.h"
+#include "cordic_bank_host.h"
 #include "cordic_fm_demod.h"
 
 namespace cordic_amd {
@@ -45,30 +45,21 @@ constexpr uint32_t fmd_bank_tile_vecs(int passes)
 static_assert(kFmdTileVecs == fmd_bank_tile_vecs(kFmdPasses),
 	"a tile of the single call is a bank's tile of 8 passes");
 
-// P for a bank of `total_vecs` whole vectors on a device of `cus` CUs: the
-// rule of the data-fed job sets (xy_tile_vecs, cordic_abi.cpp) -- the longest
-// tile that still gives every resident block (8 per CU) four of them -- in the
-// steps 1, 2, 4, 8.
+// P for a bank of `total_vecs` whole vectors on `cus` CUs: the tile-length rule
+// (cordic_bank_host.h) with 8 resident blocks per CU, in the steps 1, 2, 4, 8.
 inline int fmd_bank_passes(uint64_t total_vecs, int cus)
 {
-	const uint64_t per = total_vecs / ((uint64_t)(cus > 0 ? cus : 256) * 8u * 4u);
-	int p = 8;
-	while (p > 1 && (uint64_t)p * kFmdBankPassVecs > per)
-		p >>= 1;
-	return p;
+	return (int)bank_passes(total_vecs, cus, 8, kFmdBankPassVecs, 8);
 }
 
 // The argument checks of cordic_demodbank_create that need no device: every
 // job with n > 0 has four non-NULL, 4-byte-aligned sample pointers, an aligned
 // d_last, reserved == 0 and a length within SIZE_MAX >> 4; no output range
 // (d_omag, d_ofreq, the word at d_last) overlaps another output range or any
-// input range of the bank.  Found by sorting the ranges by address: a range
-// that begins inside an earlier one is an overlap, which is refused unless
-// both are inputs.
+// input range of the bank (BankRanges, cordic_bank_host.h).
 inline bool fmd_bank_jobs_valid(size_t njobs, const cordic_demod_job *jobs)
 {
-	struct Range { uint64_t lo, hi; bool out; };
-	std::vector<Range> r;
+	BankRanges r;
 	for (size_t k = 0; k < njobs; k++) {
 		const cordic_demod_job &jb = jobs[k];
 		if (jb.n == 0)
@@ -79,26 +70,13 @@ inline bool fmd_bank_jobs_valid(size_t njobs, const cordic_demod_job *jobs)
 		if (!p[0] || !p[1] || !p[2] || !p[3] || ((p[0] | p[1] | p[2] | p[3] | l) & 3u)
 				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
 			return false;
-		const uint64_t bytes = jb.n * 4;
-		for (int i = 0; i < 4; i++) {
-			if (bytes > ~(uint64_t)0 - p[i])
+		for (int i = 0; i < 4; i++)
+			if (!r.add(p[i], jb.n * 4, i >= 2))
 				return false;
-			r.push_back(Range{p[i], p[i] + bytes, i >= 2});
-		}
-		if (l)
-			r.push_back(Range{l, (uint64_t)l + 4, true});
-	}
-	std::sort(r.begin(), r.end(),
-		[](const Range &a, const Range &b) { return a.lo < b.lo; });
-	uint64_t any_end = 0, out_end = 0;	// ends of the ranges in front
-	for (const Range &a : r) {
-		if (a.lo < (a.out ? any_end : out_end))
+		if (l && !r.add(l, 4, true))
 			return false;
-		any_end = std::max(any_end, a.hi);
-		if (a.out)
-			out_end = std::max(out_end, a.hi);
 	}
-	return true;
+	return r.outputs_clear();
 }
 
 // tiles of `tile_vecs` vectors the jobs cut into (saturating at 2^63)

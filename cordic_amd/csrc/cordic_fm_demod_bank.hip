@@ -51,7 +51,6 @@
 
 #include <cstdint>
 #include <cstdlib>
-#include <new>
 #include <vector>
 
 #include "cordic_device.h"
@@ -127,19 +126,13 @@ int launch_fmd_bank(const cordic_config &cfg, const DemodTile *d_tiles,
 } // namespace cordic_amd
 
 // ------------------------------------------------------------ the C ABI
-struct cordic_demodbank {
+struct cordic_demodbank : BankHandle<cordic_demod_job> {
 	cordic_config cfg;
-	int	device = -1;
-	bool	fused = false;
-	int	passes = 0, cus = 0;
-	uint64_t samples = 0;
+	int	passes = 0;
 	// fused
 	cordic_amd::DemodTile *d_tiles = nullptr;
 	cordic_amd::DemodTail *d_tails = nullptr;
 	uint32_t ntiles = 0, ntails = 0;
-	// one by one: the non-empty jobs and the scratch of the longest
-	std::vector<cordic_demod_job> jobs;
-	void	*d_work = nullptr;
 };
 
 int cordic_demodbank_create(const cordic_config *cfg, size_t njobs,
@@ -153,54 +146,19 @@ int cordic_demodbank_create(const cordic_config *cfg, size_t njobs,
 	if (njobs >= ((size_t)1 << 28) || !fmd_bank_jobs_valid(njobs, jobs))
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();	// (a stale error is not this call's)
-	// blocking uploads below: not while the legacy stream is being captured
-	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	const hipError_t ce = hipStreamIsCapturing(nullptr, &cs);
-	(void)hipGetLastError();
-	if (ce == hipErrorStreamCaptureImplicit
-			|| (ce == hipSuccess && cs != hipStreamCaptureStatusNone))
-		return CORDIC_ERR_UNSUPPORTED;
-
-	uint64_t samples = 0, vecs = 0;
-	size_t longest = 0;
-	for (size_t k = 0; k < njobs; k++) {
-		samples += jobs[k].n;
-		vecs += jobs[k].n / 4;
-		if (jobs[k].n > longest)
-			longest = (size_t)jobs[k].n;
-	}
-	cordic_demodbank *b = new (std::nothrow) cordic_demodbank;
-	if (!b)
-		return CORDIC_ERR_NOMEM;
+	cordic_demodbank *b = nullptr;
+	if (int rc = bank_begin(njobs, jobs, fmd_core_is_fused(*cfg), fmd_work_bytes, &b))
+		return rc;
 	b->cfg = *cfg;
-	b->samples = samples;
-	b->fused = fmd_core_is_fused(*cfg);
-	if (hipGetDevice(&b->device) != hipSuccess) {
-		(void)hipGetLastError();
-		b->device = -1;
-	}
 	if (!b->fused) {
-		for (size_t k = 0; k < njobs; k++)
-			if (jobs[k].n)
-				b->jobs.push_back(jobs[k]);
-		if (!dev_zalloc(&b->d_work, fmd_work_bytes(longest))) {
-			cordic_demodbank_destroy(b);
-			return CORDIC_ERR_DEVICE;
-		}
 		*bank = b;
 		return CORDIC_OK;
 	}
-	b->cus = jobs_cus_now();
-	if (b->cus <= 0) {
-		(void)hipGetLastError();
-		b->cus = 256;
-	}
-	b->passes = fmd_bank_passes(vecs, b->cus);
-	if (const char *e = std::getenv("CORDIC_FMD_BANK_PASSES")) {
-		const long v = std::strtol(e, nullptr, 10);
-		if (v == 1 || v == 2 || v == 4 || v == 8)
-			b->passes = (int)v;
-	}
+	uint64_t vecs = 0;
+	for (size_t k = 0; k < njobs; k++)
+		vecs += jobs[k].n / 4;
+	b->passes = (int)bank_forced_passes(std::getenv("CORDIC_FMD_BANK_PASSES"), 8,
+			(uint32_t)fmd_bank_passes(vecs, b->cus));
 	const uint32_t tile_vecs = fmd_bank_tile_vecs(b->passes);
 	if (fmd_bank_count_tiles(njobs, jobs, tile_vecs) > 0xffffffffull) {
 		delete b;
@@ -250,27 +208,16 @@ int cordic_demodbank_run(const cordic_demodbank *bank, void *stream)
 	if (!bank)
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();
-	int dev = -1;
-	if (hipGetDevice(&dev) != hipSuccess) {
-		(void)hipGetLastError();
-		return CORDIC_ERR_DEVICE;
-	}
-	// (the tables hold device addresses)
-	if (dev != bank->device)
-		return CORDIC_ERR_ARGS;
-	if (!bank->fused) {
-		for (const cordic_demod_job &jb : bank->jobs)
-			if (int rc = cordic_fm_demod(&bank->cfg, (size_t)jb.n, jb.d_xval,
-					jb.d_yval, jb.phase0, jb.d_last, jb.d_omag, jb.d_ofreq,
-					bank->d_work, stream))
-				return rc;
-		return CORDIC_OK;
-	}
-	if (!bank->ntiles && !bank->ntails)
-		return CORDIC_OK;
-	// resident blocks
-	const size_t cap = env_block_cap("CORDIC_FMD_MAX_BLOCKS", (size_t)bank->cus * 8);
-	const int grid = (int)(bank->ntiles < cap ? bank->ntiles : cap);
-	return launch_fmd_bank(bank->cfg, bank->d_tiles, bank->ntiles, grid,
-		bank->d_tails, bank->ntails, stream);
+	return bank_run(*bank, [&] {
+		if (!bank->ntiles && !bank->ntails)
+			return (int)CORDIC_OK;
+		// resident blocks
+		const size_t cap = env_block_cap("CORDIC_FMD_MAX_BLOCKS", (size_t)bank->cus * 8);
+		const int grid = (int)(bank->ntiles < cap ? bank->ntiles : cap);
+		return launch_fmd_bank(bank->cfg, bank->d_tiles, bank->ntiles, grid,
+			bank->d_tails, bank->ntails, stream);
+	}, [&](const cordic_demod_job &jb) {
+		return cordic_fm_demod(&bank->cfg, (size_t)jb.n, jb.d_xval, jb.d_yval,
+			jb.phase0, jb.d_last, jb.d_omag, jb.d_ofreq, bank->d_work, stream);
+	});
 }

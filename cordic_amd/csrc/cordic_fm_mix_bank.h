@@ -11,13 +11,13 @@
 #ifndef CORDIC_FM_MIX_BANK_H
 #define CORDIC_FM_MIX_BANK_H
 
-#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
 
 #include "cordic_amd.h"
+#include "cordic_bank_host.h"
 
 namespace cordic_amd {
 
@@ -47,34 +47,22 @@ inline uint64_t fmxb_passes_of(uint64_t n)
 	return n / kFmxbPass + (n % kFmxbPass ? 1 : 0);
 }
 
-// P, the passes of a base span, for a bank of `total_passes` on a device of
-// `cus` CUs: the rule of the data-fed job sets and of fmd_bank_passes -- the
-// longest span that still gives every resident block (4 per CU) four of them
-// -- in the steps 1, 2, 4, 8, 16, ...
+// P, the passes of a base span, for a bank of `total_passes` on `cus` CUs: the
+// tile-length rule (cordic_bank_host.h), 4 resident blocks per CU, steps 1, 2, 4, ...
 inline uint32_t fmxb_passes(uint64_t total_passes, int cus)
 {
-	const uint64_t per = total_passes
-		/ ((uint64_t)(cus > 0 ? cus : 256) * kFmxbBlocksPerCu * 4u);
-	uint32_t p = 1;
-	while (p < kFmxbMaxPasses && (uint64_t)p * 2 <= per)
-		p <<= 1;
-	return p;
+	return bank_passes(total_passes, cus, kFmxbBlocksPerCu, 1, kFmxbMaxPasses);
 }
 
 // CORDIC_FMXB_PASSES / CORDIC_FMXB_MAX_SPANS (read at create): a power of two
 // within 1 .. 2^20 replaces P; a value within 1 .. 4095 lowers the span cap.
 inline uint32_t fmxb_forced_passes(const char *e, uint32_t p)
 {
-	if (!e)
-		return p;
-	const long v = std::strtol(e, nullptr, 10);
-	return (v >= 1 && v <= (long)kFmxbMaxPasses && !(v & (v - 1))) ? (uint32_t)v : p;
+	return bank_forced_passes(e, kFmxbMaxPasses, p);
 }
 inline uint32_t fmxb_forced_cap(const char *e)
 {
-	if (!e)
-		return kFmxbMaxSpans;
-	const long v = std::strtol(e, nullptr, 10);
+	const long v = e ? std::strtol(e, nullptr, 10) : 0;
 	return (v >= 1 && v < (long)kFmxbMaxSpans) ? (uint32_t)v : kFmxbMaxSpans;
 }
 
@@ -94,13 +82,10 @@ inline uint64_t fmxb_job_passes(uint64_t n, uint32_t passes, uint32_t cap)
 // with n > 0 has non-NULL d_fcw, d_xval, d_yval, d_oxval, d_oyval, all seven
 // pointers on the 4-byte grid, reserved == 0 and a length within SIZE_MAX >> 4;
 // no output range (d_oxval, d_oyval, the word at d_acc) overlaps another output
-// range or any input range of the bank.  Found by sorting the ranges by
-// address, as fmd_bank_jobs_valid does: a range that begins inside an earlier
-// one is an overlap, which is refused unless both are inputs.
+// range or any input range of the bank (BankRanges, cordic_bank_host.h).
 inline bool fmxb_jobs_valid(size_t njobs, const cordic_fmmix_job *jobs)
 {
-	struct Range { uint64_t lo, hi; bool out; };
-	std::vector<Range> r;
+	BankRanges r;
 	for (size_t k = 0; k < njobs; k++) {
 		const cordic_fmmix_job &jb = jobs[k];
 		if (jb.n == 0)
@@ -114,28 +99,13 @@ inline bool fmxb_jobs_valid(size_t njobs, const cordic_fmmix_job *jobs)
 				|| ((p[0] | p[1] | p[2] | p[3] | p[4] | p[5] | a) & 3u)
 				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
 			return false;
-		const uint64_t bytes = jb.n * 4;
-		for (int i = 0; i < 6; i++) {
-			if (!p[i])
-				continue;
-			if (bytes > ~(uint64_t)0 - p[i])
+		for (int i = 0; i < 6; i++)
+			if (p[i] && !r.add(p[i], jb.n * 4, i >= 4))
 				return false;
-			r.push_back(Range{p[i], p[i] + bytes, i >= 4});
-		}
-		if (a)
-			r.push_back(Range{a, (uint64_t)a + 4, true});
-	}
-	std::sort(r.begin(), r.end(),
-		[](const Range &a, const Range &b) { return a.lo < b.lo; });
-	uint64_t any_end = 0, out_end = 0;	// ends of the ranges in front
-	for (const Range &a : r) {
-		if (a.lo < (a.out ? any_end : out_end))
+		if (a && !r.add(a, 4, true))
 			return false;
-		any_end = std::max(any_end, a.hi);
-		if (a.out)
-			out_end = std::max(out_end, a.hi);
 	}
-	return true;
+	return r.outputs_clear();
 }
 
 // spans the jobs cut into (saturating at 2^63)

@@ -3,8 +3,7 @@
 // the rule "no output range over another output or any input", and the
 // environment's cap on a grid.  Plain C++ that touches no device, so that a
 // stand-alone program can run it under a sanitizer (tests/test_hostargs.py).
-// (A bank of many jobs sorts its ranges instead: fmd_bank_jobs_valid,
-// cordic_fm_demod_bank.h; fmxb_jobs_valid, cordic_fm_mix_bank.h.)
+// (A bank of many jobs sorts its ranges instead: BankRanges, cordic_bank_host.h.)
 //
 // No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
 // does not hash this unit.

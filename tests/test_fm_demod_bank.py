@@ -141,6 +141,202 @@ def test_info_run_and_destroy_on_a_null_handle():
     L.cordic_demodbank_destroy(None)        # a no-op
 
 
+CUTTER = r"""
+#include <cstdio>
+#include <cstring>
+#include "cordic_fm_demod_bank.h"
+
+using namespace cordic_amd;
+
+static int failures;
+#define EXPECT(c) do { if (!(c)) { std::printf("line %d: %s\n", __LINE__, #c); \
+	failures++; } } while (0)
+
+// addresses that are never dereferenced: job k's four arrays in four regions
+static cordic_demod_job job_at(size_t k, uint64_t n, bool last)
+{
+	cordic_demod_job j;
+	std::memset(&j, 0, sizeof j);
+	const uintptr_t base = 0x10000000u + (uintptr_t)k * 0x100000u + 4 * (k % 4);
+	j.d_xval = (const int32_t *)(base);
+	j.d_yval = (const int32_t *)(base + 0x1000000000u);
+	j.d_omag = (int32_t *)(base + 0x2000000000u);
+	j.d_ofreq = (int32_t *)(base + 0x3000000000u);
+	j.d_last = last ? (uint32_t *)(0x6000000000u + 16 * k) : nullptr;
+	j.n = n;
+	j.phase0 = (uint32_t)(k * 0x9e3779b1u + 1);
+	return j;
+}
+
+static void check_cut(const std::vector<cordic_demod_job> &jobs, int passes)
+{
+	const uint32_t tv = fmd_bank_tile_vecs(passes);
+	EXPECT(tv == (uint32_t)passes * 256 - 1);
+	std::vector<DemodTile> tiles;
+	std::vector<DemodTail> tails;
+	fmd_bank_cut(jobs.size(), jobs.data(), tv, &tiles, &tails);
+	EXPECT(tiles.size() == fmd_bank_count_tiles(jobs.size(), jobs.data(), tv));
+	size_t at = 0, tail_at = 0;
+	for (size_t k = 0; k < jobs.size(); k++) {
+		const cordic_demod_job &jb = jobs[k];
+		const uint64_t x = (uintptr_t)jb.d_xval, y = (uintptr_t)jb.d_yval,
+			m = (uintptr_t)jb.d_omag, f = (uintptr_t)jb.d_ofreq,
+			l = (uintptr_t)jb.d_last;
+		// the tiles cover the job's n / 4 vectors exactly and in order
+		const uint64_t nvec = jb.n / 4;
+		uint64_t v = 0;
+		while (v < nvec) {
+			EXPECT(at < tiles.size());
+			if (at >= tiles.size())
+				return;
+			const DemodTile &t = tiles[at++];
+			EXPECT(t.x == x + v * 16 && t.y == y + v * 16);
+			EXPECT(t.mag == m + v * 16 && t.freq == f + v * 16);
+			EXPECT(t.nvec >= 1 && t.nvec <= tv && t.nvec <= nvec - v);
+			// only a job's last tile is shorter
+			EXPECT(t.nvec == tv || v + t.nvec == nvec);
+			EXPECT(t.first == (v == 0 ? 1u : 0u));
+			EXPECT(t.phase0 == (v == 0 ? jb.phase0 : 0u));
+			EXPECT(t.last == (v == 0 ? l : 0));
+			EXPECT(t.pad == 0);
+			v += t.nvec ? t.nvec : 1;
+		}
+		EXPECT(v == nvec);
+		// a tail exactly when the length is no multiple of 4 or there is a d_last
+		if (jb.n == 0 || (jb.n % 4 == 0 && !l))
+			continue;
+		EXPECT(tail_at < tails.size());
+		if (tail_at >= tails.size())
+			return;
+		const DemodTail &t = tails[tail_at++];
+		const uint64_t s0 = nvec ? nvec * 4 - 1 : 0;
+		EXPECT(t.x == x + s0 * 4 && t.y == y + s0 * 4);
+		EXPECT(t.mag == m + s0 * 4 && t.freq == f + s0 * 4);
+		EXPECT(t.last == l && t.phase0 == jb.phase0 && t.pad == 0);
+		EXPECT(t.count == jb.n - s0 && t.count >= 1 && t.count <= 4);
+		EXPECT(t.first == (nvec == 0 ? 1u : 0u));
+	}
+	EXPECT(at == tiles.size() && tail_at == tails.size());
+}
+
+int main()
+{
+	std::vector<uint64_t> lens = {0, 1, 3, 4, 5, 7, 8, 1019, 1020, 1021, 1024};
+	for (uint64_t p = 1; p <= 8; p *= 2) {
+		const uint64_t t = (p * 256 - 1) * 4;	// samples of a full tile
+		for (uint64_t n : {t - 1, t, t + 1, t + 4, t + 5})
+			lens.push_back(n);
+	}
+	lens.push_back(40003);
+	std::vector<cordic_demod_job> jobs;
+	for (size_t k = 0; k < lens.size(); k++)
+		jobs.push_back(job_at(k, lens[k], k % 2 == 1));
+	EXPECT(fmd_bank_jobs_valid(jobs.size(), jobs.data()));
+	for (int p = 1; p <= 8; p *= 2)
+		check_cut(jobs, p);
+	// ... the other jobs with a d_last, and no job at all
+	for (size_t k = 0; k < jobs.size(); k++)
+		jobs[k] = job_at(k, lens[k], k % 2 == 0);
+	EXPECT(fmd_bank_jobs_valid(jobs.size(), jobs.data()));
+	for (int p = 1; p <= 8; p *= 2) {
+		check_cut(jobs, p);
+		check_cut(std::vector<cordic_demod_job>(), p);
+	}
+	{	// a job of the greatest length: 2^58 vectors, counted without a cut
+		const cordic_demod_job big = job_at(0, ~(size_t)0 >> 4, false);
+		EXPECT(fmd_bank_count_tiles(1, &big, fmd_bank_tile_vecs(8))
+			== (((uint64_t)1 << 58) - 1 + 2046) / 2047);
+	}
+
+	// P by the bank's size: the longest tile that leaves 4 per resident block
+	// (8 per CU): total / (cus * 32) / 256, in the steps 1, 2, 4, 8
+	const int cuses[] = {256, 0, -1};
+	for (int cus : cuses) {
+		EXPECT(fmd_bank_passes(0, cus) == 1 && fmd_bank_passes(4194303, cus) == 1);
+		EXPECT(fmd_bank_passes(4194304, cus) == 2 && fmd_bank_passes(8388607, cus) == 2);
+		EXPECT(fmd_bank_passes(8388608, cus) == 4 && fmd_bank_passes(16777215, cus) == 4);
+		EXPECT(fmd_bank_passes(16777216, cus) == 8);
+		EXPECT(fmd_bank_passes(~(uint64_t)0, cus) == 8);
+	}
+	EXPECT(fmd_bank_passes(16383, 1) == 1 && fmd_bank_passes(16384, 1) == 2);
+	EXPECT(fmd_bank_passes(65536, 1) == 8 && fmd_bank_passes(65536, 64) == 1);
+
+	// the overlap rules
+	const uint64_t n = 64;
+	const cordic_demod_job a = job_at(0, n, true), b = job_at(1, n, true);
+	auto valid = [](cordic_demod_job x, cordic_demod_job y) {
+		const cordic_demod_job two[2] = {x, y};
+		return fmd_bank_jobs_valid(2, two);
+	};
+	EXPECT(valid(a, b));
+	// output on output
+	{ cordic_demod_job c = b; c.d_omag = a.d_omag + n - 1; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_omag = a.d_omag + n; EXPECT(valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_ofreq = a.d_omag; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = a; c.d_ofreq = c.d_omag + 1; EXPECT(!valid(c, b)); }
+	// output over input: of the same job, of another, each kind of input
+	{ cordic_demod_job c = b; c.d_omag = (int32_t *)a.d_xval + n - 1; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_ofreq = (int32_t *)a.d_yval; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_omag = (int32_t *)a.d_yval + 3; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = a; c.d_ofreq = (int32_t *)c.d_yval; EXPECT(!valid(c, b)); }
+	{ cordic_demod_job c = a; c.d_omag = (int32_t *)c.d_xval; EXPECT(!valid(c, b)); }
+	{ cordic_demod_job c = b; c.d_omag = (int32_t *)a.d_xval + n; EXPECT(valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_omag = (int32_t *)a.d_xval - n; EXPECT(valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_omag = (int32_t *)a.d_xval - n + 1; EXPECT(!valid(a, c)); }
+	// d_last: shared, inside an output, inside an input
+	{ cordic_demod_job c = b; c.d_last = a.d_last; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_last = a.d_last + 1; EXPECT(valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_last = (uint32_t *)a.d_ofreq + 5; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = b; c.d_last = (uint32_t *)a.d_xval + n - 1; EXPECT(!valid(a, c)); }
+	{ cordic_demod_job c = a; c.d_last = (uint32_t *)c.d_yval; EXPECT(!valid(c, b)); }
+	{ cordic_demod_job c = a; c.d_last = (uint32_t *)c.d_omag + n; EXPECT(valid(c, b)); }
+	// inputs may alias, within a job and between jobs
+	{ cordic_demod_job c = b; c.d_xval = a.d_xval; c.d_yval = a.d_xval + 1;
+	  EXPECT(valid(a, c)); }
+	{ cordic_demod_job c = a; c.d_yval = c.d_xval; EXPECT(valid(c, b)); }
+	// a job alone: NULLs, the 4-byte grid, reserved, the length
+	auto one = [](cordic_demod_job x) { return fmd_bank_jobs_valid(1, &x); };
+	EXPECT(one(a));
+	{ cordic_demod_job c = a; c.d_last = nullptr; EXPECT(one(c)); }
+	{ cordic_demod_job c = a; c.d_xval = nullptr; EXPECT(!one(c)); }
+	{ cordic_demod_job c = a; c.d_yval = nullptr; EXPECT(!one(c)); }
+	{ cordic_demod_job c = a; c.d_omag = nullptr; EXPECT(!one(c)); }
+	{ cordic_demod_job c = a; c.d_ofreq = nullptr; EXPECT(!one(c)); }
+#define ODD(field, type) { cordic_demod_job c = a; \
+	c.field = (type)((uintptr_t)c.field + 2); EXPECT(!one(c)); }
+	ODD(d_xval, const int32_t *) ODD(d_yval, const int32_t *) ODD(d_omag, int32_t *)
+	ODD(d_ofreq, int32_t *) ODD(d_last, uint32_t *)
+	{ cordic_demod_job c = a; c.reserved = 1; EXPECT(!one(c)); }
+	{ cordic_demod_job c = a; c.n = (~(size_t)0 >> 4) + 1; EXPECT(!one(c)); }
+	{ cordic_demod_job c = a; c.n = ~(size_t)0 >> 4; EXPECT(!one(c)); }	// its arrays reach over each other
+	// a zero-length job's pointers are not looked at
+	{ cordic_demod_job c = a; c.n = 0; c.d_xval = nullptr; c.reserved = 9;
+	  c.d_omag = (int32_t *)3; c.d_last = b.d_last; EXPECT(valid(c, b)); }
+	EXPECT(fmd_bank_jobs_valid(0, nullptr));
+	if (!failures)
+		std::printf("cutter ok\n");
+	return failures ? 1 : 0;
+}
+"""
+
+
+def test_the_host_cutter_under_address_and_ub_sanitizers(tmp_path):
+    """cordic_fm_demod_bank.h in a stand-alone program with its own main: no
+    GPU, no Python in the checked process"""
+    src, exe = tmp_path / "cutter.cpp", tmp_path / "cutter"
+    src.write_text(CUTTER)
+    csrc = os.path.join(ROOT, "cordic_amd", "csrc")
+    r = subprocess.run(
+        ["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror",
+         "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+         "-I", csrc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+        capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "cutter ok" in r.stdout
+
+
 # ---------------------------------------------------------------- GPU
 
 SENT = -0x5a5a5a5b

@@ -231,7 +231,7 @@ def test_bad_jobs_are_refused():
 # oracle's bits.
 
 def xy_tile_vecs(total_vecs):
-    """cordic_abi.cpp: xy_tile_vecs"""
+    """cordic_abi.cpp: xy_tile_vecs, on cordic_bank_host.h: bank_tile_room"""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     per = total_vecs // (cus * 8 * 4)
     return min(2048, max(256, per // 256 * 256))

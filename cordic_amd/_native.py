@@ -315,8 +315,15 @@ ABI = {
                                      C.c_void_p, C.c_uint32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_mix16_workspace": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "cordic_plan_fm_mix16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "cordic_mixbank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.POINTER(C.c_void_p)]),
+    "cordic_mixbank_create16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_void_p)]),
     "cordic_mixbank_destroy": (None, [C.c_void_p]),
     "cordic_mixbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint32),
@@ -602,6 +609,31 @@ class Plan:
             self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
             _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
             "cordic_plan_fm_mix")
+
+    def fm_mix16_workspace(self, n):
+        """cordic_plan_fm_mix16_workspace: bytes of device scratch an fm_mix16
+        call of n samples needs on this plan (16-byte aligned)"""
+        return int(lib().cordic_plan_fm_mix16_workspace(self._h, n))
+
+    def fm_mix16(self, fcw, x, y, ox, oy, work=None, pm=None, n=None, phase0=0,
+                 acc=None, stream=None):
+        """cordic_plan_fm_mix16: fm_mix on int16 x, y, ox, oy (cores with IW
+        and OW <= 16); fcw, pm and acc stay 32-bit words.  work: device
+        scratch of fm_mix16_workspace(n) bytes (16-byte aligned), the
+        caller's."""
+        n = x.numel() if n is None else n
+        _same16("cordic_plan_fm_mix16", x, y, ox, oy)
+        if work is None and n:
+            raise TypeError("work: a device buffer of fm_mix16_workspace(n) bytes")
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and work.numel() * work.element_size() < self.fm_mix16_workspace(n):
+            raise ValueError("work: %d bytes, fm_mix16_workspace(%d) = %d"
+                             % (work.numel() * work.element_size(), n,
+                                self.fm_mix16_workspace(n)))
+        _check(lib().cordic_plan_fm_mix16(
+            self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
+            _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
+            "cordic_plan_fm_mix16")
 
     @property
     def queue_info(self):
@@ -1838,6 +1870,8 @@ class MixBank:
     addresses, pm one more or None, acc a one-word device tensor or None; n
     None: fcw.numel().  The plan must stay open as long as the bank."""
 
+    _create = "cordic_mixbank_create"
+
     def __init__(self, plan, jobs):
         jobs = [tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict)
                 else tuple(jb) for jb in jobs]
@@ -1854,9 +1888,8 @@ class MixBank:
             arr[k].n = fcw.numel() if n is None else n
             arr[k].phase0 = (phase0 or 0) & 0xffffffff
         h = C.c_void_p()
-        _check(lib().cordic_mixbank_create(getattr(plan, "_h", plan), len(jobs),
-                                           arr, C.byref(h)),
-               "cordic_mixbank_create")
+        _check(getattr(lib(), self._create)(getattr(plan, "_h", plan), len(jobs),
+                                            arr, C.byref(h)), self._create)
         self._h = h
 
     def info(self):
@@ -1882,6 +1915,22 @@ class MixBank:
             self.close()
         except Exception:
             pass
+
+
+class MixBank16(MixBank):
+    """cordic_mixbank_create16: a MixBank of fm_mix16 jobs -- x, y, ox, oy are
+    int16 tensors or device addresses (cordic_fmmix_job16 has the layout of
+    cordic_fmmix_job); fcw, pm and acc stay 32-bit.  info, run and close are
+    MixBank's."""
+
+    _create = "cordic_mixbank_create16"
+
+    def __init__(self, plan, jobs):
+        for jb in jobs:
+            jb = tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict) \
+                else tuple(jb)
+            _same16(self._create, *jb[2:6])
+        MixBank.__init__(self, plan, jobs)
 
 
 class _CHostStats(C.Structure):

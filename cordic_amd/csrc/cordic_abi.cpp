@@ -181,11 +181,11 @@ int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
 		return CORDIC_OK;
 	const bool fused = fm_mix_fused(plan);
 	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval,
-			d_oyval, d_work, fmx_work_bytes(fused, n)))
+			d_oyval, 4, d_work, fmx_work_bytes(fused, n)))
 		return rc;
 	if (fused)
 		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm,
-			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, d_work, stream);
+			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, 4, d_work, stream);
 	// the fallback: the phases into the workspace, behind the accumulator's own
 	// scratch, and the rotator on them
 	uint32_t *ph = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_work)
@@ -196,10 +196,76 @@ int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
 	return cordic_plan_p2r(plan, n, d_xval, d_yval, ph, d_oxval, d_oyval, stream);
 }
 
+// ---- the same on int16 I/Q arrays.  16-bit containers: do the core's samples
+// (and phase words) fit?
+static int fits16(const cordic_config &c, bool phase_array)
+{
+	if (c.iw > 16 || c.ow > 16 || (phase_array && c.pw > 16))
+		return CORDIC_ERR_CONTAINER;
+	return CORDIC_OK;
+}
+
+// the plan, its mode, then the container (the tuning words stay 32-bit: any PW)
+static int fm_mix16_plan_ok(const cordic_plan *plan)
+{
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	return fits16(plan->cfg, false);
+}
+
+static bool fm_mix16_fused(const cordic_plan *plan)
+{
+	return fmx_is_fused16(plan->cfg, plan->d_dir, plan->dx);
+}
+
+static size_t fm_mix16_work_bytes(const cordic_plan *plan, size_t n)
+{
+	return fmx16_work_bytes(fm_mix16_fused(plan), fm_mix_fused(plan), n);
+}
+
+size_t cordic_plan_fm_mix16_workspace(const cordic_plan *plan, size_t n)
+{
+	if (fm_mix16_plan_ok(plan) != CORDIC_OK)
+		return 0;
+	return fm_mix16_work_bytes(plan, n);
+}
+
+int cordic_plan_fm_mix16(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval, int16_t *d_oxval,
+		int16_t *d_oyval, void *d_work, void *stream)
+{
+	if (int rc = fm_mix16_plan_ok(plan))
+		return rc;
+	if (n == 0)
+		return CORDIC_OK;
+	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval,
+			d_oyval, 2, d_work, fm_mix16_work_bytes(plan, n)))
+		return rc;
+	if (fm_mix16_fused(plan))
+		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm,
+			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, 2, d_work, stream);
+	// the fallback: the 32-bit call on widened copies, all of it in d_work --
+	// [its workspace | x | y | ox | oy] -- and the low halves of what it wrote
+	unsigned char *w = static_cast<unsigned char *>(d_work);
+	const size_t at = fmx_work_bytes(fm_mix_fused(plan), n), each = fmx16_array_bytes(n);
+	int32_t *wx = reinterpret_cast<int32_t *>(w + at);
+	int32_t *wy = reinterpret_cast<int32_t *>(w + at + each);
+	int32_t *wox = reinterpret_cast<int32_t *>(w + at + 2 * each);
+	int32_t *woy = reinterpret_cast<int32_t *>(w + at + 3 * each);
+	if (int rc = launch_fmx_widen(n, d_xval, d_yval, wx, wy, stream))
+		return rc;
+	if (int rc = cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc, wx, wy, wox,
+			woy, d_work, stream))
+		return rc;
+	return launch_fmx_narrow(n, wox, woy, d_oxval, d_oyval, stream);
+}
+
 // ---- FM mixer banks: many of those jobs in two launches
 // (cordic_fm_mix_bank.h)
 struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
+	bool	io16 = false;			// the jobs' sample arrays hold int16
 	uint32_t passes = 0;
 	// fused: the span table and the workspace, [start words | partials]
 	MixSpan	*d_spans = nullptr;
@@ -207,21 +273,35 @@ struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	uint32_t nspans = 0, nstarts = 0;
 };
 
-int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
-		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
+// both creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h)
+static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
+		cordic_mixbank **bank)
 {
-	if (!bank || (njobs && !jobs))
+	const bool io16 = jobs.esize() == 2;
+	if (!bank || (njobs && !jobs.j32 && !jobs.j16))
 		return CORDIC_ERR_ARGS;
-	if (int rc = fm_mix_plan_ok(plan))
+	if (int rc = io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan))
 		return rc;
 	if (njobs >= ((size_t)1 << 28) || !fmxb_jobs_valid(njobs, jobs))
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();	// (a stale error is not this call's)
+	// the handle keeps its jobs as cordic_fmmix_job, whatever the container
+	std::vector<cordic_fmmix_job> wide;
+	const cordic_fmmix_job *flat = jobs.j32;
+	if (io16) {
+		wide.reserve(njobs);
+		for (size_t k = 0; k < njobs; k++)
+			wide.push_back(jobs[k]);
+		flat = wide.data();
+	}
 	cordic_mixbank *b = nullptr;
-	if (int rc = bank_begin(njobs, jobs, fm_mix_fused(plan),
-			[](size_t n) { return fmx_work_bytes(false, n); }, &b))
+	if (int rc = bank_begin(njobs, flat, io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan),
+			[&](size_t n) {
+				return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(false, n);
+			}, &b))
 		return rc;
 	b->plan = plan;
+	b->io16 = io16;
 	if (!b->fused) {
 		*bank = b;
 		return CORDIC_OK;
@@ -247,6 +327,23 @@ int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
 	}
 	*bank = b;
 	return CORDIC_OK;
+}
+
+int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
+{
+	return mixbank_create(plan, njobs, jobs, bank);
+}
+
+int cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
+{
+	static_assert(sizeof(cordic_fmmix_job16) == sizeof(cordic_fmmix_job)
+		&& offsetof(cordic_fmmix_job16, d_xval) == offsetof(cordic_fmmix_job, d_xval)
+		&& offsetof(cordic_fmmix_job16, d_oyval) == offsetof(cordic_fmmix_job, d_oyval)
+		&& offsetof(cordic_fmmix_job16, n) == offsetof(cordic_fmmix_job, n),
+		"cordic_fmmix_job16 is cordic_fmmix_job with 16-bit sample pointers");
+	return mixbank_create(plan, njobs, jobs, bank);
 }
 
 void cordic_mixbank_destroy(cordic_mixbank *bank)
@@ -278,8 +375,14 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 	return bank_run(*bank, [&] {
 		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_spans,
 			bank->nspans, bank->d_words, bank->d_words + bank->nstarts, bank->cus,
-			stream);
+			bank->io16, stream);
 	}, [&](const cordic_fmmix_job &jb) {
+		if (bank->io16)
+			return cordic_plan_fm_mix16(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm,
+				jb.phase0, jb.d_acc, reinterpret_cast<const int16_t *>(jb.d_xval),
+				reinterpret_cast<const int16_t *>(jb.d_yval),
+				reinterpret_cast<int16_t *>(jb.d_oxval),
+				reinterpret_cast<int16_t *>(jb.d_oyval), bank->d_work, stream);
 		return cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
 			jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval, bank->d_work,
 			stream);
@@ -594,14 +697,6 @@ int cordic_jobset_create(const cordic_plan *plan, int kind, size_t njobs,
 		const cordic_job *jobs, cordic_jobset **out)
 {
 	return jobset_create(plan, kind, njobs, jobs, out, 4);
-}
-
-// 16-bit containers: do the core's samples (and phase words) fit?
-static int fits16(const cordic_config &c, bool phase_array)
-{
-	if (c.iw > 16 || c.ow > 16 || (phase_array && c.pw > 16))
-		return CORDIC_ERR_CONTAINER;
-	return CORDIC_OK;
 }
 
 int cordic_jobset_create16(const cordic_plan *plan, int kind, size_t njobs,

@@ -1,12 +1,14 @@
 // cordic_fm_mix.h -- the FM mixer (cordic_plan_fm_mix, cordic_plan_fm_mix_info,
-// cordic_plan_fm_mix_workspace; include/cordic_amd.h): the rotator with
+// cordic_plan_fm_mix_workspace, and cordic_plan_fm_mix16 / _workspace on int16
+// I/Q arrays; include/cordic_amd.h): the rotator with
 // looked-up directions whose phase is the running sum of per-sample tuning
 // words, made in the kernel,
 //   p_i = start + fcw[0] + .. + fcw[i-1] + pm[i]      (mod 2^32)
 //   (ox_i, oy_i) = cordic_p2r(x_i, y_i, p_i).
 // The launcher and the host checks for cordic_abi.cpp, where the plan and with
 // it the three entry points live; the fallback (cordic_phase_accumulate into
-// the workspace, then cordic_plan_p2r) is put together there.  Behind them, for
+// the workspace, then cordic_plan_p2r) is put together there, and so is the
+// 16-bit fallback (widen, the 32-bit call, narrow).  Behind them, for
 // hipcc only, the device functions that the kernel of this call and the kernel
 // of the FM mixer banks (cordic_fm_mix_bank.hip) share.
 //
@@ -50,19 +52,50 @@ constexpr size_t fmx_work_bytes(bool fused, size_t n)
 // d_dir / dx: the plan's direction tables.  (The mode is the caller's to check.)
 bool	fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx);
 
-// Alignment, and no output range (d_acc and the `work_bytes` of d_work
-// included) over anything else; nothing is launched.  n > 0.
+// The same question for the int16 container (cordic_plan_fm_mix16, a 16-bit
+// bank): the fused plans of the 32-bit form with WW < 35.  The Io16 kernels are
+// instantiated for LJ = 30 only; a core with 16-bit ports and WW 35 has 19 or
+// more extra bits and takes the 16-bit fallback.
+bool	fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx);
+
+// The 16-bit fallback widens into d_work, runs the 32-bit call there and
+// narrows: [the 32-bit call's workspace | x | y | ox | oy], the four as int32,
+// every part on the 16-byte grid.  fused32: fmx_is_fused of the plan.
+constexpr size_t fmx16_array_bytes(size_t n)
+{
+	return (n * 4 + 15) & ~(size_t)15;
+}
+constexpr size_t fmx16_work_bytes(bool fused16, bool fused32, size_t n)
+{
+	return !n ? 0 : fused16 ? kFmxWorkBytes
+		: fmx_work_bytes(fused32, n) + 4 * fmx16_array_bytes(n);
+}
+static_assert(kFmxWorkBytes % 16 == 0, "the widened arrays sit on the 16-byte grid");
+
+// Alignment -- the four sample arrays on the grid of `esize`, their element
+// size in bytes (4 or 2), the words on that of 4, d_work on that of 16 -- and
+// no output range (d_acc and the `work_bytes` of d_work included) over
+// anything else, by the true byte ranges; nothing is launched.  n > 0.
 int	fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
-		const uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		const int32_t *d_oxval, const int32_t *d_oyval, const void *d_work,
+		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
+		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
 		size_t work_bytes);
 
 // The fused path: two launches on `stream` (fm_reduce, then fm_mix_xydir),
-// nothing else.  The caller has checked fmx_is_fused and fmx_check_call.
+// nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
+// The caller has checked fmx_is_fused / fmx_is_fused16 and fmx_check_call.
 int	launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
+		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
+		void *d_oyval, size_t esize, void *d_work, void *stream);
+
+// The two elementwise launches of the 16-bit fallback, on `stream`: x and y
+// into int32 arrays, ox and oy back into shorts (the low 16 bits: the 32-bit
+// outputs are sign-extended OW-bit values, OW <= 16).  Any 2-byte alignment.
+int	launch_fmx_widen(size_t n, const int16_t *d_x, const int16_t *d_y,
+		int32_t *d_wx, int32_t *d_wy, void *stream);
+int	launch_fmx_narrow(size_t n, const int32_t *d_wox, const int32_t *d_woy,
+		int16_t *d_ox, int16_t *d_oy, void *stream);
 
 } // namespace cordic_amd
 
@@ -351,28 +384,39 @@ __device__ __forceinline__ RotRegs rot_regs(const CoreParams &kp, const DirArgs 
 // par: the parity of the exchange words ex[0 .. 8), which are double-buffered
 // by pass, so that a pass has ONE barrier; it runs on from call to call.
 // pm may be NULL (wave-uniform).  Nothing at or behind hi is read or written.
-template <int LJ, int NLIVE>
+//
+// IO (Io32 / Io16, cordic_device.h; deduced from the tag behind `wave`) is the
+// container of the four sample arrays and of nothing else: a lane's 4 samples
+// are one 16-byte or one 8-byte access per array, at any element alignment,
+// widened behind the load and narrowed in front of the store; the tuning words
+// and pm are 32-bit words in either, and so is everything in between.  The
+// next pass's samples wait in the container's own vector (two registers per
+// array for Io16), so Io32 is the loop it was.
+template <int LJ, int NLIVE, typename IO>
 __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &da,
 		const RotRegs &rr, const uint32_t (&bk_base)[kDxMaxLevels],
-		const uint32_t *fcw, const uint32_t *pm, const int32_t *ax,
-		const int32_t *ay, int32_t *aox, int32_t *aoy, const size_t lo,
-		const size_t hi, uint32_t &carry, unsigned &par, uint32_t *ex,
-		const unsigned tid, const unsigned wave)
+		const uint32_t *fcw, const uint32_t *pm, const typename IO::ielem *ax,
+		const typename IO::ielem *ay, typename IO::ielem *aox,
+		typename IO::ielem *aoy, const size_t lo, const size_t hi, uint32_t &carry,
+		unsigned &par, uint32_t *ex, const unsigned tid, const unsigned wave, IO)
 {
+	typedef typename IO::ivec ivec;
+	typedef typename IO::ielem ielem;
+	typedef decltype(IO::narrow(i32x4{})) raw4;	// 4 samples as they lie in memory
 	// this lane's 4 samples of the pass at t0; nothing at or behind hi is read,
 	// and a tuning word that is not there counts 0
-	auto load_pass = [&](size_t t0, u32x4 &f, u32x4 &m, i32x4 &x, i32x4 &y) {
+	auto load_pass = [&](size_t t0, u32x4 &f, u32x4 &m, raw4 &x, raw4 &y) {
 		const size_t i = t0 + (size_t)kVec * tid;
 		f = u32x4{};
 		m = u32x4{};
-		x = i32x4{};
-		y = i32x4{};
+		x = raw4{};
+		y = raw4{};
 		if (i + kVec <= hi) {
 			f = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(fcw + i));
 			if (pm)	// (wave-uniform)
 				m = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(pm + i));
-			x = CORDIC_LOAD_IN(reinterpret_cast<const i32x4g *>(ax + i));
-			y = CORDIC_LOAD_IN(reinterpret_cast<const i32x4g *>(ay + i));
+			x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
+			y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
 		} else if (i < hi) {	// the last, partial vector: one lane of the job
 #pragma unroll
 			for (int v = 0; v < kVec; v++) {
@@ -388,11 +432,11 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 	};
 
 	u32x4 nf, nm;
-	i32x4 nx, ny;
+	raw4 nx, ny;
 	load_pass(lo, nf, nm, nx, ny);
 	for (size_t t0 = lo; t0 < hi; t0 += kFmxPass) {
 		const u32x4 f = nf, m = nm;
-		const i32x4 tx = nx, ty = ny;
+		const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
 		// the next pass's words are on their way while this one is rotated
 		if (t0 + kFmxPass < hi)
 			load_pass(t0 + kFmxPass, nf, nm, nx, ny);
@@ -425,14 +469,14 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 
 		const size_t i = t0 + (size_t)kVec * tid;
 		if (i + kVec <= hi) {
-			CORDIC_STORE_OUT(true, reinterpret_cast<i32x4g *>(aox + i), rx);
-			CORDIC_STORE_OUT(true, reinterpret_cast<i32x4g *>(aoy + i), ry);
+			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aox + i), IO::narrow(rx));
+			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aoy + i), IO::narrow(ry));
 		} else if (i < hi) {
 #pragma unroll
 			for (int v = 0; v < kVec; v++) {
 				if (i + v < hi) {
-					aox[i + v] = rx[v];
-					aoy[i + v] = ry[v];
+					aox[i + v] = (ielem)rx[v];
+					aoy[i + v] = (ielem)ry[v];
 				}
 			}
 		}

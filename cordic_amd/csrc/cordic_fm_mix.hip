@@ -1,5 +1,5 @@
-// cordic_fm_mix.hip -- the FM mixer's fused path (cordic_plan_fm_mix): the
-// rotator with looked-up directions (cordic_xydir.h) behind a prefix sum of
+// cordic_fm_mix.hip -- the FM mixer's fused path (cordic_plan_fm_mix, and
+// cordic_plan_fm_mix16 on int16 I/Q arrays): the rotator with looked-up directions (cordic_xydir.h) behind a prefix sum of
 // per-sample tuning words,
 //   start = phase0 + *d_acc
 //   p_i   = start + fcw[0] + .. + fcw[i-1] + pm[i]      (mod 2^32)
@@ -55,6 +55,7 @@
 //   fm_mix_xydir<29, N>   98  100   98   98  104  108  108
 //   rotator_xydir<30, N>  89   95   90   90   91   94   94
 //   fm_mix_xydir<30, N>   92   98   95   95  102  103  103
+//   ... <30, N, Io16>     92   96   92   92   99  100  100
 // The scan costs 3 .. 11 registers: four more words in flight per lane (fcw and
 // pm against the phase) and the carry.  With 512 registers per lane of a SIMD,
 // allocated in eights, up to 96 hold 5 waves and up to 128 hold 4: an occupancy
@@ -64,6 +65,19 @@
 // but one instance, so the step is taken and the grid is sized for 4 blocks
 // per CU.  The tables are 64 KiB at the most, so LDS admits at least two
 // blocks, and four wherever the tables stay within 40 KiB.
+//
+// The container (the third template parameter, Io32 / Io16 of cordic_device.h)
+// is what pass_loop loads x and y as and stores ox and oy as, and nothing else:
+// fm_reduce, the span geometry, the exchange words and the workspace are the
+// same.  The table above was taken again with the parameter in place: every
+// 32-bit count is what it was.  The Io16 instances exist for LJ = 30 only -- a
+// core with ports of at most 16 bits and WW 35 has 19 or more extra bits and
+// takes the 16-bit fallback (fmx_is_fused16) -- and take 0 .. 3 registers FEWER
+// than their 32-bit twins: the next pass's x and y wait in two registers each,
+// not four.  A lane moves 8 bytes per sample array and pass
+// (global_load_dwordx2 / global_store_dwordx2) at any 2-byte alignment: 16
+// bytes per sample (20 with pm) against 24 (28).  The 16-bit fallback's two
+// elementwise kernels, fmx_widen and fmx_narrow, take 12 registers each.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -84,17 +98,20 @@ struct FmxArgs {
 	const uint32_t *fcw, *pm;	// pm may be NULL
 	uint32_t *acc;			// may be NULL
 	const uint32_t *work;		// fm_reduce's: [0] start, [4 + b] partials
-	const int32_t *x, *y;
-	int32_t	*ox, *oy;
+	const void *x, *y;		// int32 or int16, by the kernel's container
+	void	*ox, *oy;
 	size_t	n, span;		// span: samples per block, whole passes
 	uint32_t xw;			// LDS byte offset of the 12 exchange words
 };
 
-template <int LJ, int NLIVE>
+template <int LJ, int NLIVE, typename IO>
 __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da,
 		FmxArgs a)
 {
 	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
+	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
+		"16-bit ports and WW 35: the fallback (fmx_is_fused16)");
+	typedef typename IO::ielem ielem;
 	constexpr int kN = dx_levels(NLIVE);
 	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -123,14 +140,16 @@ __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da
 	// the phase of sample lo, without its pm
 	uint32_t carry = a.work[0] + ex[8] + ex[9] + ex[10] + ex[11];
 	unsigned par = 0;
-	pass_loop<LJ, NLIVE>(kp, da, rr, bk_base, a.fcw, a.pm, a.x, a.y, a.ox, a.oy, lo, hi,
-		carry, par, ex, tid, wave);
+	pass_loop<LJ, NLIVE>(kp, da, rr, bk_base, a.fcw, a.pm,
+		static_cast<const ielem *>(a.x), static_cast<const ielem *>(a.y),
+		static_cast<ielem *>(a.ox), static_cast<ielem *>(a.oy), lo, hi, carry, par,
+		ex, tid, wave, IO{});
 	if (a.acc && blockIdx.x == gridDim.x - 1 && tid == 0)
 		*a.acc = carry;
 }
 
 // ---------------------------------------------------------------- host side
-template <int LJ>
+template <int LJ, typename IO>
 static bool launch_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const FmxArgs &a)
 {
@@ -138,7 +157,7 @@ static bool launch_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
 #define X(N) case N: \
 	if (da.dx.n != dx_levels(N)) \
 		return false; \
-	hipLaunchKernelGGL((fm_mix_xydir<LJ, N>), dim3(grid), dim3(kBlock), lds, st, \
+	hipLaunchKernelGGL((fm_mix_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
 		kp, da, a); \
 	return true;
 	FMX_STAGES(X)
@@ -159,6 +178,36 @@ static bool has_instance(int nlive, int ngroups)
 	}
 }
 
+// the 16-bit fallback's elementwise kernels
+__global__ __launch_bounds__(kBlock) void fmx_widen(size_t n,
+		const int16_t *__restrict__ x, const int16_t *__restrict__ y,
+		int32_t *__restrict__ wx, int32_t *__restrict__ wy)
+{
+	const size_t stride = (size_t)gridDim.x * kBlock;
+	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+		wx[i] = x[i];
+		wy[i] = y[i];
+	}
+}
+
+__global__ __launch_bounds__(kBlock) void fmx_narrow(size_t n,
+		const int32_t *__restrict__ wox, const int32_t *__restrict__ woy,
+		int16_t *__restrict__ ox, int16_t *__restrict__ oy)
+{
+	const size_t stride = (size_t)gridDim.x * kBlock;
+	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+		ox[i] = (int16_t)wox[i];
+		oy[i] = (int16_t)woy[i];
+	}
+}
+
+// (at most 2^16 blocks, each walking on by the grid)
+static unsigned elementwise_grid(size_t n)
+{
+	const size_t blocks = (n + kBlock - 1) / kBlock;
+	return (unsigned)(blocks < 65536 ? blocks : 65536);
+}
+
 } // namespace fmx
 
 bool fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx)
@@ -173,9 +222,16 @@ bool fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 		&& fmx::has_instance(cfg.nlive, dx.n);
 }
 
+bool fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx)
+{
+	// (WW 35 is LJ = 29, which has no Io16 instance: with ports of at most 16
+	// bits it means 19 or more extra bits)
+	return cfg.ww < 35 && fmx_is_fused(cfg, d_dir, dx);
+}
+
 int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
-		const uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		const int32_t *d_oxval, const int32_t *d_oyval, const void *d_work,
+		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
+		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
 		size_t work_bytes)
 {
 	using namespace fmx;
@@ -183,22 +239,24 @@ int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 			|| n > (~(size_t)0 >> 4))
 		return CORDIC_ERR_ARGS;
 	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
-		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc)
-		| reinterpret_cast<uintptr_t>(d_xval) | reinterpret_cast<uintptr_t>(d_yval)
-		| reinterpret_cast<uintptr_t>(d_oxval) | reinterpret_cast<uintptr_t>(d_oyval);
-	if ((words & 3u) || (reinterpret_cast<uintptr_t>(d_work) & 15u))
+		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc);
+	const uintptr_t samples = reinterpret_cast<uintptr_t>(d_xval)
+		| reinterpret_cast<uintptr_t>(d_yval) | reinterpret_cast<uintptr_t>(d_oxval)
+		| reinterpret_cast<uintptr_t>(d_oyval);
+	if ((words & 3u) || (samples & (esize - 1))
+			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
 		return CORDIC_ERR_ARGS;
-	const Range out[4] = {range_of(d_oxval, n * 4), range_of(d_oyval, n * 4),
+	const Range out[4] = {range_of(d_oxval, n * esize), range_of(d_oyval, n * esize),
 		range_of(d_acc, 4), range_of(d_work, work_bytes)};
 	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
-		range_of(d_xval, n * 4), range_of(d_yval, n * 4)};
+		range_of(d_xval, n * esize), range_of(d_yval, n * esize)};
 	return outputs_overlap(out, in) ? CORDIC_ERR_ARGS : CORDIC_OK;
 }
 
 int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream)
+		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
+		void *d_oyval, size_t esize, void *d_work, void *stream)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -228,10 +286,32 @@ int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 		span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = cfg.ww == 35
-		? launch_lj<29>(cfg.nlive, grid, lds, st, kp, da, a)
-		: launch_lj<30>(cfg.nlive, grid, lds, st, kp, da, a);
+	const bool done = esize == 2
+		? cfg.ww < 35 && launch_lj<30, Io16>(cfg.nlive, grid, lds, st, kp, da, a)
+		: cfg.ww == 35
+			? launch_lj<29, Io32>(cfg.nlive, grid, lds, st, kp, da, a)
+			: launch_lj<30, Io32>(cfg.nlive, grid, lds, st, kp, da, a);
 	return tnco::finish(done);
+}
+
+int launch_fmx_widen(size_t n, const int16_t *d_x, const int16_t *d_y, int32_t *d_wx,
+		int32_t *d_wy, void *stream)
+{
+	using namespace fmx;
+	(void)hipGetLastError();
+	hipLaunchKernelGGL(fmx_widen, dim3(elementwise_grid(n)), dim3(kBlock), 0,
+		static_cast<hipStream_t>(stream), n, d_x, d_y, d_wx, d_wy);
+	return tnco::finish(true);
+}
+
+int launch_fmx_narrow(size_t n, const int32_t *d_wox, const int32_t *d_woy,
+		int16_t *d_ox, int16_t *d_oy, void *stream)
+{
+	using namespace fmx;
+	(void)hipGetLastError();
+	hipLaunchKernelGGL(fmx_narrow, dim3(elementwise_grid(n)), dim3(kBlock), 0,
+		static_cast<hipStream_t>(stream), n, d_wox, d_woy, d_ox, d_oy);
+	return tnco::finish(true);
 }
 
 } // namespace cordic_amd

@@ -1,5 +1,6 @@
 // cordic_fm_mix_bank.h -- FM mixer banks: many cordic_plan_fm_mix jobs of one
-// p2r / sp2r plan in TWO launches (include/cordic_amd.h, "FM mixer banks").  The
+// p2r / sp2r plan in TWO launches (include/cordic_amd.h, "FM mixer banks"), on
+// int32 or on int16 I/Q arrays (cordic_fmmix_job / cordic_fmmix_job16).  The
 // span descriptors the host cuts at create, the cutter itself -- plain C++ that
 // touches no device, so that a stand-alone program can run it under a
 // sanitizer -- and the launcher of the two kernels that walk the descriptors
@@ -78,29 +79,66 @@ inline uint64_t fmxb_job_passes(uint64_t n, uint32_t passes, uint32_t cap)
 	return pj;
 }
 
-// The argument checks of cordic_mixbank_create that need no device: every job
-// with n > 0 has non-NULL d_fcw, d_xval, d_yval, d_oxval, d_oyval, all seven
-// pointers on the 4-byte grid, reserved == 0 and a length within SIZE_MAX >> 4;
-// no output range (d_oxval, d_oyval, the word at d_acc) overlaps another output
-// range or any input range of the bank (BankRanges, cordic_bank_host.h).
-inline bool fmxb_jobs_valid(size_t njobs, const cordic_fmmix_job *jobs)
+// The jobs of a create, of either struct: cordic_fmmix_job16 is
+// cordic_fmmix_job field for field but for the element type behind the four
+// sample pointers, which the host never dereferences.  jobs[k] is job k as a
+// cordic_fmmix_job; esize() the bytes of a sample, which is all the checks and
+// the cutter know of the container.
+struct MixJobs {
+	const cordic_fmmix_job *j32 = nullptr;
+	const cordic_fmmix_job16 *j16 = nullptr;
+	MixJobs(const cordic_fmmix_job *j) : j32(j) {}
+	MixJobs(const cordic_fmmix_job16 *j) : j16(j) {}
+	MixJobs(std::nullptr_t) {}
+	uint64_t esize() const { return j16 ? 2 : 4; }
+	uint64_t n(size_t k) const { return j16 ? j16[k].n : j32[k].n; }
+	cordic_fmmix_job operator[](size_t k) const
+	{
+		if (!j16)
+			return j32[k];
+		const cordic_fmmix_job16 &a = j16[k];
+		cordic_fmmix_job b;
+		b.d_fcw = a.d_fcw;
+		b.d_pm = a.d_pm;
+		b.d_xval = reinterpret_cast<const int32_t *>(a.d_xval);
+		b.d_yval = reinterpret_cast<const int32_t *>(a.d_yval);
+		b.d_oxval = reinterpret_cast<int32_t *>(a.d_oxval);
+		b.d_oyval = reinterpret_cast<int32_t *>(a.d_oyval);
+		b.d_acc = a.d_acc;
+		b.n = a.n;
+		b.phase0 = a.phase0;
+		b.reserved = a.reserved;
+		return b;
+	}
+};
+
+// The argument checks of cordic_mixbank_create / _create16 that need no device:
+// every job with n > 0 has non-NULL d_fcw, d_xval, d_yval, d_oxval, d_oyval, the
+// four sample pointers on the grid of their element (4 or 2 bytes), d_fcw, d_pm
+// and d_acc on the 4-byte grid, reserved == 0 and a length within SIZE_MAX >>
+// 4; no output range (d_oxval, d_oyval, the word at d_acc) overlaps another
+// output range or any input range of the bank (BankRanges, cordic_bank_host.h),
+// by the true byte ranges: n * esize for a sample array, n * 4 for d_fcw / d_pm.
+inline bool fmxb_jobs_valid(size_t njobs, MixJobs jobs)
 {
+	const uint64_t es = jobs.esize();
 	BankRanges r;
 	for (size_t k = 0; k < njobs; k++) {
-		const cordic_fmmix_job &jb = jobs[k];
+		const cordic_fmmix_job jb = jobs[k];
 		if (jb.n == 0)
 			continue;
-		// inputs, then outputs; pm is optional
+		// inputs, then outputs; pm is optional.  p[0], p[3]: words
 		const uintptr_t p[6] = {(uintptr_t)jb.d_fcw, (uintptr_t)jb.d_xval,
 			(uintptr_t)jb.d_yval, (uintptr_t)jb.d_pm, (uintptr_t)jb.d_oxval,
 			(uintptr_t)jb.d_oyval};
 		const uintptr_t a = (uintptr_t)jb.d_acc;
 		if (!p[0] || !p[1] || !p[2] || !p[4] || !p[5]
-				|| ((p[0] | p[1] | p[2] | p[3] | p[4] | p[5] | a) & 3u)
+				|| ((p[0] | p[3] | a) & 3u)
+				|| ((p[1] | p[2] | p[4] | p[5]) & (es - 1))
 				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
 			return false;
 		for (int i = 0; i < 6; i++)
-			if (p[i] && !r.add(p[i], jb.n * 4, i >= 4))
+			if (p[i] && !r.add(p[i], jb.n * (i == 0 || i == 3 ? 4 : es), i >= 4))
 				return false;
 		if (a && !r.add(a, 4, true))
 			return false;
@@ -109,15 +147,16 @@ inline bool fmxb_jobs_valid(size_t njobs, const cordic_fmmix_job *jobs)
 }
 
 // spans the jobs cut into (saturating at 2^63)
-inline uint64_t fmxb_count_spans(size_t njobs, const cordic_fmmix_job *jobs,
-		uint32_t passes, uint32_t cap)
+inline uint64_t fmxb_count_spans(size_t njobs, MixJobs jobs, uint32_t passes,
+		uint32_t cap)
 {
 	uint64_t t = 0;
 	for (size_t k = 0; k < njobs; k++) {
-		if (!jobs[k].n)
+		const uint64_t n = jobs.n(k);
+		if (!n)
 			continue;
-		const uint64_t pj = fmxb_job_passes(jobs[k].n, passes, cap);
-		t += (fmxb_passes_of(jobs[k].n) + pj - 1) / pj;
+		const uint64_t pj = fmxb_job_passes(n, passes, cap);
+		t += (fmxb_passes_of(n) + pj - 1) / pj;
 		if (t >> 63)
 			break;
 	}
@@ -126,13 +165,16 @@ inline uint64_t fmxb_count_spans(size_t njobs, const cordic_fmmix_job *jobs,
 
 // Cuts valid jobs (fmxb_jobs_valid; fewer than 2^32 spans) into spans, in the
 // jobs' order.  Start words are numbered by non-empty job, partial sums by
-// span: the workspace of the run has *njobs_live + spans->size() words.
-inline void fmxb_cut(size_t njobs, const cordic_fmmix_job *jobs, uint32_t passes,
-		uint32_t cap, std::vector<MixSpan> *spans, uint32_t *njobs_live)
+// span: the workspace of the run has *njobs_live + spans->size() words.  A
+// span's addresses are byte addresses: its first sample is esize bytes per
+// sample into the four sample arrays and 4 into d_fcw / d_pm.
+inline void fmxb_cut(size_t njobs, MixJobs jobs, uint32_t passes, uint32_t cap,
+		std::vector<MixSpan> *spans, uint32_t *njobs_live)
 {
+	const uint64_t es = jobs.esize();
 	uint32_t live = 0;
 	for (size_t k = 0; k < njobs; k++) {
-		const cordic_fmmix_job &jb = jobs[k];
+		const cordic_fmmix_job jb = jobs[k];
 		if (jb.n == 0)
 			continue;
 		const uint64_t len = fmxb_job_passes(jb.n, passes, cap) * kFmxbPass;
@@ -140,11 +182,11 @@ inline void fmxb_cut(size_t njobs, const cordic_fmmix_job *jobs, uint32_t passes
 		uint32_t idx = 0;
 		for (uint64_t s0 = 0; s0 < jb.n; s0 += len, idx++) {
 			const uint64_t cnt = jb.n - s0 < len ? jb.n - s0 : len;
-			const uint64_t at = s0 * 4;
+			const uint64_t at = s0 * 4, sat = s0 * es;
 			spans->push_back(MixSpan{(uintptr_t)jb.d_fcw + at,
 				jb.d_pm ? (uintptr_t)jb.d_pm + at : 0,
-				(uintptr_t)jb.d_xval + at, (uintptr_t)jb.d_yval + at,
-				(uintptr_t)jb.d_oxval + at, (uintptr_t)jb.d_oyval + at,
+				(uintptr_t)jb.d_xval + sat, (uintptr_t)jb.d_yval + sat,
+				(uintptr_t)jb.d_oxval + sat, (uintptr_t)jb.d_oyval + sat,
 				(uintptr_t)jb.d_acc, cnt, live, part0, idx,
 				(s0 ? 0u : kMixSpanFirst)
 					| (s0 + cnt == jb.n ? kMixSpanLast : 0u),
@@ -156,14 +198,15 @@ inline void fmxb_cut(size_t njobs, const cordic_fmmix_job *jobs, uint32_t passes
 		*njobs_live = live;
 }
 
-// The two launches, for a plan of which fmx_is_fused (cordic_fm_mix.h) is true.
+// The two launches, for a plan of which fmx_is_fused (cordic_fm_mix.h) is true
+// -- fmx_is_fused16 where the spans were cut from 16-bit jobs (io16).
 // d_start / d_part: the bank's workspace (one word per non-empty job, one per
 // span).  cus: the device's, at create.  An empty table launches nothing.
 // CORDIC_OK or CORDIC_ERR_DEVICE.
 struct DxInfo;		// (cordic_internal.h)
 int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
-		uint32_t *d_part, int cus, void *stream);
+		uint32_t *d_part, int cus, bool io16, void *stream);
 
 } // namespace cordic_amd
 #endif

@@ -1,5 +1,6 @@
-// cordic_fm_mix_bank.hip -- FM mixer banks (cordic_mixbank_create, _destroy,
-// _info, _run; include/cordic_amd.h): many cordic_plan_fm_mix jobs of one plan,
+// cordic_fm_mix_bank.hip -- FM mixer banks (cordic_mixbank_create, _create16,
+// _destroy, _info, _run; include/cordic_amd.h): many cordic_plan_fm_mix (or
+// cordic_plan_fm_mix16) jobs of one plan,
 // each with its own arrays, length, phase0 and d_acc, in TWO launches.  The
 // single call's reduce-then-scan (cordic_fm_mix.hip) reading span descriptors
 // (MixSpan, cordic_fm_mix_bank.h): the host has cut every job into spans of
@@ -57,6 +58,7 @@
 //   fm_mix_xydir<30, N> before  92   98   95   95  102  103  103
 //   fm_mix_xydir<30, N> after   92   98   95   95  102  103  103
 //   fm_mixbank_xydir<30, N>    115  117  116  116  115  124  124
+//   ... <30, N, Io16>          111  113  112  112  112  120  120
 //   fm_mixbank_reduce           42 (32 bytes of static LDS)
 // The single call's counts did not move.  The bank's kernel takes 12 .. 23
 // more: six array addresses, the sample count and the indices arrive per span
@@ -65,6 +67,13 @@
 // the single call's occupancy: no step is crossed, and the grid is sized for 4
 // blocks per CU; LDS (the tables, at most 64 KiB, and 12 words) decides where
 // it admits fewer, exactly as in launch_fm_mix.
+//
+// The container of the four sample arrays (Io32 / Io16, the third template
+// parameter) reaches pass_loop and nothing else here: MixSpan holds byte
+// addresses, which the host's cutter advances by 2 or 4 bytes per sample, and
+// fm_mixbank_reduce reads tuning words only.  The table was taken again with
+// the parameter in place: the 32-bit rows did not move, and no Io16 instance
+// (LJ = 30 only, see fmx_is_fused16) spills.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -129,13 +138,16 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_reduce(
 }
 
 // launch 2 (see the head of this file)
-template <int LJ, int NLIVE>
+template <int LJ, int NLIVE, typename IO>
 __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArgs da,
 		const MixSpan *__restrict__ spans, uint32_t nspans,
 		const uint32_t *__restrict__ start, const uint32_t *__restrict__ part,
 		uint32_t xw)
 {
 	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
+	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
+		"16-bit ports and WW 35: one by one (fmx_is_fused16)");
+	typedef typename IO::ielem ielem;
 	constexpr int kN = dx_levels(NLIVE);
 	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -167,17 +179,17 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 		pass_loop<LJ, NLIVE>(kp, da, rr, bk_base,
 			reinterpret_cast<const uint32_t *>((uintptr_t)d.fcw),
 			reinterpret_cast<const uint32_t *>((uintptr_t)d.pm),
-			reinterpret_cast<const int32_t *>((uintptr_t)d.x),
-			reinterpret_cast<const int32_t *>((uintptr_t)d.y),
-			reinterpret_cast<int32_t *>((uintptr_t)d.ox),
-			reinterpret_cast<int32_t *>((uintptr_t)d.oy), (size_t)0, (size_t)d.n,
-			carry, par, ex, tid, wave);
+			reinterpret_cast<const ielem *>((uintptr_t)d.x),
+			reinterpret_cast<const ielem *>((uintptr_t)d.y),
+			reinterpret_cast<ielem *>((uintptr_t)d.ox),
+			reinterpret_cast<ielem *>((uintptr_t)d.oy), (size_t)0, (size_t)d.n,
+			carry, par, ex, tid, wave, IO{});
 		if ((d.flags & kMixSpanLast) && d.acc && tid == 0)
 			*reinterpret_cast<uint32_t *>((uintptr_t)d.acc) = carry;
 	}
 }
 
-template <int LJ>
+template <int LJ, typename IO>
 static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const MixSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part, uint32_t xw)
@@ -186,7 +198,7 @@ static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
 #define X(N) case N: \
 	if (da.dx.n != dx_levels(N)) \
 		return false; \
-	hipLaunchKernelGGL((fm_mixbank_xydir<LJ, N>), dim3(grid), dim3(kBlock), lds, st, \
+	hipLaunchKernelGGL((fm_mixbank_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
 		kp, da, spans, nspans, start, part, xw); \
 	return true;
 	FMX_STAGES(X)
@@ -200,7 +212,7 @@ static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
 
 int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
-		uint32_t *d_part, int cus, void *stream)
+		uint32_t *d_part, int cus, bool io16, void *stream)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -220,11 +232,14 @@ int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 	const unsigned grid = (unsigned)(nspans < cap ? nspans : cap);
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = cfg.ww == 35
-		? launch_bank_lj<29>(cfg.nlive, grid, lds, st, kp, da, d_spans, nspans,
-			d_start, d_part, xw)
-		: launch_bank_lj<30>(cfg.nlive, grid, lds, st, kp, da, d_spans, nspans,
-			d_start, d_part, xw);
+	const bool done = io16
+		? cfg.ww < 35 && launch_bank_lj<30, Io16>(cfg.nlive, grid, lds, st, kp, da,
+			d_spans, nspans, d_start, d_part, xw)
+		: cfg.ww == 35
+			? launch_bank_lj<29, Io32>(cfg.nlive, grid, lds, st, kp, da, d_spans,
+				nspans, d_start, d_part, xw)
+			: launch_bank_lj<30, Io32>(cfg.nlive, grid, lds, st, kp, da, d_spans,
+				nspans, d_start, d_part, xw);
 	return tnco::finish(done);
 }
 

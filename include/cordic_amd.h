@@ -1086,9 +1086,45 @@ int	cordic_demodbank_run(const cordic_demodbank *bank, void *stream);
  * d_work off the 16-byte grid, an overlap as above.  What
  * cordic_last_kernel() reports after the call is unspecified.
  *
- * There is no int16 form and no cordic_config-level twin: the direction tables
- * live in the plan, and the int16 rotators have no looked-up-direction kernel.
+ * There is no cordic_config-level twin: the direction tables live in the plan.
  * Many short jobs of one plan go into an FM mixer bank (below).
+ *
+ * cordic_plan_fm_mix16: the same call on int16 I/Q arrays -- ADC samples kept
+ * in shorts, as cordic_plan_mix16 takes them.  Everything above holds: start,
+ * a_i, p_i, *d_acc afterwards, phase0 added by every call, d_pm optional.  For
+ * every i, d_oxval[i] and d_oyval[i] equal what cordic_plan_fm_mix writes when
+ * given d_xval and d_yval sign-extended to int32_t (exact: the 32-bit outputs
+ * are sign-extended OW-bit values and OW <= 16).  The tuning words, d_pm,
+ * phase0 and *d_acc stay 32-bit words -- the accumulator is 32 bits wide
+ * whatever PW is.  The inputs are taken modulo IW: bits of a short above IW are
+ * ignored.  The container rule is cordic_plan_mix16's: IW <= 16 and OW <= 16,
+ * any PW, CORDIC_ERR_CONTAINER otherwise -- checked behind the NULL plan
+ * (CORDIC_ERR_ARGS) and the mode (CORDIC_ERR_MODE), in that order.
+ *
+ * The four sample arrays may sit at any 2-byte-aligned address, for any n;
+ * d_fcw, d_pm and d_acc are 4-byte aligned, d_work 16-byte aligned.  The
+ * overlap rule above applies over the true byte ranges, n * 2 for a sample
+ * array and n * 4 for d_fcw / d_pm, on the host with nothing written.  n == 0:
+ * CORDIC_OK, nothing touched.
+ *
+ * Two paths, identical bits, under the launch contract above word for word:
+ *   fused     the plans for which cordic_plan_fm_mix_info answers 1 -- it
+ *             covers both containers, and *tile is the same 1024 -- with WW <
+ *             35.  The same two launches, the second reading and writing
+ *             shorts, 8 bytes per lane and array: 16 bytes per sample (20 with
+ *             d_pm).  Legal inside a stream capture.
+ *   fallback  every other plan that the container rule admits (9 live stages,
+ *             CORDIC_FLAG_UNIT_GAIN, sp2r, a stage count without an instance;
+ *             and 16-bit ports with WW 35, that is 19 or more extra bits, for
+ *             which the int16 kernels are not instantiated): one launch widens
+ *             d_xval and d_yval into d_work, cordic_plan_fm_mix runs there,
+ *             one launch narrows -- a fixed number of launches, nothing
+ *             allocated.
+ * cordic_plan_fm_mix16_workspace is a pure host function: 0 for n == 0 or a
+ * NULL plan, a multiple of 16, non-decreasing in n; for a fused plan equal to
+ * cordic_plan_fm_mix_workspace, for any other at most 20 n + 65536 + 96 (the
+ * 32-bit call's workspace and four widened arrays, each part on the 16-byte
+ * grid).
  */
 size_t	cordic_plan_fm_mix_workspace(const cordic_plan *plan, size_t n);
 int	cordic_plan_fm_mix_info(const cordic_plan *plan, int32_t *fused,
@@ -1098,6 +1134,12 @@ int	cordic_plan_fm_mix(const cordic_plan *plan, size_t n,
 		uint32_t *d_acc,
 		const int32_t *d_xval, const int32_t *d_yval,
 		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
+size_t	cordic_plan_fm_mix16_workspace(const cordic_plan *plan, size_t n);
+int	cordic_plan_fm_mix16(const cordic_plan *plan, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval,
+		int16_t *d_oxval, int16_t *d_oyval, void *d_work, void *stream);
 
 /* FM mixer banks: many per-sample-tuned mixer jobs in two launches.
  *
@@ -1156,6 +1198,19 @@ int	cordic_plan_fm_mix(const cordic_plan *plan, size_t n,
  * 0; *tile = the samples of a full span of the bank's base size, P * 1024, 0
  * one by one.  cordic_mixbank_info and _run return CORDIC_ERR_ARGS for a NULL
  * bank; cordic_mixbank_destroy(NULL) does nothing.
+ *
+ * cordic_mixbank_create16: the bank of cordic_plan_fm_mix16 jobs, on int16 I/Q
+ * arrays.  It returns an ordinary cordic_mixbank that remembers its container,
+ * as cordic_jobset_create16 returns an ordinary job set: _run, _info and
+ * _destroy work on it unchanged, and run gives per job the bits of
+ * cordic_plan_fm_mix16.  Everything above holds, with these differences: the
+ * four sample pointers are 2-byte aligned (d_fcw, d_pm, d_acc 4-byte), their
+ * byte ranges in the overlap check are n * 2, and a plan with IW > 16 or OW >
+ * 16 is CORDIC_ERR_CONTAINER (behind CORDIC_ERR_ARGS for a NULL plan or bank
+ * and CORDIC_ERR_MODE).  The bank is fused where cordic_plan_fm_mix16 is --
+ * cordic_plan_fm_mix_info answers 1 and WW < 35: exactly two launches, ANY
+ * 2-byte-aligned sample arrays -- and otherwise runs one by one through
+ * cordic_plan_fm_mix16 with a workspace sized at create for the longest job.
  */
 typedef struct cordic_fmmix_job {
 	const uint32_t *d_fcw;		/* n words                              */
@@ -1174,6 +1229,18 @@ void	cordic_mixbank_destroy(cordic_mixbank *bank);
 int	cordic_mixbank_info(const cordic_mixbank *bank, uint64_t *samples,
 		uint32_t *spans, int32_t *fused, int32_t *tile);
 int	cordic_mixbank_run(const cordic_mixbank *bank, void *stream);
+typedef struct cordic_fmmix_job16 {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	const int16_t *d_xval, *d_yval;	/* n shorts each                        */
+	int16_t	*d_oxval, *d_oyval;	/* n shorts each                        */
+	uint32_t *d_acc;		/* optional device word (NULL: none)    */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                    */
+} cordic_fmmix_job16;			/* 72 bytes                             */
+int	cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank);
 
 /* ------------------------------------------- clocked view (streaming shim)
  *

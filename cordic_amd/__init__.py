@@ -20,7 +20,8 @@ from ._native import (  # noqa: F401
     Config, CordicError, Plan, Jobset, JOBS_PHASE_ARRAYS, JOBS_NCO, JOBS_R2P, JOBS_P2R_XY, JOBS_MIX, JOBS_PATH_NONE, JOBS_PATH_FUSED, JOBS_PATH_ONE_BY_ONE, jobset_reap, Group, Arrays, device_count, shard_range, rccl_unique_id, RCCL_ID_BYTES, Table, TBL, QTR, Quad, OscBank, Stream, Seq, seed_table, dir_table, Quality, Sfdr, fill_circle, last_kernel, KERNEL_GENERIC, KERNEL_UNROLLED, KERNEL_SEEDED, KERNEL_LEFT_JUSTIFIED, KERNEL_DIRECTIONS,
     lib, lib_path,
     p2r, p2r_const, nco, mix, r2p, fm_workspace, phase_accumulate,
-    fm_demod_workspace, fm_demod_info, fm_demod, DemodBank, MixBank, MixBank16,
+    fm_demod_workspace, fm_demod_info, fm_demod16_info, fm_demod, DemodBank,
+    DemodBank16, MixBank, MixBank16,
     p2r_host, r2p_host, HostArray, host_last_stats, host_release,
     host_set_devices, host_lane_stats,
     fill_phase_ramp, fill_iq_ramp, digest_u32,
@@ -31,6 +32,7 @@ __all__ = [
     "seed_table", "Quality", "Sfdr", "fill_circle", "last_kernel", "KERNEL_GENERIC", "KERNEL_UNROLLED", "KERNEL_SEEDED", "KERNEL_LEFT_JUSTIFIED", "Table", "TBL", "QTR", "Quad", "OscBank", "Stream", "Seq", "lib", "lib_path",
     "p2r", "p2r_const", "nco", "r2p", "p2r_host", "r2p_host",
     "fm_workspace", "phase_accumulate",
-    "fm_demod_workspace", "fm_demod_info", "fm_demod", "DemodBank", "MixBank", "MixBank16",
+    "fm_demod_workspace", "fm_demod_info", "fm_demod16_info", "fm_demod",
+    "DemodBank", "DemodBank16", "MixBank", "MixBank16",
     "fill_phase_ramp", "fill_iq_ramp", "digest_u32",
 ]

@@ -299,8 +299,12 @@ ABI = {
     "cordic_fm_demod16": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_fm_demod16_info": (C.c_int, [_cfgp, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
     "cordic_demodbank_create": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p,
                                           C.POINTER(C.c_void_p)]),
+    "cordic_demodbank_create16": (C.c_int, [_cfgp, C.c_size_t, C.c_void_p,
+                                            C.POINTER(C.c_void_p)]),
     "cordic_demodbank_destroy": (None, [C.c_void_p]),
     "cordic_demodbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint32),
@@ -1765,6 +1769,17 @@ def fm_demod_info(cfg):
     return int(fused.value), int(tile.value)
 
 
+def fm_demod16_info(cfg):
+    """cordic_fm_demod16_info: (fused, tile) -- whether int16 arrays of this
+    core (IW, OW, PW <= 16), at any alignment, run the fused kernel, and its
+    tile in samples"""
+    fused, tile = C.c_int32(0), C.c_int32(0)
+    _check(lib().cordic_fm_demod16_info(cfg.ref, C.byref(fused),
+                                        C.byref(tile)),
+           "cordic_fm_demod16_info")
+    return int(fused.value), int(tile.value)
+
+
 def fm_demod(cfg, x, y, mag, freq, work, n=None, phase0=0, last=None,
              stream=None):
     """cordic_fm_demod: mag[i] as r2p, freq[i] = the converter's phase step
@@ -1807,6 +1822,8 @@ class DemodBank:
     last) or dicts with those keys; x, y, mag, freq are int32 tensors or device
     addresses, last a one-word device tensor or None; n None: x.numel()."""
 
+    _create = "cordic_demodbank_create"
+
     def __init__(self, cfg, jobs):
         jobs = [tuple(jb.get(k) for k in _DEMOD_KEYS) if isinstance(jb, dict)
                 else tuple(jb) for jb in jobs]
@@ -1821,9 +1838,8 @@ class DemodBank:
             arr[k].n = x.numel() if n is None else n
             arr[k].phase0 = (phase0 or 0) & 0xffffffff
         h = C.c_void_p()
-        _check(lib().cordic_demodbank_create(cfg.ref, len(jobs), arr,
-                                             C.byref(h)),
-               "cordic_demodbank_create")
+        _check(getattr(lib(), self._create)(cfg.ref, len(jobs), arr,
+                                            C.byref(h)), self._create)
         self._h = h
 
     def info(self):
@@ -1849,6 +1865,22 @@ class DemodBank:
             self.close()
         except Exception:
             pass
+
+
+class DemodBank16(DemodBank):
+    """cordic_demodbank_create16: a DemodBank of fm_demod16 jobs -- x, y, mag,
+    freq are int16 tensors or device addresses (cordic_demod_job16 has the
+    layout of cordic_demod_job); last stays a 32-bit word.  info, run and close
+    are DemodBank's."""
+
+    _create = "cordic_demodbank_create16"
+
+    def __init__(self, cfg, jobs):
+        for jb in jobs:
+            jb = tuple(jb.get(k) for k in _DEMOD_KEYS) if isinstance(jb, dict) \
+                else tuple(jb)
+            _same16(self._create, *jb[0:4])
+        DemodBank.__init__(self, cfg, jobs)
 
 
 class _CFmMixJob(C.Structure):

@@ -46,9 +46,10 @@ constexpr size_t fmd_work_bytes(size_t n)
 			& ~(size_t)15 : 0;
 }
 
-// 1: 16-byte-aligned 32-bit arrays of this core run the fused kernel -- the
-// cores that launch_topolar sends to topolar_lj.  (The mode is the caller's to
-// check.)
+// 1: 16-byte-aligned 32-bit arrays of this core, and 16-bit arrays at any
+// alignment of theirs, run the fused kernel -- the cores that launch_topolar
+// sends to topolar_lj.  (The mode, and the 16-bit container's limit on the
+// ports, are the caller's to check.)
 bool	fmd_core_is_fused(const cordic_config &cfg);
 
 // What cordic_fm_demod_info, cordic_fm_demod and cordic_demodbank_create ask of
@@ -197,6 +198,16 @@ __device__ __forceinline__ uint32_t phase_in_front(uint32_t phase0,
 // nothing and holds (phase0 + *d_last) mod 2^PW instead.  That lane alone reads
 // *d_last, and nothing here writes it.
 //
+// IO (Io32 / Io16, cordic_device.h; deduced from the tag behind `par`) is the
+// container of the four sample arrays and of nothing else: a lane's 4 samples
+// are one 16-byte or one 8-byte access per array, at any element alignment
+// (the vector typedefs carry the element's), widened behind the load and
+// narrowed in front of the store, and "one vector in front" is 16 or 8 bytes.
+// The prefetched vectors wait in the container's own type (two registers per
+// array for Io16), so Io32 is the loop it was.  Everything between load and
+// store -- pol_lj_vector, the DPP move, the barrier, the edge words, step_of,
+// phase_in_front -- is 32-bit in either; so are phase0 and *d_last.
+//
 // A tile takes nvec / 256 + 1 passes, the same for every thread of the block.
 // A lane converts its 4 samples by pol_lj_vector and needs one more phase, the
 // last one of the lane in front:
@@ -212,11 +223,12 @@ __device__ __forceinline__ uint32_t phase_in_front(uint32_t phase0,
 // every wave has passed barrier i - 1 before any writes.  The argument counts
 // the block's passes, whatever tile they belong to; pass 0 of a tile uses no
 // word of the pass in front (the one its wave 0 reads is the halo lane's).
-template <int NLIVE, bool DYN, bool UG, bool PLAIN, typename IDX>
+template <int NLIVE, bool DYN, bool UG, bool PLAIN, typename IDX, typename IO>
 __device__ __forceinline__ void sweep_tile(const CoreParams &kp, const LaneConsts &ln,
-		const i32x4g *xin, const i32x4g *yin, i32x4g *omag, i32x4g *ofreq,
+		const typename IO::ivec *xin, const typename IO::ivec *yin,
+		typename IO::ivec *omag, typename IO::ivec *ofreq,
 		const IDX at, const uint32_t nvec, const bool first, const uint32_t phase0,
-		const uint32_t *d_last, uint32_t (*edge)[kBlock / 64], unsigned &par)
+		const uint32_t *d_last, uint32_t (*edge)[kBlock / 64], unsigned &par, IO)
 {
 	const unsigned tid = threadIdx.x, lane = tid & 63u;
 	// (the same in all of a wave's lanes: said so, it stays in a scalar)
@@ -228,14 +240,14 @@ __device__ __forceinline__ void sweep_tile(const CoreParams &kp, const LaneConst
 		prev = phase_in_front(phase0, d_last, sh);
 	uint32_t j = tid;
 	IDX g = at + tid;	// (= at + j)
-	i32x4g nx{}, ny{};	// software prefetch, afresh per tile (as
+	typename IO::ivec nx{}, ny{};	// software prefetch, afresh per tile (as
 	if (j <= nvec && !(first && j == 0)) {	// topolar_lj_jobs)
 		nx = CORDIC_LOAD_IN(&xin[g]);
 		ny = CORDIC_LOAD_IN(&yin[g]);
 	}
 	// (thread 0's vector is behind the end: so is everyone's)
 	for (uint32_t k0 = 0; k0 <= nvec; k0 += kBlock, j += kBlock, g += kBlock) {
-		const i32x4 tx = nx, ty = ny;
+		const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
 		if (j + kBlock <= nvec) {
 			nx = CORDIC_LOAD_IN(&xin[g + kBlock]);
 			ny = CORDIC_LOAD_IN(&yin[g + kBlock]);
@@ -266,8 +278,8 @@ __device__ __forceinline__ void sweep_tile(const CoreParams &kp, const LaneConst
 		for (int v = 1; v < kVec; v++)
 			rf[v] = step_of(rp[v], rp[v - 1], sh);
 		if (j != 0 && j <= nvec) {	// (not the halo)
-			CORDIC_STORE_OUT(true, &omag[g], rm);
-			CORDIC_STORE_OUT(true, &ofreq[g], rf);
+			CORDIC_STORE_OUT(true, &omag[g], IO::narrow(rm));
+			CORDIC_STORE_OUT(true, &ofreq[g], IO::narrow(rf));
 		}
 	}
 }
@@ -276,15 +288,18 @@ __device__ __forceinline__ void sweep_tile(const CoreParams &kp, const LaneConst
 // zero-padded vector, converted by the same pol_lj_vector instance as the
 // sweep, differenced, stored; then *d_last.  A job without a whole vector reads
 // its *d_last here, in the same lane, before writing it; every other job's was
-// read by the sweep, in the launch in front.
-template <int NLIVE, bool DYN, bool UG, bool PLAIN>
-__device__ __forceinline__ void tail_of(const CoreParams &kp, const DemodTail d)
+// read by the sweep, in the launch in front.  IO (a tag, as in sweep_tile): the
+// container of the four sample arrays, loaded and stored one element -- a word
+// or a short -- at a time.
+template <int NLIVE, bool DYN, bool UG, bool PLAIN, typename IO>
+__device__ __forceinline__ void tail_of(const CoreParams &kp, const DemodTail d, IO)
 {
+	typedef typename IO::ielem ielem;
 	const LaneConsts ln(kp);
-	const int32_t *x = reinterpret_cast<const int32_t *>((uintptr_t)d.x);
-	const int32_t *y = reinterpret_cast<const int32_t *>((uintptr_t)d.y);
-	int32_t *omag = reinterpret_cast<int32_t *>((uintptr_t)d.mag);
-	int32_t *ofreq = reinterpret_cast<int32_t *>((uintptr_t)d.freq);
+	const ielem *x = reinterpret_cast<const ielem *>((uintptr_t)d.x);
+	const ielem *y = reinterpret_cast<const ielem *>((uintptr_t)d.y);
+	ielem *omag = reinterpret_cast<ielem *>((uintptr_t)d.mag);
+	ielem *ofreq = reinterpret_cast<ielem *>((uintptr_t)d.freq);
 	uint32_t *lp = reinterpret_cast<uint32_t *>((uintptr_t)d.last);
 	i32x4 tx{}, ty{};
 #pragma unroll
@@ -300,15 +315,15 @@ __device__ __forceinline__ void tail_of(const CoreParams &kp, const DemodTail d)
 	uint32_t p = rp[0];
 	if (d.first) {
 		p = phase_in_front(d.phase0, lp, ln.sh);
-		omag[0] = rm[0];
-		ofreq[0] = step_of(rp[0], p, ln.sh);
+		omag[0] = (ielem)rm[0];
+		ofreq[0] = (ielem)step_of(rp[0], p, ln.sh);
 		p = rp[0];
 	}
 #pragma unroll
 	for (int v = 1; v < kVec; v++)
 		if ((uint32_t)v < d.count) {
-			omag[v] = rm[v];
-			ofreq[v] = step_of(rp[v], p, ln.sh);
+			omag[v] = (ielem)rm[v];
+			ofreq[v] = (ielem)step_of(rp[v], p, ln.sh);
 			p = rp[v];
 		}
 	if (lp)
@@ -326,9 +341,10 @@ struct Instance {
 // (cordic_inst_pol_lj.hip) -- 20 and 29 live stages on static PLAIN instances
 // (WW <= 32, rounding at the 2^30 scale), every other core on the dynamic-exit
 // one -- and unit gain on a dynamic-exit instance of its own, as launch_pol_lj
-// has it.  (CORDIC_FORCE_DYN is launch_pol_lj's knob alone.)
+// has it.  (CORDIC_FORCE_DYN is launch_pol_lj's knob alone.)  The container
+// comes as a tag: Io32 here, Io16 below.
 template <typename F>
-void with_instance(const cordic_config &cfg, const CoreParams &kp, F &&f)
+void with_instance(const cordic_config &cfg, const CoreParams &kp, F &&f, Io32)
 {
 	if (kp.post_mul != 0)		// CORDIC_FLAG_UNIT_GAIN
 		return f(Instance<kDynStages, true, true, false>{});
@@ -338,6 +354,18 @@ void with_instance(const cordic_config &cfg, const CoreParams &kp, F &&f)
 	case 29: return f(Instance<29, false, false, true>{});
 	default: return f(Instance<kDynStages, true, false, false>{});
 	}
+}
+
+// Io16: a core that a *16 call accepts has IW, OW, PW <= 16 and with them at
+// most about 13 live stages (r2p 16 16 2 16 -1: WW 24, 13 stages), so the
+// static 20- and 29-stage instances never apply: the dynamic-exit instance and
+// its unit-gain twin serve every such core.
+template <typename F>
+void with_instance(const cordic_config &, const CoreParams &kp, F &&f, Io16)
+{
+	if (kp.post_mul != 0)		// CORDIC_FLAG_UNIT_GAIN
+		return f(Instance<kDynStages, true, true, false>{});
+	return f(Instance<kDynStages, true, false, false>{});
 }
 
 } // namespace fmd

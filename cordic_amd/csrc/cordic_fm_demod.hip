@@ -1,16 +1,18 @@
 // cordic_fm_demod.hip -- FM demodulation (cordic_fm_demod, cordic_fm_demod16,
-// cordic_fm_demod_info, cordic_fm_demod_workspace): the r2p / sr2p converter
-// with its phase differenced from sample to sample,
+// cordic_fm_demod_info, cordic_fm_demod16_info, cordic_fm_demod_workspace): the
+// r2p / sr2p converter with its phase differenced from sample to sample,
 //   prev   = (phase0 + *d_last) mod 2^PW
 //   freq_i = sext_PW((ph_i - ph_(i-1)) mod 2^PW),   ph_(-1) = prev
 //   mag_i  = cordic_r2p's,   *d_last = ph_(n-1),
 // ph_i being the word cordic_r2p writes to d_ophase[i].
 //
 // FUSED (fm_demod_lj, fm_demod_tail): the cores that launch_topolar sends to
-// topolar_lj (32-bit containers, WW <= 34, no wrap), when all four arrays sit
-// on 16-byte boundaries.  (That last condition is this entry point's own:
-// topolar_lj itself takes any 4-byte-aligned array, and fm_demod_lj uses the
-// same vector types; displaced arrays are simply routed to the fallback here.)
+// topolar_lj (WW <= 34, no wrap) -- 32-bit arrays when all four sit on 16-byte
+// boundaries, 16-bit arrays (cordic_fm_demod16; the Io16 instances, 8-byte
+// vectors) at any alignment of theirs.  (The 16-byte condition is the 32-bit
+// entry point's own, kept as it was: topolar_lj itself takes any
+// 4-byte-aligned array, and fm_demod_lj uses the same vector types; displaced
+// 32-bit arrays are simply routed to the fallback here.)
 // A lane converts the 4 samples of a vector exactly as topolar_lj_sweep does
 // and needs one more phase: the last one of the vector in front.  Blocks
 // therefore sweep CONTIGUOUS tiles (b, b + gridDim.x, ...) of 8 * 256 - 1 = 2047
@@ -34,20 +36,27 @@
 // records none.
 //
 // Registers (.vgpr_count / scratch bytes of the gfx950 code objects, -O3,
-// --save-temps; profiles/r14/fm_refactor_isa.txt):
+// --save-temps; profiles/r14/fm_refactor_isa.txt, taken again with the
+// container parameter in place, profiles/r18/fm_demod16_isa.txt):
 //                        topolar_lj  topolar_lj_jobs  fm_demod_lj  fm_demod_tail
 //   20 stages, PLAIN         49            57           56 / 0        32 / 0
 //   29 stages, PLAIN         49            57           56 / 0        32 / 0
 //   dynamic exit             88            97           94 / 0        67 / 0
 //   dynamic exit, unit gain  88            97           94 / 0        67 / 0
+//   Io16, dynamic exit                                  90 / 0        67 / 0
+//   Io16, dyn., unit gain                               90 / 0        67 / 0
 // With 512 registers per lane of a SIMD, allocated in eights: 56 -> 8 waves
 // (the most a SIMD holds) for the static instances as for topolar_lj's 49,
 // and 96 -> 5 waves for the dynamic ones as for its 88.  The differencing
-// crosses no occupancy step; no instance spills.  32 bytes of LDS per block of
-// fm_demod_lj, none in the tail kernel.
+// crosses no occupancy step; no instance spills.  The Io32 counts are what
+// they were before the parameter; the Io16 instances (dynamic exit only: a
+// core with 16-bit ports has about 13 live stages) hold the prefetched
+// vectors in two registers per array where Io32 holds four, 90 -> 96 -> 5
+// waves.  32 bytes of LDS per block of fm_demod_lj, none in the tail kernel.
 //
 // FALLBACK (everything else: WW 35 .. 40 and wider, cores that wrap, the A/B
-// flags, arrays off the 16-byte grid, the 16-bit form): launch_topolar writes
+// flags, 32-bit arrays off the 16-byte grid; T = uint16_t for such cores of
+// the 16-bit form): launch_topolar writes
 // the raw phases into d_ofreq; fmd_save keeps the last phase of every
 // 4096-sample tile (and prev, and writes *d_last -- the same thread reads it
 // first); fmd_diff differences in place, a block per tile: every thread has
@@ -79,10 +88,16 @@ using namespace dev;
 // dynamic-exit instances, whose 40 stage angles live in scalar registers, then
 // move about 90 more of them through VGPR lanes inside the chain: 109 against
 // 114 Gsample/s on a WW 33 core (profiles/r14/fm_refactor_rates.txt).
-template <int NLIVE, bool DYN, bool UG, bool PLAIN>
+//
+// IO: the container of the four arrays (Io32 / Io16); nvec, the tiles and the
+// index count vectors of 4 samples in either, so the 16-bit form is the same
+// kernel on 8-byte vectors.
+template <int NLIVE, bool DYN, bool UG, bool PLAIN, typename IO = Io32>
 __global__ __launch_bounds__(kBlock) void fm_demod_lj(CoreParams kp,
-		const i32x4g *__restrict__ xin, const i32x4g *__restrict__ yin,
-		i32x4g *__restrict__ omag, i32x4g *__restrict__ ofreq, size_t nvec,
+		const typename IO::ivec *__restrict__ xin,
+		const typename IO::ivec *__restrict__ yin,
+		typename IO::ivec *__restrict__ omag,
+		typename IO::ivec *__restrict__ ofreq, size_t nvec,
 		size_t ntiles, uint32_t phase0, const uint32_t *__restrict__ d_last)
 {
 	__shared__ uint32_t edge[2][kBlock / 64];
@@ -95,17 +110,17 @@ __global__ __launch_bounds__(kBlock) void fm_demod_lj(CoreParams kp,
 			| vgpr_const((uint32_t)base);
 		sweep_tile<NLIVE, DYN, UG, PLAIN>(kp, ln, xin - 1, yin - 1, omag - 1, ofreq - 1,
 			at, (uint32_t)(left < kFmdTileVecs ? left : kFmdTileVecs), t == 0,
-			phase0, d_last, edge, par);
+			phase0, d_last, edge, par, IO{});
 	}
 }
 
 // The tail of the call, one lane (tail_of, cordic_fm_demod.h), behind the sweep
 // in stream order
-template <int NLIVE, bool DYN, bool UG, bool PLAIN>
+template <int NLIVE, bool DYN, bool UG, bool PLAIN, typename IO = Io32>
 __global__ __launch_bounds__(64) void fm_demod_tail(CoreParams kp, DemodTail d)
 {
 	if (threadIdx.x == 0)
-		tail_of<NLIVE, DYN, UG, PLAIN>(kp, d);
+		tail_of<NLIVE, DYN, UG, PLAIN>(kp, d, IO{});
 }
 
 // ---- fallback.  T: uint32_t, or uint16_t for the 16-bit form
@@ -175,10 +190,13 @@ __global__ __launch_bounds__(1024) void fmd_diff(T *ph, size_t n,
 
 // ---------------------------------------------------------------- host side
 // Two launches at the most: the sweep over the whole vectors, then the tail.
-static int run_fused(const cordic_config &cfg, size_t n, const int32_t *x,
-		const int32_t *y, uint32_t phase0, uint32_t *d_last, int32_t *mag,
-		int32_t *freq, hipStream_t st)
+// IO: the container of the four arrays, which sit on its element's grid.
+template <typename IO>
+static int run_fused(const cordic_config &cfg, size_t n, const typename IO::ielem *x,
+		const typename IO::ielem *y, uint32_t phase0, uint32_t *d_last,
+		typename IO::ielem *mag, typename IO::ielem *freq, hipStream_t st)
 {
+	typedef typename IO::ivec ivec;
 	const size_t nvec = n / kVec;
 	const CoreParams kp = make_params_jobs(cfg);
 	if (nvec) {
@@ -193,11 +211,11 @@ static int run_fused(const cordic_config &cfg, size_t n, const int32_t *x,
 		const int grid = (int)(ntiles < cap ? ntiles : cap);
 		with_instance(cfg, kp, [&](auto inst) {
 			typedef decltype(inst) I;
-			hipLaunchKernelGGL((fm_demod_lj<I::nlive, I::dyn, I::ug, I::plain>),
-				dim3(grid), dim3(kBlock), 0, st, kp, (const i32x4g *)x,
-				(const i32x4g *)y, (i32x4g *)mag, (i32x4g *)freq, nvec, ntiles,
-				phase0, d_last);
-		});
+			hipLaunchKernelGGL((fm_demod_lj<I::nlive, I::dyn, I::ug, I::plain, IO>),
+				dim3(grid), dim3(kBlock), 0, st, kp, (const ivec *)x,
+				(const ivec *)y, (ivec *)mag, (ivec *)freq, nvec, ntiles,
+				phase0, (const uint32_t *)d_last);
+		}, IO{});
 		if (int rc = tnco::finish(true))
 			return rc;
 	}
@@ -211,9 +229,9 @@ static int run_fused(const cordic_config &cfg, size_t n, const int32_t *x,
 		(uint32_t)(n - s0), phase0, nvec ? 0u : 1u, 0u};
 	with_instance(cfg, kp, [&](auto inst) {
 		typedef decltype(inst) I;
-		hipLaunchKernelGGL((fm_demod_tail<I::nlive, I::dyn, I::ug, I::plain>), dim3(1),
+		hipLaunchKernelGGL((fm_demod_tail<I::nlive, I::dyn, I::ug, I::plain, IO>), dim3(1),
 			dim3(64), 0, st, kp, tail);
-	});
+	}, IO{});
 	return tnco::finish(true);
 }
 
@@ -274,11 +292,18 @@ static int demod(const cordic_config *cfg, size_t n, const void *x, const void *
 		return CORDIC_ERR_ARGS;
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	uint32_t *work = static_cast<uint32_t *>(d_work);
-	if (io16)
+	if (io16) {
+		// (any 2-byte alignment: the 16-byte condition below is the 32-bit
+		// entry point's own)
+		if (fmd_core_is_fused(*cfg))
+			return run_fused<Io16>(*cfg, n, static_cast<const int16_t *>(x),
+				static_cast<const int16_t *>(y), phase0, d_last,
+				static_cast<int16_t *>(mag), static_cast<int16_t *>(freq), st);
 		return run_fallback<uint16_t>(*cfg, n, x, y, phase0, d_last, mag, freq,
 			work, st);
+	}
 	if (fmd_core_is_fused(*cfg) && !(arrays & 15u))
-		return run_fused(*cfg, n, static_cast<const int32_t *>(x),
+		return run_fused<Io32>(*cfg, n, static_cast<const int32_t *>(x),
 			static_cast<const int32_t *>(y), phase0, d_last,
 			static_cast<int32_t *>(mag), static_cast<int32_t *>(freq), st);
 	return run_fallback<uint32_t>(*cfg, n, x, y, phase0, d_last, mag, freq, work,
@@ -323,6 +348,16 @@ int cordic_fm_demod_info(const cordic_config *cfg, int32_t *fused, int32_t *tile
 	if (tile)
 		*tile = f ? (int32_t)kFmdTile : 0;
 	return CORDIC_OK;
+}
+
+int cordic_fm_demod16_info(const cordic_config *cfg, int32_t *fused, int32_t *tile)
+{
+	using namespace cordic_amd;
+	if (!cfg)
+		return CORDIC_ERR_ARGS;
+	if (cfg->iw > 16 || cfg->ow > 16 || cfg->pw > 16)
+		return CORDIC_ERR_CONTAINER;	// cordic_fm_demod16's order
+	return cordic_fm_demod_info(cfg, fused, tile);
 }
 
 int cordic_fm_demod(const cordic_config *cfg, size_t n, const int32_t *d_xval,

@@ -1,6 +1,7 @@
 // cordic_fm_demod_bank.h -- FM demodulation banks: many cordic_fm_demod jobs of
 // one r2p / sr2p core in at most TWO launches (include/cordic_amd.h, "FM
-// demodulation banks").  The descriptors the host cuts at create, the cutter
+// demodulation banks"), on int32 or on int16 I/Q arrays (cordic_demod_job /
+// cordic_demod_job16).  The descriptors the host cuts at create, the cutter
 // itself -- plain C++ that touches no device, so that a stand-alone program can
 // run it under a sanitizer -- and the launchers of the two kernels that walk
 // the descriptors (cordic_fm_demod_bank.hip).  Host-visible types only.
@@ -24,7 +25,7 @@ namespace cordic_amd {
 // at most P * 256 - 1 of them (P = 1, 2, 4, 8 passes of a 256-thread block, one
 // lane of which converts the halo -- the vector in front of the run -- again).
 struct DemodTile {
-	uint64_t x, y;		// addresses of the run's first input vector
+	uint64_t x, y;		// byte addresses of the run's first input vector
 	uint64_t mag, freq;	// ... and of its first output vector
 	uint64_t last;		// first == 1: the job's d_last, or 0
 	uint32_t nvec;		// vectors: 1 .. P * 256 - 1
@@ -52,26 +53,63 @@ inline int fmd_bank_passes(uint64_t total_vecs, int cus)
 	return (int)bank_passes(total_vecs, cus, 8, kFmdBankPassVecs, 8);
 }
 
-// The argument checks of cordic_demodbank_create that need no device: every
-// job with n > 0 has four non-NULL, 4-byte-aligned sample pointers, an aligned
-// d_last, reserved == 0 and a length within SIZE_MAX >> 4; no output range
-// (d_omag, d_ofreq, the word at d_last) overlaps another output range or any
-// input range of the bank (BankRanges, cordic_bank_host.h).
-inline bool fmd_bank_jobs_valid(size_t njobs, const cordic_demod_job *jobs)
+// The jobs of a create, of either struct: cordic_demod_job16 is
+// cordic_demod_job field for field but for the element type behind the four
+// sample pointers, which the host never dereferences.  jobs[k] is job k as a
+// cordic_demod_job; esize() the bytes of a sample, which is all the checks and
+// the cutter know of the container.  (A plain pointer to either struct
+// converts, so the calls on cordic_demod_job arrays read as they did.)
+struct DemodJobs {
+	const cordic_demod_job *j32 = nullptr;
+	const cordic_demod_job16 *j16 = nullptr;
+	uint64_t es = 4;	// (by the pointer's type: a NULL one still names its container)
+	DemodJobs(const cordic_demod_job *j) : j32(j) {}
+	DemodJobs(const cordic_demod_job16 *j) : j16(j), es(2) {}
+	DemodJobs(std::nullptr_t) {}
+	bool	none() const { return !j32 && !j16; }
+	uint64_t esize() const { return es; }
+	uint64_t n(size_t k) const { return j16 ? j16[k].n : j32[k].n; }
+	cordic_demod_job operator[](size_t k) const
+	{
+		if (!j16)
+			return j32[k];
+		const cordic_demod_job16 &a = j16[k];
+		cordic_demod_job b;
+		b.d_xval = reinterpret_cast<const int32_t *>(a.d_xval);
+		b.d_yval = reinterpret_cast<const int32_t *>(a.d_yval);
+		b.d_omag = reinterpret_cast<int32_t *>(a.d_omag);
+		b.d_ofreq = reinterpret_cast<int32_t *>(a.d_ofreq);
+		b.d_last = a.d_last;
+		b.n = a.n;
+		b.phase0 = a.phase0;
+		b.reserved = a.reserved;
+		return b;
+	}
+};
+
+// The argument checks of cordic_demodbank_create / _create16 that need no
+// device: every job with n > 0 has four non-NULL sample pointers on the grid of
+// their element (4 or 2 bytes), a 4-byte-aligned d_last, reserved == 0 and a
+// length within SIZE_MAX >> 4; no output range (d_omag, d_ofreq, the word at
+// d_last) overlaps another output range or any input range of the bank
+// (BankRanges, cordic_bank_host.h), by the true byte ranges: n * esize.
+inline bool fmd_bank_jobs_valid(size_t njobs, DemodJobs jobs)
 {
+	const uint64_t es = jobs.esize();
 	BankRanges r;
 	for (size_t k = 0; k < njobs; k++) {
-		const cordic_demod_job &jb = jobs[k];
+		const cordic_demod_job jb = jobs[k];
 		if (jb.n == 0)
 			continue;
 		const uintptr_t p[4] = {(uintptr_t)jb.d_xval, (uintptr_t)jb.d_yval,
 			(uintptr_t)jb.d_omag, (uintptr_t)jb.d_ofreq};
 		const uintptr_t l = (uintptr_t)jb.d_last;
-		if (!p[0] || !p[1] || !p[2] || !p[3] || ((p[0] | p[1] | p[2] | p[3] | l) & 3u)
+		if (!p[0] || !p[1] || !p[2] || !p[3]
+				|| ((p[0] | p[1] | p[2] | p[3]) & (es - 1)) || (l & 3u)
 				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
 			return false;
 		for (int i = 0; i < 4; i++)
-			if (!r.add(p[i], jb.n * 4, i >= 2))
+			if (!r.add(p[i], jb.n * es, i >= 2))
 				return false;
 		if (l && !r.add(l, 4, true))
 			return false;
@@ -80,12 +118,11 @@ inline bool fmd_bank_jobs_valid(size_t njobs, const cordic_demod_job *jobs)
 }
 
 // tiles of `tile_vecs` vectors the jobs cut into (saturating at 2^63)
-inline uint64_t fmd_bank_count_tiles(size_t njobs, const cordic_demod_job *jobs,
-		uint32_t tile_vecs)
+inline uint64_t fmd_bank_count_tiles(size_t njobs, DemodJobs jobs, uint32_t tile_vecs)
 {
 	uint64_t t = 0;
 	for (size_t k = 0; k < njobs; k++) {
-		t += (jobs[k].n / 4 + tile_vecs - 1) / tile_vecs;
+		t += (jobs.n(k) / 4 + tile_vecs - 1) / tile_vecs;
 		if (t >> 63)
 			break;
 	}
@@ -93,13 +130,14 @@ inline uint64_t fmd_bank_count_tiles(size_t njobs, const cordic_demod_job *jobs,
 }
 
 // Cuts valid jobs (fmd_bank_jobs_valid) into tiles, in the jobs' order, and
-// tails, one per job that needs the second launch.
-inline void fmd_bank_cut(size_t njobs, const cordic_demod_job *jobs,
-		uint32_t tile_vecs, std::vector<DemodTile> *tiles,
-		std::vector<DemodTail> *tails)
+// tails, one per job that needs the second launch.  The descriptors hold byte
+// addresses: a vector is 4 * esize bytes (16 or 8), a sample esize (4 or 2).
+inline void fmd_bank_cut(size_t njobs, DemodJobs jobs, uint32_t tile_vecs,
+		std::vector<DemodTile> *tiles, std::vector<DemodTail> *tails)
 {
+	const uint64_t es = jobs.esize();
 	for (size_t k = 0; k < njobs; k++) {
-		const cordic_demod_job &jb = jobs[k];
+		const cordic_demod_job jb = jobs[k];
 		if (jb.n == 0)
 			continue;
 		const uint64_t x = (uintptr_t)jb.d_xval, y = (uintptr_t)jb.d_yval,
@@ -108,24 +146,25 @@ inline void fmd_bank_cut(size_t njobs, const cordic_demod_job *jobs,
 		const uint64_t nvec = jb.n / 4;
 		for (uint64_t v0 = 0; v0 < nvec; v0 += tile_vecs) {
 			const uint64_t live = nvec - v0 < tile_vecs ? nvec - v0 : tile_vecs;
-			const uint64_t at = v0 * 16;
+			const uint64_t at = v0 * 4 * es;
 			tiles->push_back(DemodTile{x + at, y + at, m + at, f + at,
 				v0 ? 0 : l, (uint32_t)live, v0 ? 0u : jb.phase0,
 				v0 ? 0u : 1u, 0u});
 		}
 		if (nvec * 4 == jb.n && !l)
 			continue;
-		const uint64_t s0 = nvec ? nvec * 4 - 1 : 0, at = s0 * 4;
+		const uint64_t s0 = nvec ? nvec * 4 - 1 : 0, at = s0 * es;
 		tails->push_back(DemodTail{x + at, y + at, m + at, f + at, l,
 			(uint32_t)(jb.n - s0), jb.phase0, nvec ? 0u : 1u, 0u});
 	}
 }
 
-// The two launches.  grid: blocks of the main kernel (1 .. ntiles).  An empty
-// table launches nothing.  CORDIC_OK or CORDIC_ERR_DEVICE.
+// The two launches.  grid: blocks of the main kernel (1 .. ntiles).  io16: the
+// descriptors were cut from 16-bit jobs.  An empty table launches nothing.
+// CORDIC_OK or CORDIC_ERR_DEVICE.
 int	launch_fmd_bank(const cordic_config &cfg, const DemodTile *d_tiles,
 		uint32_t ntiles, int grid, const DemodTail *d_tails, uint32_t ntails,
-		void *stream);
+		bool io16, void *stream);
 
 } // namespace cordic_amd
 #endif

@@ -892,7 +892,9 @@ int	cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
  *
  * cordic_fm_demod16: the same on int16_t arrays; IW, OW, PW <= 16
  * (CORDIC_ERR_CONTAINER otherwise, the rule of cordic_r2p16); its values are
- * the low 16 bits of the 32-bit form's.
+ * the low 16 bits of the 32-bit form's, and *d_last stays a 32-bit word that
+ * holds the PW-bit phase of sample n - 1.  Bits of an input short above IW are
+ * ignored.
  *
  * Launch contract: the library allocates, copies and synchronises nothing; the
  * call is a fixed, small number of kernel launches on `stream` (at most four),
@@ -907,15 +909,27 @@ int	cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
  *             given, a tail of at most four samples follows in two small
  *             launches.
  *   fallback  everything else (wider cores, cores that wrap, the two flags,
- *             arrays off the 16-byte grid, the 16-bit form): cordic_r2p's
+ *             32-bit arrays off the 16-byte grid): cordic_r2p's
  *             launches with the phases in d_ofreq, one kernel that saves the
  *             last phase of every 4096-sample tile to d_work, one that
  *             differences in place.
+ * cordic_fm_demod16 takes the fused path for the same cores at ANY 2-byte
+ * alignment of its arrays (the 16-byte condition belongs to the 32-bit call
+ * alone): the same kernel on 8-byte vectors -- 8 bytes per sample -- in at
+ * most two launches, the sweep and, where n is no multiple of 4 or d_last is
+ * given, a one-lane tail.  Every other core takes the fallback above on
+ * shorts (cordic_r2p16's launches).  d_work is required and checked on either
+ * path.
  * cordic_fm_demod_info (a pure host function): *fused = 1 if 16-byte-aligned
  * 32-bit arrays of this core take the fused path, else 0; *tile = the samples
  * of output a block of the fused kernel makes at a time (a multiple of 4), 0
  * when not fused; either pointer may be NULL.  CORDIC_ERR_MODE / _ARGS as for
  * the call.
+ * cordic_fm_demod16_info: the same question for cordic_fm_demod16, with that
+ * call's status codes in its order -- CORDIC_ERR_ARGS for a NULL cfg,
+ * CORDIC_ERR_CONTAINER for IW, OW or PW > 16, then CORDIC_ERR_MODE / _ARGS as
+ * above; *fused = 1 if int16 arrays of this core take the fused path, *tile as
+ * above.  Neither word is written on an error.
  *
  * d_work: caller-owned device scratch of at least cordic_fm_demod_workspace(n)
  * bytes, 16-byte aligned, not shared by calls that may run at the same time.
@@ -948,6 +962,8 @@ int	cordic_fm_demod16(const cordic_config *cfg, size_t n,
 		const int16_t *d_xval, const int16_t *d_yval, uint32_t phase0,
 		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work,
 		void *stream);
+int	cordic_fm_demod16_info(const cordic_config *cfg, int32_t *fused,
+		int32_t *tile);
 
 /* FM demodulation banks: many discriminator jobs in one launch.
  *
@@ -996,8 +1012,18 @@ int	cordic_fm_demod16(const cordic_config *cfg, size_t n,
  *               _FORCE_GENERIC): run loops cordic_fm_demod over the jobs on
  *               `stream`, with a scratch area the bank allocated at create for
  *               its longest job; legal inside a capture as well.
- * There is no 16-bit form: cordic_fm_demod16 has no fused kernel that a bank
- * could be the tile form of.
+ *
+ * cordic_demodbank_create16: the bank of cordic_fm_demod16 jobs, on int16 I/Q
+ * arrays.  It returns an ordinary cordic_demodbank that remembers its
+ * container, so _run, _info and _destroy work on it unchanged, and a run gives,
+ * for every job, bit for bit what cordic_fm_demod16 gives.  Everything above
+ * holds, with these differences: the four sample pointers are 2-byte aligned
+ * (d_last stays a 4-byte-aligned word), the byte ranges of the overlap check
+ * are n * 2, and a core with IW, OW or PW > 16 is CORDIC_ERR_CONTAINER (behind
+ * CORDIC_ERR_ARGS for a NULL cfg, bank or jobs and CORDIC_ERR_MODE).  The bank
+ * is fused where cordic_fm_demod16_info answers 1 -- tiles of (P * 256 - 1) * 4
+ * samples of 8-byte vectors, at most two launches -- and otherwise loops
+ * cordic_fm_demod16 over its jobs with the bank's scratch.
  *
  * cordic_demodbank_info (any pointer may be NULL): *samples = the samples of
  * all jobs; *tiles = the tiles the main kernel walks; *tail_jobs = the jobs
@@ -1019,6 +1045,16 @@ void	cordic_demodbank_destroy(cordic_demodbank *bank);
 int	cordic_demodbank_info(const cordic_demodbank *bank, uint64_t *samples,
 		uint32_t *tiles, uint32_t *tail_jobs, int32_t *fused, int32_t *tile);
 int	cordic_demodbank_run(const cordic_demodbank *bank, void *stream);
+typedef struct cordic_demod_job16 {
+	const int16_t *d_xval, *d_yval;	/* n shorts each                         */
+	int16_t	*d_omag, *d_ofreq;	/* n shorts each                         */
+	uint32_t *d_last;		/* optional device word (NULL: none)     */
+	uint64_t n;			/* samples; 0 allowed                    */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                     */
+} cordic_demod_job16;			/* 56 bytes                              */
+int	cordic_demodbank_create16(const cordic_config *cfg, size_t njobs,
+		const cordic_demod_job16 *jobs, cordic_demodbank **bank);
 
 /* -------------------------------------------------------------- FM mixer
  *

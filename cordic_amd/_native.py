@@ -351,6 +351,21 @@ ABI = {
     "cordic_oscbank_run": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "cordic_oscbank_retune": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t,
                                         C.c_void_p, C.c_void_p]),
+    "cordic_table_fmbank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.POINTER(C.c_void_p)]),
+    "cordic_table_fmbank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                               C.c_void_p,
+                                               C.POINTER(C.c_void_p)]),
+    "cordic_quad_fmbank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.POINTER(C.c_void_p)]),
+    "cordic_quad_fmbank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                              C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
+    "cordic_fmbank_destroy": (None, [C.c_void_p]),
+    "cordic_fmbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_int32)]),
+    "cordic_fmbank_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cordic_p2r_host": (C.c_int, [_cfgp, C.c_size_t, _i32p, _i32p, C.c_int,
                                   _u32p, _i32p, _i32p]),
     "cordic_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
@@ -1187,6 +1202,67 @@ class OscBank:
             pass
 
 
+class _CFmOscJob(C.Structure):
+    """cordic_fmosc_job / cordic_fmosc_job16 (the same layout)"""
+    _fields_ = [("d_fcw", C.c_void_p), ("d_pm", C.c_void_p),
+                ("d_sin", C.c_void_p), ("d_cos", C.c_void_p),
+                ("d_acc", C.c_void_p), ("n", C.c_uint64),
+                ("phase0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_FMOSC_KEYS = ("fcw", "pm", "sin", "cos", "n", "phase0", "acc")
+
+
+class FmBank:
+    """cordic_fmbank: many fm jobs of one Table / Quad core, cut once and run
+    in two launches.  jobs: tuples (fcw, pm, sin, cos, n, phase0, acc) or dicts
+    with those keys; fcw is an int32 tensor or a device address, pm one more or
+    None, sin / cos int32 tensors (int16 with i16) or device addresses, cos
+    None: sine only, acc a one-word device tensor or None; n None:
+    fcw.numel().  The core must stay open as long as the bank."""
+
+    def __init__(self, core, fn, jobs, i16=False):
+        jobs = [tuple(jb.get(k) for k in _FMOSC_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = (core, jobs)   # the core and the tensors behind the addresses
+        arr = (_CFmOscJob * max(1, len(jobs)))()
+        for k, (fcw, pm, sin, cos, n, phase0, acc) in enumerate(jobs):
+            if i16:
+                _same16(fn + "16", sin, cos)
+            arr[k].d_fcw = _ptr(fcw)
+            arr[k].d_pm = _ptr(pm)
+            arr[k].d_sin = _ptr(sin)
+            arr[k].d_cos = _ptr(cos)
+            arr[k].d_acc = _ptr(acc)
+            arr[k].n = fcw.numel() if n is None else n
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+        fn += "16" if i16 else ""
+        h = C.c_void_p()
+        _check(getattr(lib(), fn)(core._h, len(jobs), arr, C.byref(h)), fn)
+        self._h = h
+
+    def info(self):
+        a, b, c = C.c_uint64(), C.c_uint32(), C.c_int32()
+        _check(lib().cordic_fmbank_info(self._h, C.byref(a), C.byref(b),
+                                        C.byref(c)), "cordic_fmbank_info")
+        return dict(samples=a.value, spans=b.value, tile=c.value)
+
+    def run(self, stream=None):
+        _check(lib().cordic_fmbank_run(self._h, _stream(stream)),
+               "cordic_fmbank_run")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cordic_fmbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Table:
     """A -t tbl / -t qtr core: cordic_table_config + its device table."""
 
@@ -1249,6 +1325,10 @@ class Table:
     def bank(self, jobs, i16=False):
         """cordic_table_bank_create(16): the jobs as one OscBank"""
         return OscBank(self, "cordic_table_bank_create", jobs, i16)
+
+    def fm_bank(self, jobs, i16=False):
+        """cordic_table_fmbank_create(16): the fm jobs as one FmBank"""
+        return FmBank(self, "cordic_table_fmbank_create", jobs, i16)
 
     def close(self):
         if self._h:
@@ -1335,6 +1415,10 @@ class Quad:
     def bank(self, jobs, i16=False):
         """cordic_quad_bank_create(16): the jobs as one OscBank"""
         return OscBank(self, "cordic_quad_bank_create", jobs, i16)
+
+    def fm_bank(self, jobs, i16=False):
+        """cordic_quad_fmbank_create(16): the fm jobs as one FmBank"""
+        return FmBank(self, "cordic_quad_fmbank_create", jobs, i16)
 
     def close(self):
         if self._h:

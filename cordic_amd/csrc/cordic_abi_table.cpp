@@ -1,10 +1,13 @@
 // cordic_abi_table.cpp -- the C ABI's table-driven sine cores on the device:
 // table and quadratic handles, their lookups and oscillators (the modulated
-// ones included), and the oscillator banks cut for them (include/cordic_amd.h;
+// ones included), and the oscillator banks and FM oscillator banks cut for them
+// (include/cordic_amd.h;
 // the cores' host side: cordic_abi.cpp).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cstddef>
+#include <cstdlib>
 #include <new>
 #include <vector>
 
@@ -14,6 +17,7 @@
 #include "cordic_queue_ring.h"
 #include "cordic_table_bank.h"
 #include "cordic_table_fm.h"
+#include "cordic_table_fm_bank.h"
 #include "cordic_table_nco.h"
 
 using namespace cordic_amd;
@@ -585,4 +589,140 @@ int cordic_oscbank_retune(cordic_oscbank *bank, size_t first, size_t count,
 		return CORDIC_ERR_DEVICE;
 	}
 	return CORDIC_OK;
+}
+
+// ---------------------------------------------------- FM oscillator banks
+// Many modulated oscillator jobs of one table / quadratic core in two launches
+// (include/cordic_amd.h, "FM oscillator banks"; the cutter and the kernels:
+// cordic_table_fm_bank.h, cordic_table_fm_bank.hip).  There is no one-by-one
+// path: every core the single call serves is served from the span table.
+struct cordic_fmbank {
+	SineCore core;		// the handle's: it must outlive the bank
+	int	device = -1, cus = 0;	// (cus: of the device, at create)
+	bool	io16 = false;		// the jobs' outputs hold int16
+	uint64_t samples = 0;
+	uint32_t tiles = 0;		// T, the tiles of a base span
+	// the span table and the workspace, [start words | partials]
+	FmSpan	*d_spans = nullptr;
+	uint32_t *d_words = nullptr;
+	uint32_t nspans = 0, nstarts = 0;
+};
+
+namespace {
+// all four creates: `h` is the table or quadratic handle, `jobs` either job
+// struct (FmJobs, cordic_table_fm_bank.h)
+template <typename H>
+int fmbank_create(const H *h, size_t njobs, FmJobs jobs, cordic_fmbank **bank)
+{
+	const bool io16 = jobs.esize() == 2;
+	if (!h || !bank || (njobs && !jobs.j32 && !jobs.j16))
+		return CORDIC_ERR_ARGS;
+	const SineCore core = h->core();
+	if (io16 && core.ow() > 16)
+		return CORDIC_ERR_CONTAINER;
+	if (core.quad && core.lds_bytes() > 64 * 1024)
+		return CORDIC_ERR_UNSUPPORTED;
+	if (!core.sane() || njobs >= ((size_t)1 << 28) || !fmob_jobs_valid(njobs, jobs))
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	if (legacy_stream_capturing())	// (blocking uploads below)
+		return CORDIC_ERR_UNSUPPORTED;
+	uint64_t samples = 0, tiles = 0;
+	for (size_t k = 0; k < njobs; k++) {
+		samples += jobs.n(k) * (jobs.n(k) && jobs.quadrature(k) ? 2u : 1u);
+		tiles += fmob_tiles_of(jobs.n(k));
+	}
+	const int cus = cus_or_256();
+	int per_cu = 1;
+	if (tiles)
+		if (int rc = fmob_resident(core, io16, &per_cu))
+			return rc;
+	const uint32_t base = fmob_forced_tiles(std::getenv("CORDIC_FMOB_TILES"),
+			fmob_tiles(tiles, cus, per_cu));
+	const uint32_t cap = fmob_forced_cap(std::getenv("CORDIC_FMOB_MAX_SPANS"));
+	if (fmob_count_spans(njobs, jobs, base, cap) > 0xffffffffull)
+		return CORDIC_ERR_ARGS;
+	cordic_fmbank *b = new (std::nothrow) cordic_fmbank;
+	if (!b)
+		return CORDIC_ERR_NOMEM;
+	b->core = core;
+	b->device = current_device();
+	b->cus = cus;
+	b->io16 = io16;
+	b->samples = samples;
+	b->tiles = base;
+	std::vector<FmSpan> spans;
+	fmob_cut(njobs, jobs, base, cap, &spans, &b->nstarts);
+	b->nspans = (uint32_t)spans.size();
+	if (!dev_upload(spans.data(), spans.size() * sizeof(FmSpan), &b->d_spans)
+			|| !dev_zalloc(&b->d_words,
+				((size_t)b->nstarts + b->nspans) * sizeof(uint32_t))) {
+		cordic_fmbank_destroy(b);
+		return CORDIC_ERR_DEVICE;
+	}
+	*bank = b;
+	return CORDIC_OK;
+}
+
+static_assert(sizeof(cordic_fmosc_job) == 56
+	&& sizeof(cordic_fmosc_job16) == sizeof(cordic_fmosc_job)
+	&& offsetof(cordic_fmosc_job16, d_sin) == offsetof(cordic_fmosc_job, d_sin)
+	&& offsetof(cordic_fmosc_job16, d_cos) == offsetof(cordic_fmosc_job, d_cos)
+	&& offsetof(cordic_fmosc_job16, d_acc) == offsetof(cordic_fmosc_job, d_acc)
+	&& offsetof(cordic_fmosc_job16, n) == offsetof(cordic_fmosc_job, n),
+	"cordic_fmosc_job16 is cordic_fmosc_job with 16-bit output pointers");
+} // namespace
+
+int cordic_table_fmbank_create(const cordic_table *tbl, size_t njobs,
+		const cordic_fmosc_job *jobs, cordic_fmbank **bank)
+{
+	return fmbank_create(tbl, njobs, jobs, bank);
+}
+
+int cordic_table_fmbank_create16(const cordic_table *tbl, size_t njobs,
+		const cordic_fmosc_job16 *jobs, cordic_fmbank **bank)
+{
+	return fmbank_create(tbl, njobs, jobs, bank);
+}
+
+int cordic_quad_fmbank_create(const cordic_quad *core, size_t njobs,
+		const cordic_fmosc_job *jobs, cordic_fmbank **bank)
+{
+	return fmbank_create(core, njobs, jobs, bank);
+}
+
+int cordic_quad_fmbank_create16(const cordic_quad *core, size_t njobs,
+		const cordic_fmosc_job16 *jobs, cordic_fmbank **bank)
+{
+	return fmbank_create(core, njobs, jobs, bank);
+}
+
+void cordic_fmbank_destroy(cordic_fmbank *bank)
+{
+	if (!bank)
+		return;
+	dev_free(bank->d_spans, bank->d_words);
+	delete bank;
+}
+
+int cordic_fmbank_info(const cordic_fmbank *bank, uint64_t *samples,
+		uint32_t *spans, int32_t *tile)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	if (samples) *samples = bank->samples;
+	if (spans) *spans = bank->nspans;
+	if (tile) *tile = (int32_t)(bank->tiles * kFmobTile);
+	return CORDIC_OK;
+}
+
+int cordic_fmbank_run(const cordic_fmbank *bank, void *stream)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();
+	if (int rc = device_is_current(bank->device))
+		return rc;
+	return launch_fmosc_bank(bank->core, bank->d_spans, bank->nspans, bank->d_words,
+		bank->d_words + bank->nstarts, bank->cus, bank->io16, stream);
 }

@@ -19,6 +19,8 @@
 //      block writes *d_acc.
 // No block ever waits for another: what a block needs of the others is
 // complete when launch 2 starts.  The price is a second read of fcw.
+// The walk over a block's tiles is tile_loop (cordic_table_fm.h), which the
+// FM oscillator banks' kernel (cordic_table_fm_bank.hip) runs as well.
 //
 // *d_acc is read in launch 1 only and written in launch 2 only, so no block
 // of a call can see the value the call itself writes.
@@ -52,15 +54,6 @@ namespace tfm {
 
 using namespace tnco;
 
-constexpr int kTile = (int)kFmTile;
-// the phases of a tile behind the last 8 of the tile before it
-constexpr size_t kPhaseBytes = (size_t)(8 + kTile) * sizeof(uint32_t);
-
-// four consecutive words at any 4-byte-aligned address: one dwordx4 access
-struct __attribute__((packed, aligned(4))) Words4 {
-	uint32_t v[4];
-};
-
 // the phase as a core of its own: cordic_phase_accumulate's output
 struct CoreIdent {
 	typedef int32_t entry;
@@ -70,24 +63,6 @@ struct CoreIdent {
 		return (int32_t)ph;
 	}
 };
-
-// sum of v over the block's 1024 threads, in every thread; wsum: 16 words of
-// LDS that are free again when the call returns
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wsum)
-{
-#pragma unroll
-	for (int d = 32; d; d >>= 1)
-		v += __shfl_xor(v, d);
-	if ((threadIdx.x & 63u) == 0)
-		wsum[threadIdx.x >> 6] = v;
-	__syncthreads();
-	uint32_t s = 0;
-#pragma unroll
-	for (int j = 0; j < 16; j++)
-		s += wsum[j];
-	__syncthreads();
-	return s;
-}
 
 // launch 1: work[4 + b] = the sum of block b's span [b * span, (b + 1) * span)
 // of fcw (cut at n), work[0] = phase0 + *d_acc.  The span is read on fcw's own
@@ -142,16 +117,11 @@ template <typename CORE, typename T>
 __global__ __launch_bounds__(1024) void table_fm(CORE core, FmArgs a, T *d_sin,
 		T *d_cos)
 {
-	typedef typename OutVec<T>::type V;
-	constexpr int W = 16 / sizeof(T);
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	__shared__ uint32_t wsum[16];
-	const unsigned tid = threadIdx.x, lane = tid & 63u;
-	// (the same in all of a wave's lanes: said so, it stays in a scalar)
-	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+	const unsigned tid = threadIdx.x;
 	const typename CORE::entry *tab = core.stage(lds_raw);
-	// ph[8 + j]: the phase of sample t0 + j of the current tile; ph[0 .. 8):
-	// the last 8 phases of the tile before it
+	// the tile's phases behind the table (tile_loop, cordic_table_fm.h)
 	uint32_t *ph = reinterpret_cast<uint32_t *>(lds_raw + a.table_bytes);
 
 	const size_t lo = (size_t)blockIdx.x * a.span;	// < n by the grid
@@ -160,125 +130,7 @@ __global__ __launch_bounds__(1024) void table_fm(CORE core, FmArgs a, T *d_sin,
 	uint32_t carry = a.work[0]
 		+ block_sum(tid < blockIdx.x ? a.work[4 + tid] : 0u, wsum);
 
-	// this lane's 4 words of the tile at t0; nothing at or behind hi is read
-	auto load_tile = [&](size_t t0, uint32_t (&f)[4], uint32_t (&m)[4]) {
-		const size_t i = t0 + 4 * (size_t)tid;
-		if (i + 4 <= hi) {
-			const Words4 q = *reinterpret_cast<const Words4 *>(a.fcw + i);
-#pragma unroll
-			for (int k = 0; k < 4; k++)
-				f[k] = q.v[k];
-			if (a.pm) {
-				const Words4 r = *reinterpret_cast<const Words4 *>(a.pm + i);
-#pragma unroll
-				for (int k = 0; k < 4; k++)
-					m[k] = r.v[k];
-			} else {
-#pragma unroll
-				for (int k = 0; k < 4; k++)
-					m[k] = 0u;
-			}
-		} else {
-#pragma unroll
-			for (int k = 0; k < 4; k++) {
-				const bool in = i + k < hi;
-				f[k] = in ? a.fcw[i + k] : 0u;
-				m[k] = (in && a.pm) ? a.pm[i + k] : 0u;
-			}
-		}
-	};
-
-	// one stream's window of the tile [t0, t1): see the head of this file
-	auto emit = [&](T *out, uint32_t lead, size_t t0, size_t t1) {
-		const size_t w0 = (t0 == lo) ? lo
-			: t0 - (size_t)(reinterpret_cast<uintptr_t>(out + t0) & 15u) / sizeof(T);
-		const size_t w1 = (t1 == hi) ? hi
-			: t1 - (size_t)(reinterpret_cast<uintptr_t>(out + t1) & 15u) / sizeof(T);
-		size_t h = head_elems(reinterpret_cast<uintptr_t>(out + w0), sizeof(T));
-		if (h > w1 - w0)
-			h = w1 - w0;
-		// At most 4096 / W vectors, so one per thread covers them.  Behind a
-		// span's first tile out + t0 and out + t1 = out + t0 + 4096 sit alike
-		// on the 16-byte grid: the window is moved back, not widened, and is
-		// 4096 samples (shorter in the last tile).  The first tile has nothing
-		// in front of t0: at most 4096 samples again, less its head.
-		const size_t nv = (w1 - w0 - h) / W;
-		const size_t tail = w0 + h + nv * W;
-		// pw[i] for a sample index i in [t0 - 8, t1)
-		auto phase_of = [&](size_t i) -> uint32_t {
-			return ph[8 + ((ptrdiff_t)i - (ptrdiff_t)t0)];
-		};
-		if (tid < nv) {
-			const size_t e = w0 + h + (size_t)tid * W;
-			const uint32_t *pp = ph + (8 + ((ptrdiff_t)e - (ptrdiff_t)t0));
-			uint32_t q[W];
-			if ((reinterpret_cast<uintptr_t>(pp) & 15u) == 0) {
-				// (uniform: the stream sits on the tile grid)
-#pragma unroll
-				for (int v = 0; v < W; v += 4) {
-					const uint4 r = *reinterpret_cast<const uint4 *>(pp + v);
-					q[v] = r.x; q[v + 1] = r.y; q[v + 2] = r.z; q[v + 3] = r.w;
-				}
-			} else {
-#pragma unroll
-				for (int v = 0; v < W; v++)
-					q[v] = pp[v];
-			}
-			V o;
-#pragma unroll
-			for (int v = 0; v < W; v++)
-				o[v] = (T)core.sample(tab, q[v] + lead);
-			__builtin_nontemporal_store(o, reinterpret_cast<V *>(out + e));
-		}
-		// fewer than W samples each, and only in a span's first / last tile
-		if (tid < h)
-			out[w0 + tid] = (T)core.sample(tab, phase_of(w0 + tid) + lead);
-		if (tid < w1 - tail)
-			out[tail + tid] = (T)core.sample(tab, phase_of(tail + tid) + lead);
-	};
-
-	uint32_t f[4], m[4];
-	load_tile(lo, f, m);
-	for (size_t t0 = lo; t0 < hi; t0 += kTile) {
-		const size_t t1 = (hi - t0 < (size_t)kTile) ? hi : t0 + kTile;
-		// inclusive sums: in the lane, then over the wave's lanes
-		const uint32_t s0 = f[0], s1 = s0 + f[1], s2 = s1 + f[2], s3 = s2 + f[3];
-		uint32_t incl = s3;
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const uint32_t up = __shfl_up(incl, d);
-			if (lane >= (unsigned)d)
-				incl += up;
-		}
-		if (lane == 63)
-			wsum[wave] = incl;
-		__syncthreads();
-		// the waves in front of this one, and the tile's total
-		uint32_t front = 0, total = 0;
-#pragma unroll
-		for (unsigned j = 0; j < 16; j++) {
-			const uint32_t w = wsum[j];
-			front += (j < wave) ? w : 0u;
-			total += w;
-		}
-		const uint32_t excl = carry + front + incl - s3;
-		// Every lane rewrites its own 4 phases only, and the readers of the
-		// tile before are past the barrier above: the owners of the last 8
-		// move theirs to the front first.  (The first tile of a span never
-		// looks in front of itself.)
-		uint4 *mine = reinterpret_cast<uint4 *>(ph + 8 + 4 * tid);
-		if (tid >= 1022)
-			*reinterpret_cast<uint4 *>(ph + 4 * (tid - 1022)) = *mine;
-		*mine = make_uint4(excl + m[0], excl + s0 + m[1], excl + s1 + m[2],
-			excl + s2 + m[3]);
-		carry += total;
-		__syncthreads();
-		// the next tile's words are on their way while this one is sampled
-		load_tile(t0 + kTile, f, m);
-		emit(d_sin, 0u, t0, t1);
-		if (d_cos)
-			emit(d_cos, a.quarter, t0, t1);
-	}
+	tile_loop<CORE, T>(core, tab, ph, wsum, a, d_sin, d_cos, lo, hi, carry);
 	if (a.acc && blockIdx.x == gridDim.x - 1 && tid == 0)
 		*a.acc = carry;
 }

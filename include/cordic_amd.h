@@ -862,6 +862,103 @@ int	cordic_quad_fm16(const cordic_quad *core, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
 		int16_t *d_sin, int16_t *d_cos, void *d_work, void *stream);
 
+/* FM oscillator banks: many modulated oscillator jobs in two launches.
+ *
+ * What oscillator banks are to cordic_table_nco, for cordic_table_fm /
+ * cordic_quad_fm: the transmit half of a channelised FM link -- a bank of FSK
+ * or chirp generators, the LO bank of an AFC loop whose tuning words come from
+ * a loop filter.  Hundreds or thousands of SHORT blocks of ONE core, each with
+ * its own tuning-word array, optional phase-word array, outputs, length,
+ * phase0 and optional d_acc, are described once; one cordic_fmbank_run then
+ * gives, for every job with n > 0, bit for bit what
+ *   cordic_table_fm(tbl, n, d_fcw, d_pm, phase0, d_acc, d_sin, d_cos, work,
+ *                   stream)
+ * (cordic_quad_fm for a bank of a quadratic core; the ...16 form for a bank
+ * made by a ...create16) gives -- *d_acc afterwards (all 32 bits, pm not in
+ * it) and the rule that phase0 is added by every run included.  So a bank
+ * whose jobs have a d_acc and phase0 == 0, run k times on new tuning words in
+ * the same arrays, continues every waveform k times with no host work in
+ * between, and a captured run replayed k times continues k times.
+ *
+ * Sine-only (d_cos NULL) and quadrature jobs, and jobs with and without d_pm
+ * or d_acc, may be mixed in one bank; lengths may be ragged, zero included (a
+ * zero-length job's pointers are not looked at).  d_fcw, d_pm and d_acc are
+ * 4-byte aligned; d_sin and d_cos 4-byte, in the 16-bit forms 2-byte, each
+ * array on its own alignment.  Nothing outside [0, n) of any output is
+ * written.
+ *
+ * Create is host work with blocking uploads: CORDIC_ERR_UNSUPPORTED while the
+ * legacy stream is being captured, as cordic_mixbank_create.  The bank REFERS
+ * to the core handle (destroy the bank first) and belongs to the device that
+ * was current at create: CORDIC_ERR_ARGS from run on another device.  The bank
+ * owns its device memory, allocated at create: the span table and a workspace
+ * of one word per non-empty job plus one per span.  Run allocates, copies and
+ * synchronises nothing.  Two runs of ONE bank must not be in flight at the
+ * same time (the workspace is the d_work of the single call).
+ *
+ * CORDIC_ERR_ARGS for a NULL core or bank pointer, NULL jobs with njobs > 0,
+ * 2^28 or more jobs, 2^32 or more spans, and for a job with n > 0: a NULL
+ * d_fcw or d_sin, a pointer off its grid, reserved != 0, n beyond SIZE_MAX >>
+ * 4.  No output range of the bank -- every job's d_sin, d_cos and the 4 bytes
+ * at its d_acc -- may overlap another output range or any job's input range
+ * (CORDIC_ERR_ARGS, found by sorting the true byte ranges; two jobs sharing a
+ * d_acc is such an overlap); inputs may alias each other.
+ * CORDIC_ERR_CONTAINER: a 16-bit create on a core with OW > 16 (behind the
+ * NULL checks).  CORDIC_ERR_UNSUPPORTED: a quadratic core whose tables exceed
+ * 64 KiB, as cordic_quad_fm.  njobs == 0 or all-empty jobs give a valid bank
+ * whose run launches nothing.
+ *
+ * There is one path: every core the single call serves is served fused, on
+ * the layout the single call would take (a table that does not fit LDS beside
+ * a tile's phases is gathered from L2).  Every job is cut into spans of whole
+ * 4096-sample tiles, never across a job's end -- T tiles by the bank's size, T
+ * = 1, 2, 4, ...; a job that would have more than 1024 spans gets longer ones
+ * -- and run is exactly TWO kernel launches on `stream`, or none for an empty
+ * bank: a reduction of the tuning words per span, then the scan with the core
+ * behind it walking the spans.  No block waits for another; no tile queue is
+ * taken, so the cordic_*_queue_info counters do not move; legal inside a
+ * stream capture.  Every *d_acc is read in the first launch only and written
+ * in the second only.
+ *
+ * cordic_fmbank_info (any pointer may be NULL): *samples = the samples of all
+ * jobs, a quadrature job counting twice as in cordic_oscbank_info; *spans =
+ * the spans the second launch walks; *tile = the samples of a full span of the
+ * bank's base size, T * 4096.  cordic_fmbank_info and _run return
+ * CORDIC_ERR_ARGS for a NULL bank and write nothing through the out-pointers;
+ * cordic_fmbank_destroy(NULL) does nothing.
+ */
+typedef struct cordic_fmosc_job {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	int32_t	*d_sin, *d_cos;		/* n words each; d_cos NULL: sine only  */
+	uint32_t *d_acc;		/* optional device word (NULL: none)    */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                    */
+} cordic_fmosc_job;			/* 56 bytes                             */
+typedef struct cordic_fmosc_job16 {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	int16_t	*d_sin, *d_cos;		/* n shorts each; d_cos NULL: sine only */
+	uint32_t *d_acc;		/* optional device word (NULL: none)    */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0;
+	uint32_t reserved;		/* 0                                    */
+} cordic_fmosc_job16;			/* 56 bytes                             */
+typedef struct cordic_fmbank cordic_fmbank;
+int	cordic_table_fmbank_create(const cordic_table *tbl, size_t njobs,
+		const cordic_fmosc_job *jobs, cordic_fmbank **bank);
+int	cordic_table_fmbank_create16(const cordic_table *tbl, size_t njobs,
+		const cordic_fmosc_job16 *jobs, cordic_fmbank **bank);
+int	cordic_quad_fmbank_create(const cordic_quad *core, size_t njobs,
+		const cordic_fmosc_job *jobs, cordic_fmbank **bank);
+int	cordic_quad_fmbank_create16(const cordic_quad *core, size_t njobs,
+		const cordic_fmosc_job16 *jobs, cordic_fmbank **bank);
+void	cordic_fmbank_destroy(cordic_fmbank *bank);
+int	cordic_fmbank_info(const cordic_fmbank *bank, uint64_t *samples,
+		uint32_t *spans, int32_t *tile);
+int	cordic_fmbank_run(const cordic_fmbank *bank, void *stream);
+
 /* ------------------------------------------------------- FM demodulation
  *
  * The receive half of the block above: the converter (cordic_r2p) with its

@@ -267,18 +267,15 @@ struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
 	bool	io16 = false;			// the jobs' sample arrays hold int16
 	uint32_t passes = 0;
-	// fused: the span table and the workspace, [start words | partials]
-	MixSpan	*d_spans = nullptr;
-	uint32_t *d_words = nullptr;
-	uint32_t nspans = 0, nstarts = 0;
+	SpanTable<MixSpan> spans;		// fused
 };
 
 // both creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h)
 static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
 		cordic_mixbank **bank)
 {
-	const bool io16 = jobs.esize() == 2;
-	if (!bank || (njobs && !jobs.j32 && !jobs.j16))
+	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
+	if (!bank || (njobs && jobs.none()))
 		return CORDIC_ERR_ARGS;
 	if (int rc = io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan))
 		return rc;
@@ -308,22 +305,12 @@ static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
 	}
 	uint64_t passes = 0;
 	for (size_t k = 0; k < njobs; k++)
-		passes += fmxb_passes_of(jobs[k].n);
-	b->passes = fmxb_forced_passes(std::getenv("CORDIC_FMXB_PASSES"),
-			fmxb_passes(passes, b->cus));
-	const uint32_t cap = fmxb_forced_cap(std::getenv("CORDIC_FMXB_MAX_SPANS"));
-	if (fmxb_count_spans(njobs, jobs, b->passes, cap) > 0xffffffffull) {
-		delete b;
-		return CORDIC_ERR_ARGS;
-	}
-	std::vector<MixSpan> spans;
-	fmxb_cut(njobs, jobs, b->passes, cap, &spans, &b->nstarts);
-	b->nspans = (uint32_t)spans.size();
-	if (!dev_upload(spans.data(), spans.size() * sizeof(MixSpan), &b->d_spans)
-			|| !dev_zalloc(&b->d_words,
-				((size_t)b->nstarts + b->nspans) * sizeof(uint32_t))) {
+		passes += span_units_of(kFmxbRule, jobs.n(k));
+	if (int rc = span_table_build(&b->spans, "CORDIC_FMXB_PASSES",
+			"CORDIC_FMXB_MAX_SPANS", kFmxbRule, passes, b->cus, kFmxbBlocksPerCu,
+			njobs, jobs, &b->passes)) {
 		cordic_mixbank_destroy(b);
-		return CORDIC_ERR_DEVICE;
+		return rc;
 	}
 	*bank = b;
 	return CORDIC_OK;
@@ -338,11 +325,6 @@ int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
 int cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
 		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
 {
-	static_assert(sizeof(cordic_fmmix_job16) == sizeof(cordic_fmmix_job)
-		&& offsetof(cordic_fmmix_job16, d_xval) == offsetof(cordic_fmmix_job, d_xval)
-		&& offsetof(cordic_fmmix_job16, d_oyval) == offsetof(cordic_fmmix_job, d_oyval)
-		&& offsetof(cordic_fmmix_job16, n) == offsetof(cordic_fmmix_job, n),
-		"cordic_fmmix_job16 is cordic_fmmix_job with 16-bit sample pointers");
 	return mixbank_create(plan, njobs, jobs, bank);
 }
 
@@ -350,7 +332,8 @@ void cordic_mixbank_destroy(cordic_mixbank *bank)
 {
 	if (!bank)
 		return;
-	dev_free(bank->d_spans, bank->d_words, bank->d_work);
+	bank->spans.free();
+	dev_free(bank->d_work);
 	delete bank;
 }
 
@@ -360,9 +343,9 @@ int cordic_mixbank_info(const cordic_mixbank *bank, uint64_t *samples,
 	if (!bank)
 		return CORDIC_ERR_ARGS;
 	if (samples) *samples = bank->samples;
-	if (spans) *spans = bank->nspans;
+	if (spans) *spans = bank->spans.nspans;
 	if (fused) *fused = bank->fused ? 1 : 0;
-	if (tile) *tile = bank->fused ? (int32_t)(bank->passes * kFmxbPass) : 0;
+	if (tile) *tile = bank->fused ? (int32_t)(bank->passes * kFmxbRule.unit) : 0;
 	return CORDIC_OK;
 }
 
@@ -373,9 +356,9 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 	(void)hipGetLastError();
 	const cordic_plan *plan = bank->plan;
 	return bank_run(*bank, [&] {
-		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_spans,
-			bank->nspans, bank->d_words, bank->d_words + bank->nstarts, bank->cus,
-			bank->io16, stream);
+		const SpanTable<MixSpan> &t = bank->spans;
+		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, t.d_spans, t.nspans,
+			t.start(), t.part(), bank->cus, bank->io16, stream);
 	}, [&](const cordic_fmmix_job &jb) {
 		if (bank->io16)
 			return cordic_plan_fm_mix16(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm,

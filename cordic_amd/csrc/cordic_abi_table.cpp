@@ -602,10 +602,7 @@ struct cordic_fmbank {
 	bool	io16 = false;		// the jobs' outputs hold int16
 	uint64_t samples = 0;
 	uint32_t tiles = 0;		// T, the tiles of a base span
-	// the span table and the workspace, [start words | partials]
-	FmSpan	*d_spans = nullptr;
-	uint32_t *d_words = nullptr;
-	uint32_t nspans = 0, nstarts = 0;
+	SpanTable<FmSpan> spans;
 };
 
 namespace {
@@ -614,8 +611,8 @@ namespace {
 template <typename H>
 int fmbank_create(const H *h, size_t njobs, FmJobs jobs, cordic_fmbank **bank)
 {
-	const bool io16 = jobs.esize() == 2;
-	if (!h || !bank || (njobs && !jobs.j32 && !jobs.j16))
+	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
+	if (!h || !bank || (njobs && jobs.none()))
 		return CORDIC_ERR_ARGS;
 	const SineCore core = h->core();
 	if (io16 && core.ow() > 16)
@@ -630,18 +627,13 @@ int fmbank_create(const H *h, size_t njobs, FmJobs jobs, cordic_fmbank **bank)
 	uint64_t samples = 0, tiles = 0;
 	for (size_t k = 0; k < njobs; k++) {
 		samples += jobs.n(k) * (jobs.n(k) && jobs.quadrature(k) ? 2u : 1u);
-		tiles += fmob_tiles_of(jobs.n(k));
+		tiles += span_units_of(kFmobRule, jobs.n(k));
 	}
 	const int cus = cus_or_256();
 	int per_cu = 1;
 	if (tiles)
 		if (int rc = fmob_resident(core, io16, &per_cu))
 			return rc;
-	const uint32_t base = fmob_forced_tiles(std::getenv("CORDIC_FMOB_TILES"),
-			fmob_tiles(tiles, cus, per_cu));
-	const uint32_t cap = fmob_forced_cap(std::getenv("CORDIC_FMOB_MAX_SPANS"));
-	if (fmob_count_spans(njobs, jobs, base, cap) > 0xffffffffull)
-		return CORDIC_ERR_ARGS;
 	cordic_fmbank *b = new (std::nothrow) cordic_fmbank;
 	if (!b)
 		return CORDIC_ERR_NOMEM;
@@ -650,27 +642,15 @@ int fmbank_create(const H *h, size_t njobs, FmJobs jobs, cordic_fmbank **bank)
 	b->cus = cus;
 	b->io16 = io16;
 	b->samples = samples;
-	b->tiles = base;
-	std::vector<FmSpan> spans;
-	fmob_cut(njobs, jobs, base, cap, &spans, &b->nstarts);
-	b->nspans = (uint32_t)spans.size();
-	if (!dev_upload(spans.data(), spans.size() * sizeof(FmSpan), &b->d_spans)
-			|| !dev_zalloc(&b->d_words,
-				((size_t)b->nstarts + b->nspans) * sizeof(uint32_t))) {
+	if (int rc = span_table_build(&b->spans, "CORDIC_FMOB_TILES",
+			"CORDIC_FMOB_MAX_SPANS", kFmobRule, tiles, cus, per_cu, njobs, jobs,
+			&b->tiles)) {
 		cordic_fmbank_destroy(b);
-		return CORDIC_ERR_DEVICE;
+		return rc;
 	}
 	*bank = b;
 	return CORDIC_OK;
 }
-
-static_assert(sizeof(cordic_fmosc_job) == 56
-	&& sizeof(cordic_fmosc_job16) == sizeof(cordic_fmosc_job)
-	&& offsetof(cordic_fmosc_job16, d_sin) == offsetof(cordic_fmosc_job, d_sin)
-	&& offsetof(cordic_fmosc_job16, d_cos) == offsetof(cordic_fmosc_job, d_cos)
-	&& offsetof(cordic_fmosc_job16, d_acc) == offsetof(cordic_fmosc_job, d_acc)
-	&& offsetof(cordic_fmosc_job16, n) == offsetof(cordic_fmosc_job, n),
-	"cordic_fmosc_job16 is cordic_fmosc_job with 16-bit output pointers");
 } // namespace
 
 int cordic_table_fmbank_create(const cordic_table *tbl, size_t njobs,
@@ -701,7 +681,7 @@ void cordic_fmbank_destroy(cordic_fmbank *bank)
 {
 	if (!bank)
 		return;
-	dev_free(bank->d_spans, bank->d_words);
+	bank->spans.free();
 	delete bank;
 }
 
@@ -711,8 +691,8 @@ int cordic_fmbank_info(const cordic_fmbank *bank, uint64_t *samples,
 	if (!bank)
 		return CORDIC_ERR_ARGS;
 	if (samples) *samples = bank->samples;
-	if (spans) *spans = bank->nspans;
-	if (tile) *tile = (int32_t)(bank->tiles * kFmobTile);
+	if (spans) *spans = bank->spans.nspans;
+	if (tile) *tile = (int32_t)(bank->tiles * kFmobRule.unit);
 	return CORDIC_OK;
 }
 
@@ -723,6 +703,7 @@ int cordic_fmbank_run(const cordic_fmbank *bank, void *stream)
 	(void)hipGetLastError();
 	if (int rc = device_is_current(bank->device))
 		return rc;
-	return launch_fmosc_bank(bank->core, bank->d_spans, bank->nspans, bank->d_words,
-		bank->d_words + bank->nstarts, bank->cus, bank->io16, stream);
+	const SpanTable<FmSpan> &t = bank->spans;
+	return launch_fmosc_bank(bank->core, t.d_spans, t.nspans, t.start(), t.part(),
+		bank->cus, bank->io16, stream);
 }

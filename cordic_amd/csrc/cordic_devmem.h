@@ -1,16 +1,19 @@
 // cordic_devmem.h -- host-only helpers of the C ABI units (cordic_abi*.cpp,
 // cordic_fm_demod_bank.hip): device memory of the handles, the stream-capture
-// queries, a handle's device, the skeleton of the two FM bank handles.  Handles
+// queries, a handle's device, the skeleton of the FM bank handles and the span
+// table of the two prefix-sum ones.  Handles
 // are C structs that their *_destroy functions free; nothing here owns memory.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <new>
 #include <vector>
 
 #include "cordic_amd.h"
+#include "cordic_span_bank.h"
 
 // frees the non-null ones of its pointers, then nulls them
 template <typename... T> static void dev_free(T *&...p)
@@ -148,6 +151,48 @@ static int bank_begin(size_t njobs, const Job *jobs, bool fused,
 		return CORDIC_ERR_DEVICE;
 	}
 	*out = b;
+	return CORDIC_OK;
+}
+
+// ---- What cordic_mixbank (cordic_abi.cpp) and cordic_fmbank
+// (cordic_abi_table.cpp) share, the prefix-sum banks (cordic_span_bank.h): the
+// span table on the device and the workspace of a run, [start words, one per
+// non-empty job | partial sums, one per span].
+template <typename SPAN> struct SpanTable {
+	SPAN	*d_spans = nullptr;
+	uint32_t *d_words = nullptr;
+	uint32_t nspans = 0, nstarts = 0;
+	uint32_t *start() const { return d_words; }
+	uint32_t *part() const { return d_words + nstarts; }
+	void	free() { dev_free(d_spans, d_words); }
+};
+
+// The tail of a create, behind its own argument checks: the base span for
+// `total_units` on `cus` CUs with `per_cu` resident blocks each, or what the
+// environment variable `env_base` forces, into *base (for *_info); the span cap
+// of `rule`, or what `env_cap` lowers it to; then cuts, uploads and allocates.
+// CORDIC_OK; CORDIC_ERR_ARGS: more than 2^32 - 1 spans; CORDIC_ERR_DEVICE: an
+// upload failed, and nothing stays allocated.
+template <typename SPAN, typename Jobs>
+static int span_table_build(SpanTable<SPAN> *t, const char *env_base,
+		const char *env_cap, const cordic_amd::SpanRule &rule, uint64_t total_units,
+		int cus, int per_cu, size_t njobs, Jobs jobs, uint32_t *base)
+{
+	using namespace cordic_amd;
+	*base = span_forced_base(rule, std::getenv(env_base),
+			span_base_units(rule, total_units, cus, per_cu));
+	const uint32_t cap = span_forced_cap(rule, std::getenv(env_cap));
+	if (span_count(rule, njobs, jobs, *base, cap) > 0xffffffffull)
+		return CORDIC_ERR_ARGS;
+	std::vector<SPAN> spans;
+	span_cut(rule, njobs, jobs, *base, cap, &spans, &t->nstarts);
+	t->nspans = (uint32_t)spans.size();
+	if (!dev_upload(spans.data(), spans.size() * sizeof(SPAN), &t->d_spans)
+			|| !dev_zalloc(&t->d_words,
+				((size_t)t->nstarts + t->nspans) * sizeof(uint32_t))) {
+		t->free();
+		return CORDIC_ERR_DEVICE;
+	}
 	return CORDIC_OK;
 }
 

@@ -11,6 +11,7 @@
 #ifndef CORDIC_FM_DEMOD_BANK_H
 #define CORDIC_FM_DEMOD_BANK_H
 
+#include <array>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -18,6 +19,7 @@
 #include "cordic_amd.h"
 #include "cordic_bank_host.h"
 #include "cordic_fm_demod.h"
+#include "cordic_span_bank.h"
 
 namespace cordic_amd {
 
@@ -53,68 +55,27 @@ inline int fmd_bank_passes(uint64_t total_vecs, int cus)
 	return (int)bank_passes(total_vecs, cus, 8, kFmdBankPassVecs, 8);
 }
 
-// The jobs of a create, of either struct: cordic_demod_job16 is
-// cordic_demod_job field for field but for the element type behind the four
-// sample pointers, which the host never dereferences.  jobs[k] is job k as a
-// cordic_demod_job; esize() the bytes of a sample, which is all the checks and
-// the cutter know of the container.  (A plain pointer to either struct
-// converts, so the calls on cordic_demod_job arrays read as they did.)
-struct DemodJobs {
-	const cordic_demod_job *j32 = nullptr;
-	const cordic_demod_job16 *j16 = nullptr;
-	uint64_t es = 4;	// (by the pointer's type: a NULL one still names its container)
-	DemodJobs(const cordic_demod_job *j) : j32(j) {}
-	DemodJobs(const cordic_demod_job16 *j) : j16(j), es(2) {}
-	DemodJobs(std::nullptr_t) {}
-	bool	none() const { return !j32 && !j16; }
-	uint64_t esize() const { return es; }
-	uint64_t n(size_t k) const { return j16 ? j16[k].n : j32[k].n; }
-	cordic_demod_job operator[](size_t k) const
-	{
-		if (!j16)
-			return j32[k];
-		const cordic_demod_job16 &a = j16[k];
-		cordic_demod_job b;
-		b.d_xval = reinterpret_cast<const int32_t *>(a.d_xval);
-		b.d_yval = reinterpret_cast<const int32_t *>(a.d_yval);
-		b.d_omag = reinterpret_cast<int32_t *>(a.d_omag);
-		b.d_ofreq = reinterpret_cast<int32_t *>(a.d_ofreq);
-		b.d_last = a.d_last;
-		b.n = a.n;
-		b.phase0 = a.phase0;
-		b.reserved = a.reserved;
-		return b;
-	}
-};
+// The jobs of a create, of either struct (JobView, cordic_span_bank.h)
+typedef JobView<cordic_demod_job, cordic_demod_job16> DemodJobs;
+#define F(f) CORDIC_SAME_FIELD(cordic_demod_job, cordic_demod_job16, f)
+static_assert(sizeof(cordic_demod_job) == 56 && F(d_xval) && F(d_yval) && F(d_omag)
+	&& F(d_ofreq) && F(d_last) && F(n) && F(phase0) && F(reserved),
+	"cordic_demod_job16 is cordic_demod_job with 16-bit sample pointers");
+#undef F
 
 // The argument checks of cordic_demodbank_create / _create16 that need no
-// device: every job with n > 0 has four non-NULL sample pointers on the grid of
-// their element (4 or 2 bytes), a 4-byte-aligned d_last, reserved == 0 and a
-// length within SIZE_MAX >> 4; no output range (d_omag, d_ofreq, the word at
-// d_last) overlaps another output range or any input range of the bank
-// (BankRanges, cordic_bank_host.h), by the true byte ranges: n * esize.
+// device (bank_jobs_valid, cordic_span_bank.h): the four sample arrays
+// required, d_last optional; the outputs are d_omag, d_ofreq and the word at
+// d_last.
 inline bool fmd_bank_jobs_valid(size_t njobs, DemodJobs jobs)
 {
-	const uint64_t es = jobs.esize();
-	BankRanges r;
-	for (size_t k = 0; k < njobs; k++) {
-		const cordic_demod_job jb = jobs[k];
-		if (jb.n == 0)
-			continue;
-		const uintptr_t p[4] = {(uintptr_t)jb.d_xval, (uintptr_t)jb.d_yval,
-			(uintptr_t)jb.d_omag, (uintptr_t)jb.d_ofreq};
-		const uintptr_t l = (uintptr_t)jb.d_last;
-		if (!p[0] || !p[1] || !p[2] || !p[3]
-				|| ((p[0] | p[1] | p[2] | p[3]) & (es - 1)) || (l & 3u)
-				|| jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
-			return false;
-		for (int i = 0; i < 4; i++)
-			if (!r.add(p[i], jb.n * es, i >= 2))
-				return false;
-		if (l && !r.add(l, 4, true))
-			return false;
-	}
-	return r.outputs_clear();
+	return bank_jobs_valid(njobs, jobs,
+		[](const cordic_demod_job &jb, uint64_t es, const void **word) {
+			*word = jb.d_last;
+			return std::array<JobArray, 4>{{{jb.d_xval, es, true, false},
+				{jb.d_yval, es, true, false}, {jb.d_omag, es, true, true},
+				{jb.d_ofreq, es, true, true}}};
+		});
 }
 
 // tiles of `tile_vecs` vectors the jobs cut into (saturating at 2^63)

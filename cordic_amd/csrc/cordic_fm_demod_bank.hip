@@ -224,12 +224,6 @@ int cordic_demodbank_create(const cordic_config *cfg, size_t njobs,
 int cordic_demodbank_create16(const cordic_config *cfg, size_t njobs,
 		const cordic_demod_job16 *jobs, cordic_demodbank **bank)
 {
-	static_assert(sizeof(cordic_demod_job16) == sizeof(cordic_demod_job)
-		&& offsetof(cordic_demod_job16, d_xval) == offsetof(cordic_demod_job, d_xval)
-		&& offsetof(cordic_demod_job16, d_ofreq) == offsetof(cordic_demod_job, d_ofreq)
-		&& offsetof(cordic_demod_job16, d_last) == offsetof(cordic_demod_job, d_last)
-		&& offsetof(cordic_demod_job16, n) == offsetof(cordic_demod_job, n),
-		"cordic_demod_job16 is cordic_demod_job with 16-bit sample pointers");
 	return demodbank_create(cfg, njobs, jobs, bank);
 }
 

@@ -5,10 +5,9 @@
 // single call's reduce-then-scan (cordic_fm_mix.hip) reading span descriptors
 // (MixSpan, cordic_fm_mix_bank.h): the host has cut every job into spans of
 // whole 1024-sample passes, never across a job's end, a job into at most 4096.
-//   1. fm_mixbank_reduce: block b sums the tuning words of spans b, b + grid,
-//      ... into one workspace word per span (a span of one pass is one pass of
-//      one block: 256 lanes, one 16-byte load each); a job's first span latches
-//      phase0 + *d_acc into the job's start word.
+//   1. span_reduce<MixSpan, 256> (cordic_span_reduce.h, where launch 1 and the
+//      descriptor's head are described for both prefix-sum banks): a span of
+//      one pass is one pass of one block, 256 lanes, one 16-byte load each.
 //   2. fm_mixbank_xydir<LJ, NLIVE>: at most the resident blocks.  A block
 //      stages the plan's direction tables ONCE, then walks spans b, b + grid,
 //      ... in the table's order, which is the jobs' own.  Per span the
@@ -40,9 +39,9 @@
 // while a slower wave still reads it.  The carry is set anew per span from the
 // job's start word and partials: nothing of the span before survives in it.
 //
-// The base span is P passes, chosen at create -- fmxb_passes: the longest span,
-// in the steps 1, 2, 4, 8, 16, ..., that still gives every resident block four
-// -- or forced by CORDIC_FMXB_PASSES; a job that would have more than 4096 spans
+// The base span is P passes, chosen at create -- span_base_units
+// (cordic_span_bank.h): the longest span, in the steps 1, 2, 4, 8, 16, ..., that
+// still gives every resident block four -- or forced by CORDIC_FMXB_PASSES; a job that would have more than 4096 spans
 // (CORDIC_FMXB_MAX_SPANS lowers that; both read at create) gets spans twice,
 // four times, ... as long, that job alone.  Launch 2's grid is min(spans, CUs *
 // resident blocks per CU), capped further by CORDIC_FMXB_MAX_BLOCKS (read at
@@ -59,7 +58,7 @@
 //   fm_mix_xydir<30, N> after   92   98   95   95  102  103  103
 //   fm_mixbank_xydir<30, N>    115  117  116  116  115  124  124
 //   ... <30, N, Io16>          111  113  112  112  112  120  120
-//   fm_mixbank_reduce           42 (32 bytes of static LDS)
+//   span_reduce<MixSpan, 256>   42 (32 bytes of static LDS)
 // The single call's counts did not move.  The bank's kernel takes 12 .. 23
 // more: six array addresses, the sample count and the indices arrive per span
 // where the single call has them as kernel arguments, and the lane's element
@@ -71,7 +70,7 @@
 // The container of the four sample arrays (Io32 / Io16, the third template
 // parameter) reaches pass_loop and nothing else here: MixSpan holds byte
 // addresses, which the host's cutter advances by 2 or 4 bytes per sample, and
-// fm_mixbank_reduce reads tuning words only.  The table was taken again with
+// span_reduce reads tuning words only.  The table was taken again with
 // the parameter in place: the 32-bit rows did not move, and no Io16 instance
 // (LJ = 30 only, see fmx_is_fused16) spills.
 #include <hip/hip_runtime.h>
@@ -84,58 +83,15 @@
 #include "cordic_hostargs.h"
 #include "cordic_fm_mix.h"
 #include "cordic_fm_mix_bank.h"
+#include "cordic_span_reduce.h"
 
 namespace cordic_amd {
 
-static_assert(kFmxbPass == kFmxPass && kFmxbMaxSpans == kFmxMaxBlocks
+static_assert(kFmxbRule.unit == kFmxPass && kFmxbRule.max_spans == kFmxMaxBlocks
 	&& (size_t)kFmxbBlocksPerCu == kFmxBlocksPerCu, "the single call's geometry");
-static_assert(sizeof(MixSpan) == 88, "the descriptor is read as scalar words");
+static_assert(dev::kBlock == 256, "launch 1 is instantiated at the block of launch 2");
 
 namespace fmx {
-
-// launch 1: part[d.part0 + d.idx] = the sum of the span's tuning words;
-// start[d.start] = phase0 + *d_acc for a job's first span.  The two words of
-// wsum are double-buffered by span, as the exchange words of pass_loop are by
-// pass: one barrier per span.
-__global__ __launch_bounds__(kBlock) void fm_mixbank_reduce(
-		const MixSpan *__restrict__ spans, uint32_t nspans,
-		uint32_t *__restrict__ start, uint32_t *__restrict__ part)
-{
-	__shared__ uint32_t wsum[2][kBlock / 64];
-	const unsigned tid = threadIdx.x;
-	unsigned par = 0;
-	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
-		const MixSpan d = spans[t];
-		const uint32_t *f = reinterpret_cast<const uint32_t *>((uintptr_t)d.fcw);
-		const u32x4g *fv = reinterpret_cast<const u32x4g *>(f);
-		const uint64_t nv = d.n / kVec;
-		uint32_t s = 0;
-#pragma unroll 4
-		for (uint64_t g = tid; g < nv; g += kBlock) {
-			const u32x4 q = fv[g];
-			s += q[0] + q[1] + q[2] + q[3];
-		}
-		const uint64_t r = nv * kVec + tid;	// fewer than 4 behind the vectors
-		if (r < d.n)
-			s += f[r];
-#pragma unroll
-		for (int k = 32; k; k >>= 1)
-			s += __shfl_xor(s, k);
-		if ((tid & 63u) == 0)
-			wsum[par][tid >> 6] = s;
-		__syncthreads();
-		if (tid == 0) {
-			part[d.part0 + d.idx] = wsum[par][0] + wsum[par][1] + wsum[par][2]
-				+ wsum[par][3];
-			if (d.flags & kMixSpanFirst) {
-				const uint32_t *acc
-					= reinterpret_cast<const uint32_t *>((uintptr_t)d.acc);
-				start[d.start] = d.phase0 + (acc ? *acc : 0u);
-			}
-		}
-		par ^= 1;
-	}
-}
 
 // launch 2 (see the head of this file)
 template <int LJ, int NLIVE, typename IO>
@@ -184,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 			reinterpret_cast<ielem *>((uintptr_t)d.ox),
 			reinterpret_cast<ielem *>((uintptr_t)d.oy), (size_t)0, (size_t)d.n,
 			carry, par, ex, tid, wave, IO{});
-		if ((d.flags & kMixSpanLast) && d.acc && tid == 0)
+		if ((d.flags & kSpanLast) && d.acc && tid == 0)
 			*reinterpret_cast<uint32_t *>((uintptr_t)d.acc) = carry;
 	}
 }
@@ -221,15 +177,12 @@ int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 	hipStream_t st = static_cast<hipStream_t>(stream);
 	uint32_t xw = 0;
 	const size_t lds = lds_bytes(dx, &xw);
-	// launch 1 has 8 waves a SIMD (few registers, 32 bytes of LDS)
-	size_t rgrid = (size_t)cus * 8;
-	if (rgrid > nspans)
-		rgrid = nspans;
-	hipLaunchKernelGGL(fm_mixbank_reduce, dim3((unsigned)rgrid), dim3(kBlock), 0, st,
+	// launch 1 has 8 waves a SIMD: 8 blocks of 4 waves a CU
+	const SpanGrids g = span_grids(nspans, cus, 8, "CORDIC_FMXB_MAX_BLOCKS",
+		blocks_per_cu(lds));
+	hipLaunchKernelGGL((span_reduce<MixSpan, 256>), dim3(g.reduce), dim3(256), 0, st,
 		d_spans, nspans, d_start, d_part);
-	size_t cap = (size_t)cus * blocks_per_cu(lds);
-	cap = env_block_cap("CORDIC_FMXB_MAX_BLOCKS", cap);
-	const unsigned grid = (unsigned)(nspans < cap ? nspans : cap);
+	const unsigned grid = g.walk;
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
 	const bool done = io16

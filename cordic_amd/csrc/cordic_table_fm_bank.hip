@@ -6,10 +6,9 @@
 // reduce-then-scan (cordic_table_fm.hip) reading span descriptors (FmSpan,
 // cordic_table_fm_bank.h): the host has cut every job into spans of whole
 // 4096-sample tiles, never across a job's end, a job into at most 1024.
-//   1. fm_oscbank_reduce: blocks of 1024 threads, so that a tile is one 16-byte
-//      load per lane (at any 4-byte alignment).  Block b sums the tuning words
-//      of spans b, b + grid, ... into one workspace word per span; a job's
-//      first span latches phase0 + *d_acc into the job's start word.
+//   1. span_reduce<FmSpan, 1024> (cordic_span_reduce.h, where launch 1 and the
+//      descriptor's head are described for both prefix-sum banks): blocks of
+//      1024 threads, so that a tile is one 16-byte load per lane.
 //   2. table_fmbank<CORE, T>: at most the resident blocks, sized as the single
 //      call sizes its grid (lds_blocks_per_cu of table + phases + static, per
 //      CU).  A block stages the core's table ONCE, then walks spans b, b +
@@ -44,9 +43,9 @@
 //   - The carry is set anew per span from the job's start word and partials:
 //     nothing of the span before survives in it.
 //
-// The base span is T tiles, chosen at create -- fmob_tiles: the longest span,
-// in the steps 1, 2, 4, ..., that still gives every resident block four -- or
-// forced by CORDIC_FMOB_TILES; a job that would have more than 1024 spans
+// The base span is T tiles, chosen at create -- span_base_units
+// (cordic_span_bank.h): the longest span, in the steps 1, 2, 4, ..., that still
+// gives every resident block four -- or forced by CORDIC_FMOB_TILES; a job that would have more than 1024 spans
 // (CORDIC_FMOB_MAX_SPANS lowers that; both read at create) gets spans twice,
 // four times, ... as long, that job alone.  Launch 2's grid is min(spans, CUs *
 // resident blocks per CU), capped further by CORDIC_FMOB_MAX_BLOCKS (read at
@@ -66,7 +65,8 @@
 //   table_fm before        61     61       61     59       63     63         61
 //   table_fm after         53     55       53     55       53     55         53
 //   table_fmbank           83     86       83     85       83     87         (none)
-//   fm_reduce 48 before and after; fm_oscbank_reduce 60 (128 bytes of static LDS)
+//   fm_reduce 48 before and after; span_reduce<FmSpan, 1024> 42 (128 bytes of
+//   static LDS)
 // table_fm stays within the 64 registers its comment promises.  (The loop lifted
 // word for word, with 64-bit sample indices, took 57 .. 61 but spilled six more
 // scalar registers into lanes and cost the single call 6 %; tile_loop counts in
@@ -97,59 +97,14 @@
 #include "cordic_table_nco.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_hostargs.h"
+#include "cordic_span_reduce.h"
 
 namespace cordic_amd {
 
-static_assert(kFmobTile == kFmTile && kFmobMaxSpans == kFmMaxBlocks,
+static_assert(kFmobRule.unit == kFmTile && kFmobRule.max_spans == kFmMaxBlocks,
 	"the single call's geometry");
 
 namespace tfm {
-
-// launch 1: part[d.part0 + d.idx] = the sum of the span's tuning words;
-// start[d.start] = phase0 + *d_acc for a job's first span.  The 16 words of
-// wsum are double-buffered by span: one barrier per span.
-__global__ __launch_bounds__(1024) void fm_oscbank_reduce(
-		const FmSpan *__restrict__ spans, uint32_t nspans,
-		uint32_t *__restrict__ start, uint32_t *__restrict__ part)
-{
-	__shared__ uint32_t wsum[2][16];
-	const unsigned tid = threadIdx.x;
-	unsigned par = 0;
-	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
-		const FmSpan d = spans[t];
-		const uint32_t *f = reinterpret_cast<const uint32_t *>((uintptr_t)d.fcw);
-		const Words4 *fv = reinterpret_cast<const Words4 *>(f);
-		const uint64_t nv = d.n / 4;
-		uint32_t s = 0;
-#pragma unroll 4
-		for (uint64_t g = tid; g < nv; g += 1024) {
-			const Words4 q = fv[g];
-			s += q.v[0] + q.v[1] + q.v[2] + q.v[3];
-		}
-		const uint64_t r = nv * 4 + tid;	// fewer than 4 behind the vectors
-		if (r < d.n)
-			s += f[r];
-#pragma unroll
-		for (int k = 32; k; k >>= 1)
-			s += __shfl_xor(s, k);
-		if ((tid & 63u) == 0)
-			wsum[par][tid >> 6] = s;
-		__syncthreads();
-		if (tid == 0) {
-			uint32_t sum = 0;
-#pragma unroll
-			for (int j = 0; j < 16; j++)
-				sum += wsum[par][j];
-			part[d.part0 + d.idx] = sum;
-			if (d.flags & kFmSpanFirst) {
-				const uint32_t *acc
-					= reinterpret_cast<const uint32_t *>((uintptr_t)d.acc);
-				start[d.start] = d.phase0 + (acc ? *acc : 0u);
-			}
-		}
-		par ^= 1;
-	}
-}
 
 // what tile_loop reads of a span
 struct SpanArgs {
@@ -183,7 +138,7 @@ __global__ __launch_bounds__(1024) void table_fmbank(CORE core,
 		tile_loop<CORE, T>(core, tab, ph, wsum, a,
 			reinterpret_cast<T *>((uintptr_t)d.sin),
 			reinterpret_cast<T *>((uintptr_t)d.cos), (size_t)0, (size_t)d.n, carry);
-		if ((d.flags & kFmSpanLast) && d.acc && tid == 0)
+		if ((d.flags & kSpanLast) && d.acc && tid == 0)
 			*reinterpret_cast<uint32_t *>((uintptr_t)d.acc) = carry;
 	}
 }
@@ -211,15 +166,12 @@ bool bank_one(const CORE &core, const BankCall &c, uint32_t quarter, size_t tabl
 		*c.per_cu = per_cu;
 		return true;
 	}
-	// launch 1 has two blocks of 16 waves a CU (few registers, 128 bytes of LDS)
-	size_t rgrid = (size_t)c.cus * 2;
-	if (rgrid > c.nspans)
-		rgrid = c.nspans;
-	hipLaunchKernelGGL(fm_oscbank_reduce, dim3((unsigned)rgrid), dim3(1024), 0, c.st,
+	// launch 1 has two blocks of 16 waves a CU
+	const SpanGrids g = span_grids(c.nspans, c.cus, 2, "CORDIC_FMOB_MAX_BLOCKS",
+		(size_t)per_cu);
+	hipLaunchKernelGGL((span_reduce<FmSpan, 1024>), dim3(g.reduce), dim3(1024), 0, c.st,
 		c.spans, c.nspans, c.start, c.part);
-	size_t cap = env_block_cap("CORDIC_FMOB_MAX_BLOCKS", (size_t)c.cus * per_cu);
-	const unsigned grid = (unsigned)(c.nspans < cap ? c.nspans : cap);
-	hipLaunchKernelGGL((table_fmbank<CORE, T>), dim3(grid), dim3(1024), lds, c.st, core,
+	hipLaunchKernelGGL((table_fmbank<CORE, T>), dim3(g.walk), dim3(1024), lds, c.st, core,
 		c.spans, c.nspans, (const uint32_t *)c.start, (const uint32_t *)c.part,
 		quarter, (uint32_t)table_bytes);
 	return true;

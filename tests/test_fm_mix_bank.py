@@ -183,8 +183,8 @@ static void check_cut(const std::vector<cordic_fmmix_job> &jobs, uint32_t passes
 {
 	std::vector<MixSpan> spans;
 	uint32_t live = 0;
-	fmxb_cut(jobs.size(), jobs.data(), passes, cap, &spans, &live);
-	EXPECT(spans.size() == fmxb_count_spans(jobs.size(), jobs.data(), passes, cap));
+	span_cut(kFmxbRule, jobs.size(), MixJobs(jobs.data()), passes, cap, &spans, &live);
+	EXPECT(spans.size() == span_count(kFmxbRule, jobs.size(), MixJobs(jobs.data()), passes, cap));
 	size_t at = 0;
 	uint32_t seen = 0;
 	for (size_t k = 0; k < jobs.size(); k++) {
@@ -211,17 +211,17 @@ static void check_cut(const std::vector<cordic_fmmix_job> &jobs, uint32_t passes
 			EXPECT(s.n >= 1 && s.n <= jb.n - done);
 			EXPECT(s.start == seen && s.part0 == first && s.idx == at - first);
 			const bool is_first = done == 0, is_last = done + s.n == jb.n;
-			EXPECT(s.flags == ((is_first ? kMixSpanFirst : 0u)
-				| (is_last ? kMixSpanLast : 0u)));
+			EXPECT(s.flags == ((is_first ? kSpanFirst : 0u)
+				| (is_last ? kSpanLast : 0u)));
 			if (!is_last) {		// whole passes, all of one length
-				EXPECT(s.n % kFmxbPass == 0);
+				EXPECT(s.n % kFmxbRule.unit == 0);
 				EXPECT(full == 0 || s.n == full);
 				full = s.n;
 			} else {
 				EXPECT(full == 0 || s.n <= full);
 			}
 			if (full) {		// P, or P doubled
-				const uint64_t p = full / kFmxbPass;
+				const uint64_t p = full / kFmxbRule.unit;
 				EXPECT(p >= passes && p % passes == 0 && !((p / passes) & (p / passes - 1)));
 			}
 			done += s.n;
@@ -231,8 +231,8 @@ static void check_cut(const std::vector<cordic_fmmix_job> &jobs, uint32_t passes
 		const size_t count = at - first;
 		EXPECT(count <= cap);
 		// doubled only as far as the cap asks
-		const uint64_t np = fmxb_passes_of(jb.n);
-		const uint64_t pj = fmxb_job_passes(jb.n, passes, cap);
+		const uint64_t np = span_units_of(kFmxbRule, jb.n);
+		const uint64_t pj = span_job_units(kFmxbRule, jb.n, passes, cap);
 		EXPECT(count == (np + pj - 1) / pj);
 		EXPECT(pj == passes || (np + pj / 2 - 1) / (pj / 2) > cap);
 		seen++;
@@ -250,33 +250,37 @@ int main()
 		jobs.push_back(job_at(k, lens[k], k % 2 == 0, k % 3 != 0));
 	EXPECT(fmxb_jobs_valid(jobs.size(), jobs.data()));
 	for (uint32_t p = 1; p <= 64; p *= 2) {		// every forced P
-		check_cut(jobs, p, kFmxbMaxSpans);
+		check_cut(jobs, p, kFmxbRule.max_spans);
 		check_cut(jobs, p, 3);			// a forced span cap of 3
 		check_cut(jobs, p, 1);
 	}
 	check_cut(jobs, 1, 7);
-	check_cut(std::vector<cordic_fmmix_job>(), 1, kFmxbMaxSpans);
+	check_cut(std::vector<cordic_fmmix_job>(), 1, kFmxbRule.max_spans);
 	{	// a job of the greatest length stays within the cap
 		std::vector<cordic_fmmix_job> big(1, job_at(0, ~(size_t)0 >> 4, false, true));
-		EXPECT(fmxb_count_spans(1, big.data(), 1, kFmxbMaxSpans) <= kFmxbMaxSpans);
-		EXPECT(fmxb_count_spans(1, big.data(), 1, 3) <= 3);
+		EXPECT(span_count(kFmxbRule, 1, MixJobs(big.data()), 1, kFmxbRule.max_spans)
+			<= kFmxbRule.max_spans);
+		EXPECT(span_count(kFmxbRule, 1, MixJobs(big.data()), 1, 3) <= 3);
 	}
 
 	// P by the bank's size: the longest span that leaves 4 per resident block
+	auto fmxb_passes = [](uint64_t total_passes, int cus) {
+		return span_base_units(kFmxbRule, total_passes, cus, kFmxbBlocksPerCu);
+	};
 	EXPECT(fmxb_passes(0, 256) == 1 && fmxb_passes(4095, 256) == 1);
 	EXPECT(fmxb_passes(4096, 256) == 1 && fmxb_passes(8191, 256) == 1);
 	EXPECT(fmxb_passes(8192, 256) == 2 && fmxb_passes(65536, 256) == 16);
 	EXPECT(fmxb_passes(65536, 0) == 16 && fmxb_passes(65536, 64) == 64);
-	EXPECT(fmxb_passes(~(uint64_t)0, 1) == kFmxbMaxPasses);
+	EXPECT(fmxb_passes(~(uint64_t)0, 1) == kFmxbRule.max_units);
 	// the knobs
-	EXPECT(fmxb_forced_passes(nullptr, 4) == 4 && fmxb_forced_passes("8", 4) == 8);
-	EXPECT(fmxb_forced_passes("3", 4) == 4 && fmxb_forced_passes("0", 4) == 4);
-	EXPECT(fmxb_forced_passes("-2", 4) == 4 && fmxb_forced_passes("x", 4) == 4);
-	EXPECT(fmxb_forced_passes("1048576", 4) == 1048576);
-	EXPECT(fmxb_forced_passes("2097152", 4) == 4);
-	EXPECT(fmxb_forced_cap(nullptr) == 4096 && fmxb_forced_cap("3") == 3);
-	EXPECT(fmxb_forced_cap("0") == 4096 && fmxb_forced_cap("4096") == 4096);
-	EXPECT(fmxb_forced_cap("99999") == 4096 && fmxb_forced_cap("4095") == 4095);
+	EXPECT(span_forced_base(kFmxbRule, nullptr, 4) == 4 && span_forced_base(kFmxbRule, "8", 4) == 8);
+	EXPECT(span_forced_base(kFmxbRule, "3", 4) == 4 && span_forced_base(kFmxbRule, "0", 4) == 4);
+	EXPECT(span_forced_base(kFmxbRule, "-2", 4) == 4 && span_forced_base(kFmxbRule, "x", 4) == 4);
+	EXPECT(span_forced_base(kFmxbRule, "1048576", 4) == 1048576);
+	EXPECT(span_forced_base(kFmxbRule, "2097152", 4) == 4);
+	EXPECT(span_forced_cap(kFmxbRule, nullptr) == 4096 && span_forced_cap(kFmxbRule, "3") == 3);
+	EXPECT(span_forced_cap(kFmxbRule, "0") == 4096 && span_forced_cap(kFmxbRule, "4096") == 4096);
+	EXPECT(span_forced_cap(kFmxbRule, "99999") == 4096 && span_forced_cap(kFmxbRule, "4095") == 4095);
 
 	// the overlap rules
 	const uint64_t n = 64;

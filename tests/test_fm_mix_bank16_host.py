@@ -58,8 +58,8 @@ static void check_cut(const std::vector<Job> &jobs, uint32_t passes, uint32_t ca
 {
 	std::vector<MixSpan> spans;
 	uint32_t live = 0;
-	fmxb_cut(jobs.size(), jobs.data(), passes, cap, &spans, &live);
-	EXPECT(spans.size() == fmxb_count_spans(jobs.size(), jobs.data(), passes, cap));
+	span_cut(kFmxbRule, jobs.size(), MixJobs(jobs.data()), passes, cap, &spans, &live);
+	EXPECT(spans.size() == span_count(kFmxbRule, jobs.size(), MixJobs(jobs.data()), passes, cap));
 	size_t at = 0;
 	uint32_t seen = 0;
 	for (size_t k = 0; k < jobs.size(); k++) {
@@ -67,7 +67,7 @@ static void check_cut(const std::vector<Job> &jobs, uint32_t passes, uint32_t ca
 		if (!jb.n)
 			continue;
 		const size_t first = at;
-		const uint64_t pj = fmxb_job_passes(jb.n, passes, cap);
+		const uint64_t pj = span_job_units(kFmxbRule, jb.n, passes, cap);
 		uint64_t done = 0;
 		while (done < jb.n) {
 			EXPECT(at < spans.size());
@@ -84,16 +84,16 @@ static void check_cut(const std::vector<Job> &jobs, uint32_t passes, uint32_t ca
 			EXPECT(s.phase0 == jb.phase0 && s.pad == 0);
 			EXPECT(s.start == seen && s.part0 == first && s.idx == at - first);
 			const bool is_first = done == 0;
-			const bool is_last = jb.n - done <= pj * kFmxbPass;
-			EXPECT(s.n == (is_last ? jb.n - done : pj * kFmxbPass));
-			EXPECT(s.flags == ((is_first ? kMixSpanFirst : 0u)
-				| (is_last ? kMixSpanLast : 0u)));
+			const bool is_last = jb.n - done <= pj * kFmxbRule.unit;
+			EXPECT(s.n == (is_last ? jb.n - done : pj * kFmxbRule.unit));
+			EXPECT(s.flags == ((is_first ? kSpanFirst : 0u)
+				| (is_last ? kSpanLast : 0u)));
 			done += s.n;
 			at++;
 		}
 		EXPECT(done == jb.n);
 		EXPECT(at - first <= cap);
-		EXPECT(at - first == (fmxb_passes_of(jb.n) + pj - 1) / pj);
+		EXPECT(at - first == (span_units_of(kFmxbRule, jb.n) + pj - 1) / pj);
 		seen++;
 	}
 	EXPECT(at == spans.size() && seen == live);
@@ -121,21 +121,21 @@ int main()
 	EXPECT(fmxb_jobs_valid(j32.size(), j32.data()));
 	EXPECT(MixJobs(j16.data()).esize() == 2 && MixJobs(j32.data()).esize() == 4);
 	for (uint32_t p = 1; p <= 8; p *= 2) {
-		check_cut(j16, p, kFmxbMaxSpans, 2);
-		check_cut(j32, p, kFmxbMaxSpans, 4);
+		check_cut(j16, p, kFmxbRule.max_spans, 2);
+		check_cut(j32, p, kFmxbRule.max_spans, 4);
 		check_cut(j16, p, 2, 2);
 		check_cut(j32, p, 2, 4);
 	}
-	check_cut(std::vector<cordic_fmmix_job16>(), 1, kFmxbMaxSpans, 2);
+	check_cut(std::vector<cordic_fmmix_job16>(), 1, kFmxbRule.max_spans, 2);
 	{	// the three lengths by hand, P = 1
 		std::vector<MixSpan> s;
 		uint32_t live = 0;
 		const cordic_fmmix_job16 a[3] = {job16(0, 1024), job16(1, 1025), job16(2, huge)};
-		fmxb_cut(3, a, 1, kFmxbMaxSpans, &s, &live);
+		span_cut(kFmxbRule, 3, MixJobs(a), 1, kFmxbRule.max_spans, &s, &live);
 		EXPECT(live == 3 && s.size() == 1 + 2 + 2049);
-		EXPECT(s[0].n == 1024 && s[0].flags == (kMixSpanFirst | kMixSpanLast));
-		EXPECT(s[1].n == 1024 && s[1].flags == kMixSpanFirst && s[1].idx == 0);
-		EXPECT(s[2].n == 1 && s[2].flags == kMixSpanLast && s[2].idx == 1);
+		EXPECT(s[0].n == 1024 && s[0].flags == (kSpanFirst | kSpanLast));
+		EXPECT(s[1].n == 1024 && s[1].flags == kSpanFirst && s[1].idx == 0);
+		EXPECT(s[2].n == 1 && s[2].flags == kSpanLast && s[2].idx == 1);
 		EXPECT(s[2].part0 == 1 && s[2].start == 1);
 		EXPECT(s[2].x == (uintptr_t)a[1].d_xval + 2048);	// 1024 shorts on
 		EXPECT(s[2].oy == (uintptr_t)a[1].d_oyval + 2048);
@@ -146,11 +146,11 @@ int main()
 		EXPECT(s[4].x == (uintptr_t)a[2].d_xval + 4096 && s[4].idx == 1);
 		EXPECT(s[4].fcw == (uintptr_t)a[2].d_fcw + 8192);
 		EXPECT(s.back().n == 1 && s.back().idx == 2048
-			&& s.back().flags == kMixSpanLast);
+			&& s.back().flags == kSpanLast);
 		// the same jobs as 32-bit ones: 4 bytes per sample everywhere
 		std::vector<MixSpan> w;
 		const cordic_fmmix_job b[3] = {job32(0, 1024), job32(1, 1025), job32(2, huge)};
-		fmxb_cut(3, b, 1, kFmxbMaxSpans, &w, &live);
+		span_cut(kFmxbRule, 3, MixJobs(b), 1, kFmxbRule.max_spans, &w, &live);
 		EXPECT(live == 3 && w.size() == s.size());
 		EXPECT(w[2].x == (uintptr_t)b[1].d_xval + 4096);
 		EXPECT(w[2].fcw == (uintptr_t)b[1].d_fcw + 4096);
@@ -239,6 +239,11 @@ def test_one_implementation_serves_both_job_structs():
     """no second copy of the checks or the cutter, and the cutter touches no
     device"""
     text = open(os.path.join(CSRC, "cordic_fm_mix_bank.h")).read()
-    for fn in ("fmxb_jobs_valid", "fmxb_count_spans", "fmxb_cut"):
+    assert len(re.findall(r"\binline\s+\w+\s+fmxb_jobs_valid\s*\(", text)) == 1
+    assert "#include <hip" not in text and "hipMalloc" not in text
+    # the span count and the cutter: the prefix-sum banks' shared layer
+    assert '#include "cordic_span_bank.h"' in text
+    text = open(os.path.join(CSRC, "cordic_span_bank.h")).read()
+    for fn in ("span_count", "span_cut"):
         assert len(re.findall(r"\binline\s+\w+\s+%s\s*\(" % fn, text)) == 1, fn
     assert "#include <hip" not in text and "hipMalloc" not in text

@@ -41,8 +41,8 @@ static void check_cut(const std::vector<J> &jobs, uint32_t tiles, uint32_t cap)
 	const uint64_t es = sizeof *jobs.data()->d_sin;
 	std::vector<FmSpan> spans;
 	uint32_t live = 0;
-	fmob_cut(jobs.size(), jobs.data(), tiles, cap, &spans, &live);
-	EXPECT(spans.size() == fmob_count_spans(jobs.size(), jobs.data(), tiles, cap));
+	span_cut(kFmobRule, jobs.size(), FmJobs(jobs.data()), tiles, cap, &spans, &live);
+	EXPECT(spans.size() == span_count(kFmobRule, jobs.size(), FmJobs(jobs.data()), tiles, cap));
 	size_t at = 0;
 	uint32_t seen = 0;
 	for (size_t k = 0; k < jobs.size(); k++) {
@@ -67,17 +67,17 @@ static void check_cut(const std::vector<J> &jobs, uint32_t tiles, uint32_t cap)
 			EXPECT(s.n >= 1 && s.n <= jb.n - done);
 			EXPECT(s.start == seen && s.part0 == first && s.idx == at - first);
 			const bool is_first = done == 0, is_last = done + s.n == jb.n;
-			EXPECT(s.flags == ((is_first ? kFmSpanFirst : 0u)
-				| (is_last ? kFmSpanLast : 0u)));
+			EXPECT(s.flags == ((is_first ? kSpanFirst : 0u)
+				| (is_last ? kSpanLast : 0u)));
 			if (!is_last) {		// whole tiles, all of one length
-				EXPECT(s.n % kFmobTile == 0);
+				EXPECT(s.n % kFmobRule.unit == 0);
 				EXPECT(full == 0 || s.n == full);
 				full = s.n;
 			} else {
 				EXPECT(full == 0 || s.n <= full);
 			}
 			if (full) {		// T, or T doubled
-				const uint64_t p = full / kFmobTile;
+				const uint64_t p = full / kFmobRule.unit;
 				EXPECT(p >= tiles && p % tiles == 0
 					&& !((p / tiles) & (p / tiles - 1)));
 			}
@@ -88,8 +88,8 @@ static void check_cut(const std::vector<J> &jobs, uint32_t tiles, uint32_t cap)
 		const size_t count = at - first;
 		EXPECT(count <= cap);
 		// doubled only as far as the cap asks
-		const uint64_t nt = fmob_tiles_of(jb.n);
-		const uint64_t tj = fmob_job_tiles(jb.n, tiles, cap);
+		const uint64_t nt = span_units_of(kFmobRule, jb.n);
+		const uint64_t tj = span_job_units(kFmobRule, jb.n, tiles, cap);
 		EXPECT(count == (nt + tj - 1) / tj);
 		EXPECT(tj == tiles || (nt + tj / 2 - 1) / (tj / 2) > cap);
 		seen++;
@@ -106,10 +106,13 @@ static void check_counts()
 	const uint64_t c3[] = {0, 1, 1, 1, 2, 3};
 	for (int i = 0; i < 6; i++) {
 		const cordic_fmosc_job j = job_at<cordic_fmosc_job>(0, lens[i], true, true, true);
-		EXPECT(fmob_count_spans(1, &j, 1, kFmobMaxSpans) == t1[i]);
-		EXPECT(fmob_count_spans(1, &j, 2, kFmobMaxSpans) == t2[i]);
-		EXPECT(fmob_count_spans(1, &j, 1, 3) == c3[i]);
+		EXPECT(span_count(kFmobRule, 1, FmJobs(&j), 1, kFmobRule.max_spans) == t1[i]);
+		EXPECT(span_count(kFmobRule, 1, FmJobs(&j), 2, kFmobRule.max_spans) == t2[i]);
+		EXPECT(span_count(kFmobRule, 1, FmJobs(&j), 1, 3) == c3[i]);
 	}
+	auto fmob_job_tiles = [](uint64_t n, uint32_t tiles, uint32_t cap) {
+		return span_job_units(kFmobRule, n, tiles, cap);
+	};
 	EXPECT(fmob_job_tiles(5 * 4096 + 3, 1, 3) == 2 && fmob_job_tiles(9 * 4096, 1, 3) == 4);
 	EXPECT(fmob_job_tiles(9 * 4096, 1, 1024) == 1 && fmob_job_tiles(4097, 2, 1) == 2);
 	EXPECT(fmob_job_tiles(1025 * 4096, 1, 1024) == 2);
@@ -125,16 +128,17 @@ template <typename J> static void check_container()
 		jobs.push_back(job_at<J>(k, lens[k], k % 2 == 0, k % 3 != 1, k % 3 != 0));
 	EXPECT(fmob_jobs_valid(jobs.size(), jobs.data()));
 	for (uint32_t t = 1; t <= 16; t *= 2) {		// every forced T
-		check_cut(jobs, t, kFmobMaxSpans);
+		check_cut(jobs, t, kFmobRule.max_spans);
 		check_cut(jobs, t, 3);			// a forced span cap of 3
 		check_cut(jobs, t, 1);
 	}
 	check_cut(jobs, 1, 7);
-	check_cut(std::vector<J>(), 1, kFmobMaxSpans);
+	check_cut(std::vector<J>(), 1, kFmobRule.max_spans);
 	{	// a job of the greatest length stays within the cap
 		std::vector<J> big(1, job_at<J>(0, ~(size_t)0 >> 4, false, false, true));
-		EXPECT(fmob_count_spans(1, big.data(), 1, kFmobMaxSpans) <= kFmobMaxSpans);
-		EXPECT(fmob_count_spans(1, big.data(), 1, 3) <= 3);
+		EXPECT(span_count(kFmobRule, 1, FmJobs(big.data()), 1, kFmobRule.max_spans)
+			<= kFmobRule.max_spans);
+		EXPECT(span_count(kFmobRule, 1, FmJobs(big.data()), 1, 3) <= 3);
 	}
 
 	// every refusal of the job check
@@ -197,20 +201,23 @@ int main()
 	check_container<cordic_fmosc_job16>();
 
 	// T by the bank's size: the longest span that leaves 4 per resident block
+	auto fmob_tiles = [](uint64_t total_tiles, int cus, int blocks_per_cu) {
+		return span_base_units(kFmobRule, total_tiles, cus, blocks_per_cu);
+	};
 	EXPECT(fmob_tiles(0, 256, 2) == 1 && fmob_tiles(4095, 256, 2) == 1);
 	EXPECT(fmob_tiles(4096, 256, 2) == 2 && fmob_tiles(4096, 256, 1) == 4);
 	EXPECT(fmob_tiles(16384, 256, 2) == 8 && fmob_tiles(16384, 0, 2) == 8);
 	EXPECT(fmob_tiles(16384, 256, 0) == 16);	// (no count: one block per CU)
-	EXPECT(fmob_tiles(~(uint64_t)0, 1, 1) == kFmobMaxTiles);
+	EXPECT(fmob_tiles(~(uint64_t)0, 1, 1) == kFmobRule.max_units);
 	// the knobs
-	EXPECT(fmob_forced_tiles(nullptr, 4) == 4 && fmob_forced_tiles("8", 4) == 8);
-	EXPECT(fmob_forced_tiles("3", 4) == 4 && fmob_forced_tiles("0", 4) == 4);
-	EXPECT(fmob_forced_tiles("-2", 4) == 4 && fmob_forced_tiles("x", 4) == 4);
-	EXPECT(fmob_forced_tiles("262144", 4) == 262144);
-	EXPECT(fmob_forced_tiles("524288", 4) == 4);
-	EXPECT(fmob_forced_cap(nullptr) == 1024 && fmob_forced_cap("3") == 3);
-	EXPECT(fmob_forced_cap("0") == 1024 && fmob_forced_cap("1024") == 1024);
-	EXPECT(fmob_forced_cap("99999") == 1024 && fmob_forced_cap("1023") == 1023);
+	EXPECT(span_forced_base(kFmobRule, nullptr, 4) == 4 && span_forced_base(kFmobRule, "8", 4) == 8);
+	EXPECT(span_forced_base(kFmobRule, "3", 4) == 4 && span_forced_base(kFmobRule, "0", 4) == 4);
+	EXPECT(span_forced_base(kFmobRule, "-2", 4) == 4 && span_forced_base(kFmobRule, "x", 4) == 4);
+	EXPECT(span_forced_base(kFmobRule, "262144", 4) == 262144);
+	EXPECT(span_forced_base(kFmobRule, "524288", 4) == 4);
+	EXPECT(span_forced_cap(kFmobRule, nullptr) == 1024 && span_forced_cap(kFmobRule, "3") == 3);
+	EXPECT(span_forced_cap(kFmobRule, "0") == 1024 && span_forced_cap(kFmobRule, "1024") == 1024);
+	EXPECT(span_forced_cap(kFmobRule, "99999") == 1024 && span_forced_cap(kFmobRule, "1023") == 1023);
 	if (!failures)
 		std::printf("cutter ok\n");
 	return failures ? 1 : 0;

@@ -334,6 +334,35 @@ ABI = {
                                       C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]),
     "cordic_mixbank_run": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_rx_workspace": (C.c_size_t, [C.c_void_p, _cfgp, C.c_size_t]),
+    "cordic_plan_fm_rx16_workspace": (C.c_size_t, [C.c_void_p, _cfgp,
+                                                   C.c_size_t]),
+    "cordic_plan_fm_rx_info": (C.c_int, [C.c_void_p, _cfgp,
+                                         C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
+    "cordic_plan_fm_rx16_info": (C.c_int, [C.c_void_p, _cfgp,
+                                           C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32)]),
+    "cordic_plan_fm_rx": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t, C.c_void_p,
+                                    C.c_void_p, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_rx16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_rxbank_create": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                       C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cordic_rxbank_create16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                         C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cordic_rxbank_destroy": (None, [C.c_void_p]),
+    "cordic_rxbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32)]),
+    "cordic_rxbank_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cordic_table_bank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                            C.POINTER(C.c_void_p)]),
     "cordic_table_bank_create16": (C.c_int, [C.c_void_p, C.c_size_t,
@@ -653,6 +682,72 @@ class Plan:
             self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
             _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
             "cordic_plan_fm_mix16")
+
+    def fm_rx_workspace(self, conv, n):
+        """cordic_plan_fm_rx_workspace: bytes of device scratch an fm_rx call
+        of n samples into the converter `conv` needs (16-byte aligned)"""
+        return int(lib().cordic_plan_fm_rx_workspace(
+            self._h, conv.ref if conv is not None else None, n))
+
+    def fm_rx16_workspace(self, conv, n):
+        """cordic_plan_fm_rx16_workspace: the same for fm_rx16"""
+        return int(lib().cordic_plan_fm_rx16_workspace(
+            self._h, conv.ref if conv is not None else None, n))
+
+    def _fm_rx_info(self, name, conv):
+        fused, tile = C.c_int32(0), C.c_int32(0)
+        _check(getattr(lib(), name)(
+            self._h, conv.ref if conv is not None else None, C.byref(fused),
+            C.byref(tile)), name)
+        return int(fused.value), int(tile.value)
+
+    def fm_rx_info(self, conv):
+        """cordic_plan_fm_rx_info: (fused, tile) -- whether fm_rx into the
+        converter `conv` runs the fused kernel, and the samples a block makes
+        per pass"""
+        return self._fm_rx_info("cordic_plan_fm_rx_info", conv)
+
+    def fm_rx16_info(self, conv):
+        """cordic_plan_fm_rx16_info: the same for fm_rx16"""
+        return self._fm_rx_info("cordic_plan_fm_rx16_info", conv)
+
+    def _fm_rx(self, name, wsize, conv, fcw, x, y, mag, freq, work, pm, n,
+               phase0, acc, dphase0, last, stream):
+        n = x.numel() if n is None else n
+        if work is None and n:
+            raise TypeError("work: a device buffer of %s(conv, n) bytes"
+                            % wsize.__name__)
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and work.numel() * work.element_size() < wsize(conv, n):
+            raise ValueError("work: %d bytes, %s(conv, %d) = %d"
+                             % (work.numel() * work.element_size(),
+                                wsize.__name__, n, wsize(conv, n)))
+        _check(getattr(lib(), name)(
+            self._h, conv.ref if conv is not None else None, n, _ptr(fcw),
+            _ptr(pm), phase0 & 0xffffffff, _ptr(acc), _ptr(x), _ptr(y),
+            dphase0 & 0xffffffff, _ptr(last), _ptr(mag), _ptr(freq),
+            _ptr(work), _stream(stream)), name)
+
+    def fm_rx(self, conv, fcw, x, y, mag, freq, work=None, pm=None, n=None,
+              phase0=0, acc=None, dphase0=0, last=None, stream=None):
+        """cordic_plan_fm_rx: fm_mix and fm_demod (on the r2p / sr2p core
+        `conv`) in one call, the tuned I/Q never stored: mag and freq are what
+        fm_demod gives on fm_mix's outputs.  acc and last (one-word device
+        tensors, optional) carry the oscillator and the discriminator from
+        call to call.  work: device scratch of fm_rx_workspace(conv, n) bytes
+        (16-byte aligned), the caller's."""
+        self._fm_rx("cordic_plan_fm_rx", self.fm_rx_workspace, conv, fcw, x, y,
+                    mag, freq, work, pm, n, phase0, acc, dphase0, last, stream)
+
+    def fm_rx16(self, conv, fcw, x, y, mag, freq, work=None, pm=None, n=None,
+                phase0=0, acc=None, dphase0=0, last=None, stream=None):
+        """cordic_plan_fm_rx16: fm_rx on int16 x, y, mag, freq (both cores
+        within the 16-bit containers); fcw, pm, acc and last stay 32-bit
+        words.  work: fm_rx16_workspace(conv, n) bytes."""
+        _same16("cordic_plan_fm_rx16", x, y, mag, freq)
+        self._fm_rx("cordic_plan_fm_rx16", self.fm_rx16_workspace, conv, fcw,
+                    x, y, mag, freq, work, pm, n, phase0, acc, dphase0, last,
+                    stream)
 
     @property
     def queue_info(self):
@@ -2047,6 +2142,95 @@ class MixBank16(MixBank):
                 else tuple(jb)
             _same16(self._create, *jb[2:6])
         MixBank.__init__(self, plan, jobs)
+
+
+class _CFmRxJob(C.Structure):
+    """cordic_fmrx_job"""
+    _fields_ = [("d_fcw", C.c_void_p), ("d_pm", C.c_void_p),
+                ("d_xval", C.c_void_p), ("d_yval", C.c_void_p),
+                ("d_omag", C.c_void_p), ("d_ofreq", C.c_void_p),
+                ("d_acc", C.c_void_p), ("d_last", C.c_void_p),
+                ("n", C.c_uint64), ("phase0", C.c_uint32),
+                ("dphase0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+_FMRX_KEYS = ("fcw", "pm", "x", "y", "mag", "freq", "n", "phase0", "acc",
+              "dphase0", "last")
+
+
+class RxBank:
+    """cordic_rxbank: many fm_rx jobs of one p2r / sp2r plan and one r2p /
+    sr2p converter, cut once and run in two launches.  jobs: tuples (fcw, pm,
+    x, y, mag, freq, n, phase0, acc, dphase0, last) or dicts with those keys;
+    fcw, x, y, mag, freq are int32 tensors or device addresses, pm one more or
+    None, acc and last one-word device tensors or None; n None: fcw.numel().
+    The plan must stay open as long as the bank; conv is copied."""
+
+    _create = "cordic_rxbank_create"
+
+    def __init__(self, plan, conv, jobs):
+        jobs = [tuple(jb.get(k) for k in _FMRX_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
+        arr = (_CFmRxJob * max(1, len(jobs)))()
+        for k, (fcw, pm, x, y, mag, freq, n, phase0, acc, dphase0, last) \
+                in enumerate(jobs):
+            arr[k].d_fcw = _ptr(fcw)
+            arr[k].d_pm = _ptr(pm)
+            arr[k].d_xval = _ptr(x)
+            arr[k].d_yval = _ptr(y)
+            arr[k].d_omag = _ptr(mag)
+            arr[k].d_ofreq = _ptr(freq)
+            arr[k].d_acc = _ptr(acc)
+            arr[k].d_last = _ptr(last)
+            arr[k].n = fcw.numel() if n is None else n
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+            arr[k].dphase0 = (dphase0 or 0) & 0xffffffff
+        h = C.c_void_p()
+        _check(getattr(lib(), self._create)(
+            getattr(plan, "_h", plan), conv.ref if conv is not None else None,
+            len(jobs), arr, C.byref(h)), self._create)
+        self._h = h
+
+    def info(self):
+        a, b = C.c_uint64(), C.c_uint32()
+        c, d = C.c_int32(), C.c_int32()
+        _check(lib().cordic_rxbank_info(self._h, C.byref(a), C.byref(b),
+                                        C.byref(c), C.byref(d)),
+               "cordic_rxbank_info")
+        return dict(samples=a.value, spans=b.value, fused=c.value,
+                    tile=d.value)
+
+    def run(self, stream=None):
+        _check(lib().cordic_rxbank_run(self._h, _stream(stream)),
+               "cordic_rxbank_run")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().cordic_rxbank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RxBank16(RxBank):
+    """cordic_rxbank_create16: an RxBank of fm_rx16 jobs -- x, y, mag, freq
+    are int16 tensors or device addresses (cordic_fmrx_job16 has the layout of
+    cordic_fmrx_job); fcw, pm, acc and last stay 32-bit.  info, run and close
+    are RxBank's."""
+
+    _create = "cordic_rxbank_create16"
+
+    def __init__(self, plan, conv, jobs):
+        for jb in jobs:
+            jb = tuple(jb.get(k) for k in _FMRX_KEYS) if isinstance(jb, dict) \
+                else tuple(jb)
+            _same16(self._create, *jb[2:6])
+        RxBank.__init__(self, plan, conv, jobs)
 
 
 class _CHostStats(C.Structure):

@@ -1,5 +1,5 @@
 // cordic_abi.cpp -- the extern "C" surface declared in include/cordic_amd.h:
-// plans, job sets, FM mixer banks, the int16 calls, the config and stateless
+// plans, job sets, FM mixer banks, the tuned FM receiver, the int16 calls, the config and stateless
 // wrappers.  (Table, quadratic and oscillator-bank handles:
 // cordic_abi_table.cpp; the clocked views: cordic_abi_clocked.cpp.)  Thin by
 // design: argument checks, then the host layer (cordic_config.cpp) or the
@@ -17,6 +17,8 @@
 #include "cordic_devmem.h"
 #include "cordic_fm_mix.h"
 #include "cordic_fm_mix_bank.h"
+#include "cordic_fm_rx.h"
+#include "cordic_fm_rx_bank.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_queue_ring.h"
@@ -369,6 +371,253 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 		return cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
 			jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval, bank->d_work,
 			stream);
+	});
+}
+
+// ---- the tuned FM receiver: that mixer and the FM discriminator in one kernel
+// (cordic_fm_rx.h).  The status codes are those of the two calls, the mixer's
+// first: the plan (ARGS, MODE), then the converter (ARGS, MODE, ARGS) and, for
+// the 16-bit form, the plan's container, then the converter's.
+static int fm_rx_ok(const cordic_plan *plan, const cordic_config *conv, bool io16)
+{
+	if (!plan || !conv)
+		return CORDIC_ERR_ARGS;
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	if (int rc = fmd_check_core(conv))
+		return rc;
+	if (!io16)
+		return CORDIC_OK;
+	if (int rc = fits16(plan->cfg, false))
+		return rc;
+	return fits16(*conv, true);
+}
+
+static bool fm_rx_fused(const cordic_plan *plan, const cordic_config *conv, bool io16)
+{
+	return (io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan))
+		&& fmrx_conv_is_fused(*conv);
+}
+
+static size_t fm_rx_mix_bytes(const cordic_plan *plan, size_t n, bool io16)
+{
+	return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(fm_mix_fused(plan), n);
+}
+
+static size_t fm_rx_work_bytes(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, bool io16)
+{
+	return fmrx_work_bytes(fm_rx_fused(plan, conv, io16), fm_rx_mix_bytes(plan, n, io16),
+		n, io16 ? 2 : 4);
+}
+
+static int fm_rx_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile, bool io16)
+{
+	if (int rc = fm_rx_ok(plan, conv, io16))
+		return rc;
+	const bool f = fm_rx_fused(plan, conv, io16);
+	if (fused)
+		*fused = f ? 1 : 0;
+	if (tile)
+		*tile = f ? (int32_t)kFmrxPass : 0;
+	return CORDIC_OK;
+}
+
+static int fm_rx(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const void *d_xval, const void *d_yval, uint32_t dphase0,
+		uint32_t *d_last, void *d_omag, void *d_ofreq, void *d_work, void *stream,
+		bool io16)
+{
+	if (int rc = fm_rx_ok(plan, conv, io16))
+		return rc;
+	if (n == 0)
+		return CORDIC_OK;
+	const size_t es = io16 ? 2 : 4;
+	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_last, d_omag,
+			d_ofreq, es, d_work, fm_rx_work_bytes(plan, conv, n, io16)))
+		return rc;
+	if (fm_rx_fused(plan, conv, io16))
+		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
+			phase0, d_acc, d_xval, d_yval, dphase0, d_last, d_omag, d_ofreq, es,
+			d_work, stream);
+	// the fallback: the mixer into two arrays inside d_work -- [its workspace |
+	// tuned x | tuned y | the discriminator's workspace] -- and the
+	// discriminator from them
+	unsigned char *w = static_cast<unsigned char *>(d_work);
+	const size_t at = fm_rx_mix_bytes(plan, n, io16), each = fmrx_array_bytes(n, es);
+	void *tx = w + at, *ty = w + at + each, *dw = w + at + 2 * each;
+	if (io16) {
+		if (int rc = cordic_plan_fm_mix16(plan, n, d_fcw, d_pm, phase0, d_acc,
+				static_cast<const int16_t *>(d_xval),
+				static_cast<const int16_t *>(d_yval), static_cast<int16_t *>(tx),
+				static_cast<int16_t *>(ty), d_work, stream))
+			return rc;
+		return cordic_fm_demod16(conv, n, static_cast<const int16_t *>(tx),
+			static_cast<const int16_t *>(ty), dphase0, d_last,
+			static_cast<int16_t *>(d_omag), static_cast<int16_t *>(d_ofreq), dw, stream);
+	}
+	if (int rc = cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc,
+			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
+			static_cast<int32_t *>(tx), static_cast<int32_t *>(ty), d_work, stream))
+		return rc;
+	return cordic_fm_demod(conv, n, static_cast<const int32_t *>(tx),
+		static_cast<const int32_t *>(ty), dphase0, d_last,
+		static_cast<int32_t *>(d_omag), static_cast<int32_t *>(d_ofreq), dw, stream);
+}
+
+size_t cordic_plan_fm_rx_workspace(const cordic_plan *plan, const cordic_config *conv,
+		size_t n)
+{
+	return fm_rx_ok(plan, conv, false) == CORDIC_OK
+		? fm_rx_work_bytes(plan, conv, n, false) : 0;
+}
+
+size_t cordic_plan_fm_rx16_workspace(const cordic_plan *plan, const cordic_config *conv,
+		size_t n)
+{
+	return fm_rx_ok(plan, conv, true) == CORDIC_OK
+		? fm_rx_work_bytes(plan, conv, n, true) : 0;
+}
+
+int cordic_plan_fm_rx_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile)
+{
+	return fm_rx_info(plan, conv, fused, tile, false);
+}
+
+int cordic_plan_fm_rx16_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile)
+{
+	return fm_rx_info(plan, conv, fused, tile, true);
+}
+
+int cordic_plan_fm_rx(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last, int32_t *d_omag, int32_t *d_ofreq,
+		void *d_work, void *stream)
+{
+	return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
+		d_last, d_omag, d_ofreq, d_work, stream, false);
+}
+
+int cordic_plan_fm_rx16(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_xval, const int16_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq,
+		void *d_work, void *stream)
+{
+	return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
+		d_last, d_omag, d_ofreq, d_work, stream, true);
+}
+
+// ---- receiver banks: many of those jobs in two launches (cordic_fm_rx_bank.h)
+struct cordic_rxbank : BankHandle<cordic_fmrx_job> {
+	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
+	cordic_config conv;			// a copy
+	bool	io16 = false;			// the jobs' sample arrays hold int16
+	uint32_t passes = 0;
+	SpanTable<RxSpan> spans;		// fused
+	uint32_t *d_conv = nullptr;		// fused: conv's kernel parameters
+};
+
+// both creates: `jobs` is either job struct (RxJobs, cordic_fm_rx_bank.h)
+static int rxbank_create(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, RxJobs jobs, cordic_rxbank **bank)
+{
+	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
+	if (!bank || (njobs && jobs.none()))
+		return CORDIC_ERR_ARGS;
+	if (int rc = fm_rx_ok(plan, conv, io16))
+		return rc;
+	if (njobs >= ((size_t)1 << 28) || !fmrxb_jobs_valid(njobs, jobs))
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	// the handle keeps its jobs as cordic_fmrx_job, whatever the container
+	std::vector<cordic_fmrx_job> wide;
+	const cordic_fmrx_job *flat = jobs.j32;
+	if (io16) {
+		wide.reserve(njobs);
+		for (size_t k = 0; k < njobs; k++)
+			wide.push_back(jobs[k]);
+		flat = wide.data();
+	}
+	cordic_rxbank *b = nullptr;
+	if (int rc = bank_begin(njobs, flat, fm_rx_fused(plan, conv, io16),
+			[&](size_t n) { return fm_rx_work_bytes(plan, conv, n, io16); }, &b))
+		return rc;
+	b->plan = plan;
+	b->conv = *conv;
+	b->io16 = io16;
+	if (!b->fused) {
+		*bank = b;
+		return CORDIC_OK;
+	}
+	uint64_t passes = 0;
+	for (size_t k = 0; k < njobs; k++)
+		passes += span_units_of(kFmrxbRule, jobs.n(k));
+	int rc = span_table_build(&b->spans, "CORDIC_FMRXB_PASSES", "CORDIC_FMRXB_MAX_SPANS",
+			kFmrxbRule, passes, b->cus, kFmrxbBlocksPerCu, njobs, jobs, &b->passes);
+	if (!rc)
+		rc = fmrxb_upload_conv(b->conv, &b->d_conv);
+	if (rc) {
+		cordic_rxbank_destroy(b);
+		return rc;
+	}
+	*bank = b;
+	return CORDIC_OK;
+}
+
+int cordic_rxbank_create(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job *jobs, cordic_rxbank **bank)
+{
+	return rxbank_create(plan, conv, njobs, jobs, bank);
+}
+
+int cordic_rxbank_create16(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job16 *jobs, cordic_rxbank **bank)
+{
+	return rxbank_create(plan, conv, njobs, jobs, bank);
+}
+
+void cordic_rxbank_destroy(cordic_rxbank *bank)
+{
+	if (!bank)
+		return;
+	bank->spans.free();
+	dev_free(bank->d_work, bank->d_conv);
+	delete bank;
+}
+
+int cordic_rxbank_info(const cordic_rxbank *bank, uint64_t *samples, uint32_t *spans,
+		int32_t *fused, int32_t *tile)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	if (samples) *samples = bank->samples;
+	if (spans) *spans = bank->spans.nspans;
+	if (fused) *fused = bank->fused ? 1 : 0;
+	if (tile) *tile = bank->fused ? (int32_t)kFmrxPass : 0;
+	return CORDIC_OK;
+}
+
+int cordic_rxbank_run(const cordic_rxbank *bank, void *stream)
+{
+	if (!bank)
+		return CORDIC_ERR_ARGS;
+	(void)hipGetLastError();
+	const cordic_plan *plan = bank->plan;
+	return bank_run(*bank, [&] {
+		const SpanTable<RxSpan> &t = bank->spans;
+		return launch_fmrx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_conv,
+			t.d_spans, t.nspans, t.start(), t.part(), t.more(), bank->cus, bank->io16,
+			stream);
+	}, [&](const cordic_fmrx_job &jb) {
+		return fm_rx(plan, &bank->conv, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
+			jb.d_acc, jb.d_xval, jb.d_yval, jb.dphase0, jb.d_last, jb.d_omag,
+			jb.d_ofreq, bank->d_work, stream, bank->io16);
 	});
 }
 

@@ -157,13 +157,15 @@ static int bank_begin(size_t njobs, const Job *jobs, bool fused,
 // ---- What cordic_mixbank (cordic_abi.cpp) and cordic_fmbank
 // (cordic_abi_table.cpp) share, the prefix-sum banks (cordic_span_bank.h): the
 // span table on the device and the workspace of a run, [start words, one per
-// non-empty job | partial sums, one per span].
+// non-empty job | partial sums, one per span | SpanRule::words further latched
+// words per non-empty job].
 template <typename SPAN> struct SpanTable {
 	SPAN	*d_spans = nullptr;
 	uint32_t *d_words = nullptr;
 	uint32_t nspans = 0, nstarts = 0;
 	uint32_t *start() const { return d_words; }
 	uint32_t *part() const { return d_words + nstarts; }
+	uint32_t *more() const { return d_words + nstarts + nspans; }
 	void	free() { dev_free(d_spans, d_words); }
 };
 
@@ -189,7 +191,8 @@ static int span_table_build(SpanTable<SPAN> *t, const char *env_base,
 	t->nspans = (uint32_t)spans.size();
 	if (!dev_upload(spans.data(), spans.size() * sizeof(SPAN), &t->d_spans)
 			|| !dev_zalloc(&t->d_words,
-				((size_t)t->nstarts + t->nspans) * sizeof(uint32_t))) {
+				((size_t)t->nstarts * (1 + rule.words) + t->nspans)
+					* sizeof(uint32_t))) {
 		t->free();
 		return CORDIC_ERR_DEVICE;
 	}

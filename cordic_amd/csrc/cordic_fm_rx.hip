@@ -1,0 +1,319 @@
+// cordic_fm_rx.hip -- the tuned FM receiver's fused path (cordic_plan_fm_rx, and
+// cordic_plan_fm_rx16 on int16 arrays): the FM mixer (cordic_fm_mix.hip) and the
+// FM discriminator (cordic_fm_demod.hip) in one kernel, the tuned I/Q in
+// registers only,
+//   start = phase0 + *d_acc,   prev = (dphase0 + *d_last) mod 2^PW(conv)
+//   p_i   = start + fcw[0] + .. + fcw[i-1] + pm[i]      (mod 2^32)
+//   (tx_i, ty_i)  = what cordic_p2r writes for (x_i, y_i, p_i) on the plan's core
+//   (mag_i, ph_i) = what cordic_r2p writes for (tx_i, ty_i) on conv
+//   freq_i = sext_PW((ph_i - ph_(i-1)) mod 2^PW),   ph_(-1) = prev
+//   *d_acc = start + fcw[0] + .. + fcw[n-1],   *d_last = ph_(n-1).
+//
+// Reduce-then-scan in two launches, as the mixer.  The samples are cut into
+// spans of P passes of 1024 LESS 4 samples; block b owns span b.
+//   1. fm_rx_reduce: each block sums its span of fcw into a workspace word;
+//      block 0 latches the start AND prev beside them and copies the
+//      converter's kernel parameters behind them.  A job's first and last
+//      span run in different blocks of launch 2, and the last one writes
+//      *d_last: so launch 2 may not read it.
+//   2. fm_rx_xydir<LJ, NLIVE, IO>: the mixer's prologue (tables into LDS, the
+//      partials in front added to the start), then fmrx::pass_loop
+//      (cordic_fm_rx.h): scan, fmx::xydir_vector, fmd::pol_lj_vector on its
+//      registers, the differences, two stores.
+// No block waits for another.  *d_acc and *d_last are read in launch 1 only and
+// written in launch 2 only (one lane of the last block each).  Traffic: fcw
+// twice, x, y, mag, freq once: 20 bytes per sample on int32 (24 with pm), 12
+// (16) on int16, against 40 (44) and 24 (28) of the two calls.
+//
+// THE HALO.  A span that is not the call's first needs the phase ph of the
+// sample in front of it, which is the MIXER's output there put through the
+// converter.  The layout is the discriminator's: lane 0 of a span's first pass
+// holds the vector in front of the span (x, y, fcw, pm at lo - 4 .. lo - 1, all
+// inside the call's arrays), rotates and converts it with everyone else and
+// stores nothing; its phase word is carry - fcw[lo-1] + pm[lo-1], and its tuning
+// words are kept out of the scan.  A span of P passes therefore yields 1024 P -
+// 4 samples: 1/(256 P) of the arithmetic is done twice, and no pass diverges.
+// The alternative -- an extra vector through both chains by wave 0 in front of
+// the loop -- would hold the other three waves at the first barrier for a whole
+// chain (1/P of the block's time) and would inline both chains a second time.
+//
+// LDS is the tables' (dx_lds_layout) with 20 words behind them, in the DYNAMIC
+// block: the table lookups address LDS by byte offset from 0, which a static
+// __shared__ object would displace.  The trap below checks it.
+//
+// CORDIC_FMRX_MAX_BLOCKS=<n> in the environment (read at every call; a test and
+// A/B knob like CORDIC_FMX_MAX_BLOCKS) caps the grid at n blocks.  The bits do
+// not depend on it.
+//
+// The unit is compiled three times, one <LJ, container> each, so that the
+// three build beside each other: as itself (<30, Io32>, launch 1 and the host
+// side), as cordic_fm_rx_lj29.hip (<29, Io32>) and as cordic_fm_rx_io16.hip
+// (<30, Io16>).
+//
+// Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
+// .private_segment_fixed_size is 0 for every instance: nothing spills to
+// scratch; profiles/r20/fm_rx.txt):
+//   live stages              13   16   19   20   24   27   29
+//   fm_rx_xydir<29, N>      108  108  108  108  110  114  114
+//   fm_rx_xydir<30, N>      108  108  108  108  110  113  113
+//   ... <30, N, Io16>       106  106  106  106  108  111  111
+//   fm_rx_reduce             30 (64 bytes of static LDS)
+// against 92 .. 108 of fm_mix_xydir and 90 .. 94 of the dynamic-exit
+// discriminator: up to 128 registers hold 4 waves per SIMD, the mixer's own
+// occupancy, so no step is crossed and the grid is sized for 4 blocks per CU
+// (kFmrxBlocksPerCu), fewer where the tables fill LDS sooner.  Scalars: 105 ..
+// 106 of them, 0 parked in VGPR lanes (2 for 27 live stages, 4 for 29; 12 lane
+// moves in a whole unit).  With the converter's CoreParams as a kernel argument
+// that was 137 .. 160 parked scalars and some 650 v_readlane / v_writelane per
+// kernel, about one per multiply-add of the converter's chain, and the call ran
+// at 0.86 .. 0.96 of the two calls; hence the parameters in the workspace
+// (conv_params, cordic_fm_rx.h).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+
+#include "cordic_xydir.h"
+#include "cordic_launch.h"
+#include "cordic_jobs_fused.h"
+#include "cordic_table_nco.h"
+#include "cordic_hostargs.h"
+#include "cordic_fm_rx.h"
+
+#ifndef CORDIC_FMRX_UNIT
+#define CORDIC_FMRX_UNIT 30	// 30: <30, Io32> and the host side; 29; 16
+#endif
+
+namespace cordic_amd {
+
+namespace fmrx {
+
+using namespace dev;
+
+template <int LJ, int NLIVE, typename IO>
+__global__ __launch_bounds__(kBlock) void fm_rx_xydir(CoreParams kp, DirArgs da,
+		RxArgs a)
+{
+	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
+	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
+		"16-bit ports and WW 35: the fallback (fmx_is_fused16)");
+	typedef typename IO::ielem ielem;
+	constexpr int kN = dx_levels(NLIVE);
+	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
+	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+	const unsigned tid = threadIdx.x;
+	// (the same in all of a wave's lanes: said so, it stays in a scalar)
+	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
+	dx_lds_layout(da.dx, bk_base, lf_base);
+
+	// ---- prologue, the mixer's: the tables, and the waves' shares of the
+	// partials in front of this block (ex[8 .. 12))
+	fmx::stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	uint32_t *ex = lds + a.xw / 4u;
+	fmx::front_sum(a.work + 4, blockIdx.x, ex, tid, wave);
+	__syncthreads();
+
+	// LDS is addressed by byte offset from 0: no static LDS in this kernel
+	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
+		__builtin_trap();
+
+	const fmx::RotRegs rr = fmx::rot_regs<LJ, NLIVE>(kp, da);
+	// the converter's parameters: launch 1 left them in the workspace
+	const uint32_t *ckmem = a.work + kFmrxConvAt / 4;
+	const fmd::LaneConsts ln(conv_params(ckmem, false));
+	const size_t lo = (size_t)blockIdx.x * a.span;	// < n by the grid
+	const size_t cnt = (a.n - lo < a.span) ? a.n - lo : a.span;
+	const bool tail = blockIdx.x == gridDim.x - 1;
+	// the phase of sample lo, without its pm
+	uint32_t carry = a.work[0] + ex[8] + ex[9] + ex[10] + ex[11];
+	unsigned par = 0;
+	pass_loop<LJ, NLIVE>(kp, da, rr, bk_base, ckmem, ln, a.fcw + lo,
+		a.pm ? a.pm + lo : nullptr, static_cast<const ielem *>(a.x) + lo,
+		static_cast<const ielem *>(a.y) + lo, static_cast<ielem *>(a.mag) + lo,
+		static_cast<ielem *>(a.freq) + lo, cnt, blockIdx.x == 0, a.work[1],
+		tail ? a.last : nullptr, carry, par, ex, tid, wave, IO{});
+	if (a.acc && tail && tid == 0)
+		*a.acc = carry;
+}
+
+template <int LJ, typename IO>
+static bool launch_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
+{
+	switch (nlive) {
+#define X(N) case N: \
+	if (da.dx.n != dx_levels(N)) \
+		return false; \
+	hipLaunchKernelGGL((fm_rx_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
+		kp, da, a); \
+	return true;
+	FMX_STAGES(X)
+#undef X
+	default:
+		return false;
+	}
+}
+
+#if CORDIC_FMRX_UNIT == 29
+bool launch_rx_lj29(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
+{
+	return launch_lj<29, Io32>(nlive, grid, lds, st, kp, da, a);
+}
+#elif CORDIC_FMRX_UNIT == 16
+bool launch_rx_io16(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
+{
+	return launch_lj<30, Io16>(nlive, grid, lds, st, kp, da, a);
+}
+#else
+bool launch_rx_lj30(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
+{
+	return launch_lj<30, Io32>(nlive, grid, lds, st, kp, da, a);
+}
+
+// Four consecutive words at any 4-byte-aligned address: one dwordx4 load
+// (span_words4, cordic_span_reduce.h)
+typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// launch 1: work[4 + b] = the sum of block b's span [b * span, (b + 1) * span)
+// of fcw (cut at n); block 0: work[0] = phase0 + *d_acc, work[1] = (dphase0 +
+// *d_last) & pmask, and the converter's parameters at kFmrxConvAt.  fm_reduce
+// (cordic_table_fm.hip) with the second latch.
+struct ConvWords {
+	uint32_t w[sizeof(CoreParams) / 4];
+};
+static_assert(sizeof(CoreParams) <= kFmrxConvBytes && sizeof(CoreParams) % 4 == 0
+	&& kFmrxConvAt % 16 == 0, "the converter's parameters in the workspace");
+
+__global__ __launch_bounds__(1024) void fm_rx_reduce(const uint32_t *d_fcw, size_t n,
+		size_t span, uint32_t phase0, const uint32_t *d_acc, uint32_t dphase0,
+		const uint32_t *d_last, uint32_t pmask, uint32_t *work, ConvWords ck)
+{
+	__shared__ uint32_t wsum[16];
+	const unsigned tid = threadIdx.x;
+	if (blockIdx.x == 0 && tid < sizeof(CoreParams) / 4)
+		work[kFmrxConvAt / 4 + tid] = ck.w[tid];
+	const size_t lo = (size_t)blockIdx.x * span;	// < n by the grid
+	const size_t len = (n - lo < span) ? n - lo : span;
+	const uint32_t *f = d_fcw + lo;
+	const words4 *fv = reinterpret_cast<const words4 *>(f);
+	const size_t nv = len / 4;
+	uint32_t s = 0;
+#pragma unroll 4
+	for (size_t g = tid; g < nv; g += 1024) {
+		const words4 q = fv[g];
+		s += q[0] + q[1] + q[2] + q[3];
+	}
+	const size_t r = nv * 4 + tid;	// fewer than 4 behind the vectors
+	if (r < len)
+		s += f[r];
+#pragma unroll
+	for (int k = 32; k; k >>= 1)
+		s += __shfl_xor(s, k);
+	if ((tid & 63u) == 0)
+		wsum[tid >> 6] = s;
+	__syncthreads();
+	if (tid == 0) {
+		uint32_t sum = 0;
+#pragma unroll
+		for (int j = 0; j < 16; j++)
+			sum += wsum[j];
+		work[4 + blockIdx.x] = sum;
+		if (blockIdx.x == 0) {
+			work[0] = phase0 + (d_acc ? *d_acc : 0u);
+			work[1] = (dphase0 + (d_last ? *d_last : 0u)) & pmask;
+		}
+	}
+}
+#endif
+
+} // namespace fmrx
+
+#if CORDIC_FMRX_UNIT == 30
+bool fmrx_conv_is_fused(const cordic_config &conv)
+{
+	return fmd_core_is_fused(conv) && !(conv.flags & CORDIC_FLAG_UNIT_GAIN);
+}
+
+int fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
+		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
+		size_t esize, const void *d_work, size_t work_bytes)
+{
+	if (!d_fcw || !d_xval || !d_yval || !d_omag || !d_ofreq || !d_work
+			|| n > (~(size_t)0 >> 4))
+		return CORDIC_ERR_ARGS;
+	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
+		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc)
+		| reinterpret_cast<uintptr_t>(d_last);
+	const uintptr_t samples = reinterpret_cast<uintptr_t>(d_xval)
+		| reinterpret_cast<uintptr_t>(d_yval) | reinterpret_cast<uintptr_t>(d_omag)
+		| reinterpret_cast<uintptr_t>(d_ofreq);
+	if ((words & 3u) || (samples & (esize - 1))
+			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
+		return CORDIC_ERR_ARGS;
+	const Range out[5] = {range_of(d_omag, n * esize), range_of(d_ofreq, n * esize),
+		range_of(d_acc, 4), range_of(d_last, 4), range_of(d_work, work_bytes)};
+	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
+		range_of(d_xval, n * esize), range_of(d_yval, n * esize)};
+	return outputs_overlap(out, in) ? CORDIC_ERR_ARGS : CORDIC_OK;
+}
+
+int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
+		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
+		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
+		void *d_ofreq, size_t esize, void *d_work, void *stream)
+{
+	using namespace fmrx;
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	if (n == 0)
+		return CORDIC_OK;
+	hipStream_t st = static_cast<hipStream_t>(stream);
+	const int cus = jobs_cus_now();
+	if (cus < 0) {
+		(void)hipGetLastError();
+		return CORDIC_ERR_DEVICE;
+	}
+	uint32_t xw = 0;
+	const size_t lds = lds_bytes(dx, &xw);
+	size_t cap = (size_t)cus * blocks_per_cu(lds);
+	if (cap > kFmrxMaxBlocks)
+		cap = kFmrxMaxBlocks;
+	cap = env_block_cap("CORDIC_FMRX_MAX_BLOCKS", cap);
+	// a span of p passes yields 1024 p - 4 samples: p for at most `cap` spans
+	// (a one-pass span yields 1020, a p-pass span at least 1020 p)
+	const size_t yield1 = kFmrxPass - kFmrxHalo;
+	const size_t npass = (n + yield1 - 1) / yield1;
+	const size_t per_block = (npass + cap - 1) / cap;
+	const size_t span = per_block * kFmrxPass - kFmrxHalo;
+	const unsigned grid = (unsigned)((n + span - 1) / span);
+	// the instance first: nothing is enqueued for a core without one
+	if (!fmx_is_fused(cfg, d_dir, dx) || (esize == 2 && cfg.ww >= 35))
+		return tnco::finish(false);
+	uint32_t *work = static_cast<uint32_t *>(d_work);
+	const uint32_t pmask = 0xffffffffu >> (32 - conv.pw);
+	const CoreParams ck = make_params_jobs(conv);
+	ConvWords cw;
+	memcpy(&cw, &ck, sizeof cw);
+	hipLaunchKernelGGL(fm_rx_reduce, dim3(grid), dim3(1024), 0, st, d_fcw, n, span,
+		phase0, (const uint32_t *)d_acc, dphase0, (const uint32_t *)d_last, pmask,
+		work, cw);
+	const RxArgs a{d_fcw, d_pm, d_acc, d_last, work, d_xval, d_yval, d_omag, d_ofreq,
+		n, span, xw};
+	const DirArgs da{d_dir, dx};
+	const CoreParams kp = make_params_jobs(cfg);
+	const bool done = esize == 2
+		? cfg.ww < 35 && launch_rx_io16(cfg.nlive, grid, lds, st, kp, da, a)
+		: cfg.ww == 35
+			? launch_rx_lj29(cfg.nlive, grid, lds, st, kp, da, a)
+			: launch_rx_lj30(cfg.nlive, grid, lds, st, kp, da, a);
+	return tnco::finish(done);
+}
+#endif
+
+} // namespace cordic_amd

@@ -1,0 +1,112 @@
+// cordic_fm_rx_bank.h -- receiver banks: many cordic_plan_fm_rx jobs of one
+// plan and one converter in TWO launches (include/cordic_amd.h, "Tuned FM
+// receiver"), on int32 or on int16 arrays (cordic_fmrx_job / cordic_fmrx_job16).
+// What the bank adds to the prefix-sum banks' shared host layer
+// (cordic_span_bank.h) -- its rule, with a halo and a second latched word per
+// job, its span descriptor, its job check; plain C++ that touches no device, so
+// that a stand-alone program can run it under a sanitizer
+// (tests/test_fm_rx_host.py) -- and the launcher of the two kernels that walk
+// the descriptors (cordic_fm_rx_bank.hip).  Host-visible types only; the handle
+// and its entry points live with the plan, in cordic_abi.cpp.
+//
+// No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
+// does not hash this unit.
+#ifndef CORDIC_FM_RX_BANK_H
+#define CORDIC_FM_RX_BANK_H
+
+#include <array>
+#include <cstddef>
+#include <cstdint>
+
+#include "cordic_amd.h"
+#include "cordic_bank_host.h"
+#include "cordic_span_bank.h"
+
+namespace cordic_amd {
+
+// The bank's descriptor: a mixer bank's (the common head of a span around the
+// addresses of the four sample arrays at the span's first sample) and, behind
+// it, the job's d_last and dphase0, which the job's first span latches and its
+// last span writes.  A span's first vector is the halo (fmrx::pass_loop): a span
+// of P passes has 1024 P - 4 samples, and what lies in front of a span that is
+// not its job's first is inside the job.
+struct RxSpan {
+	uint64_t fcw, pm;
+	uint64_t x, y, mag, freq;
+	uint64_t acc;
+	uint64_t n;
+	uint32_t start;
+	uint32_t part0;
+	uint32_t idx;
+	uint32_t flags;
+	uint32_t phase0;
+	uint32_t pad;
+	uint64_t last;
+	uint32_t dphase0;
+	uint32_t pad2;
+};				// 104 bytes
+static_assert(sizeof(RxSpan) == 104, "the descriptor is read as scalar words");
+
+// passes of 1024 samples (= kFmrxPass) with a halo of 4 (= kFmrxHalo); at most
+// 4096 spans per job; a base span of at most 2^20 passes; one further latched
+// word per job.  The knobs, read at create: CORDIC_FMRXB_PASSES,
+// CORDIC_FMRXB_MAX_SPANS.
+constexpr SpanRule kFmrxbRule = {1024, 4096, 1u << 20, 4, 1};
+constexpr int	   kFmrxbBlocksPerCu = 3;	// by its registers (cordic_fm_rx_bank.hip)
+
+// The jobs of a create, of either struct (JobView, cordic_span_bank.h)
+typedef JobView<cordic_fmrx_job, cordic_fmrx_job16> RxJobs;
+#define F(f) CORDIC_SAME_FIELD(cordic_fmrx_job, cordic_fmrx_job16, f)
+static_assert(sizeof(cordic_fmrx_job) == 88 && F(d_fcw) && F(d_pm) && F(d_xval)
+	&& F(d_yval) && F(d_omag) && F(d_ofreq) && F(d_acc) && F(d_last) && F(n)
+	&& F(phase0) && F(dphase0) && F(reserved),
+	"cordic_fmrx_job16 is cordic_fmrx_job with 16-bit sample pointers");
+#undef F
+
+// The argument checks of cordic_rxbank_create / _create16 that need no device
+// (bank_jobs_valid, cordic_span_bank.h): d_fcw and the four sample arrays
+// required, d_pm, d_acc and d_last optional; the outputs are d_omag, d_ofreq
+// and the words at d_acc and d_last.
+inline bool fmrxb_jobs_valid(size_t njobs, RxJobs jobs)
+{
+	return bank_jobs_valid(njobs, jobs,
+		[](const cordic_fmrx_job &jb, uint64_t es, const void **word) {
+			word[0] = jb.d_acc;
+			word[1] = jb.d_last;
+			return std::array<JobArray, 6>{{{jb.d_fcw, 4, true, false},
+				{jb.d_xval, es, true, false}, {jb.d_yval, es, true, false},
+				{jb.d_pm, 4, false, false}, {jb.d_omag, es, true, true},
+				{jb.d_ofreq, es, true, true}}};
+		});
+}
+
+// what span_cut (cordic_span_bank.h) leaves to the bank: the sample arrays,
+// `at` bytes in, and the discriminator's word
+inline void span_place(RxSpan *d, const cordic_fmrx_job &jb, uint64_t at)
+{
+	d->x = (uintptr_t)jb.d_xval + at;
+	d->y = (uintptr_t)jb.d_yval + at;
+	d->mag = (uintptr_t)jb.d_omag + at;
+	d->freq = (uintptr_t)jb.d_ofreq + at;
+	d->last = (uintptr_t)jb.d_last;
+	d->dphase0 = jb.dphase0;
+}
+
+// The converter's kernel parameters on the device, for launch 2 to fetch by
+// scalar loads (fmrx::conv_params); the bank frees them with hipFree.
+// CORDIC_OK or CORDIC_ERR_DEVICE.
+int	fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv);
+
+// The two launches, for a plan and a converter of which the single call is
+// fused (cordic_fm_rx.h) -- the 16-bit rule where the spans were cut from
+// 16-bit jobs (io16).  d_start / d_part / d_prev: the bank's workspace (one word
+// per non-empty job, one per span, one per non-empty job).  cus: the device's,
+// at create.  An empty table launches nothing.  CORDIC_OK or CORDIC_ERR_DEVICE.
+struct DxInfo;		// (cordic_internal.h)
+int	launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
+		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
+		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
+		void *stream);
+
+} // namespace cordic_amd
+#endif

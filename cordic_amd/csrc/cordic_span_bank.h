@@ -77,11 +77,13 @@ struct JobArray {
 };
 
 // The argument checks of a bank's create that need no device.  list(jb, es,
-// &word) names the arrays of job jb, inputs before outputs, and the optional
-// 4-byte word the job reads and writes (d_acc, d_last).  Every job with n > 0
-// has its required pointers non-NULL, each pointer on the grid of its element,
-// the word on the 4-byte grid, reserved == 0 and a length within SIZE_MAX >> 4;
-// no output range (the word among them) overlaps another output range or any
+// word) names the arrays of job jb, inputs before outputs, and the optional
+// 4-byte words the job reads and writes: word[0] (d_acc, d_last) and, for a
+// bank whose jobs name two, word[1] (the receiver banks' d_last).  Every job
+// with n > 0 has its required pointers non-NULL, each pointer on the grid of its
+// element, the words on the 4-byte grid, reserved == 0 and a length within
+// SIZE_MAX >> 4; no output range (the words among them, so two jobs -- or one
+// job twice -- naming the same word) overlaps another output range or any
 // input range of the bank (BankRanges, cordic_bank_host.h), by the true byte
 // ranges, n * bytes.  A job of no samples is not looked at.
 template <typename Jobs, typename List>
@@ -92,9 +94,10 @@ inline bool bank_jobs_valid(size_t njobs, Jobs jobs, List list)
 		const auto jb = jobs[k];
 		if (jb.n == 0)
 			continue;
-		const void *word = nullptr;
-		const auto arrays = list(jb, jobs.esize(), &word);
-		if (((uintptr_t)word & 3u) || jb.reserved != 0 || jb.n > (~(size_t)0 >> 4))
+		const void *word[2] = {nullptr, nullptr};
+		const auto arrays = list(jb, jobs.esize(), word);
+		if ((((uintptr_t)word[0] | (uintptr_t)word[1]) & 3u) || jb.reserved != 0
+				|| jb.n > (~(size_t)0 >> 4))
 			return false;
 		for (const JobArray &a : arrays)
 			if ((a.required && !a.p) || ((uintptr_t)a.p & (a.bytes - 1)))
@@ -102,8 +105,9 @@ inline bool bank_jobs_valid(size_t njobs, Jobs jobs, List list)
 		for (const JobArray &a : arrays)
 			if (a.p && !r.add((uintptr_t)a.p, jb.n * a.bytes, a.is_output))
 				return false;
-		if (word && !r.add((uintptr_t)word, 4, true))
-			return false;
+		for (const void *w : word)
+			if (w && !r.add((uintptr_t)w, 4, true))
+				return false;
 	}
 	return r.outputs_clear();
 }
@@ -112,11 +116,18 @@ inline bool bank_jobs_valid(size_t njobs, Jobs jobs, List list)
 
 // unit: the samples of a pass or tile; max_spans: the most spans of one job
 // (what a span of launch 2 sums in front of itself, the single call's bound);
-// max_units: the most units of a base span.
+// max_units: the most units of a base span.  halo: the samples at the head of
+// a span's units that belong to the span in front and are made again, not
+// stored (the receiver banks: 4; a span of u units yields u * unit - halo
+// samples).  words: further latched words per job in the run's workspace,
+// behind the partial sums (the receiver banks: 1, the phase in front of sample
+// 0).  Both are 0 for the mixer and the oscillator banks.
 struct SpanRule {
 	uint64_t unit;
 	uint32_t max_spans;
 	uint32_t max_units;
+	uint32_t halo = 0;
+	uint32_t words = 0;
 };
 
 // a span's flags: its job's first, its job's last
@@ -166,13 +177,20 @@ inline uint32_t span_forced_cap(const SpanRule &r, const char *e)
 	return (v >= 1 && v < (long)r.max_spans) ? (uint32_t)v : r.max_spans;
 }
 
+// spans of ONE job of n samples at uj units per span (without a halo: its
+// units over uj, rounded up)
+inline uint64_t span_spans_of(const SpanRule &r, uint64_t n, uint64_t uj)
+{
+	const uint64_t yield = uj * r.unit - r.halo;
+	return n / yield + (n % yield ? 1 : 0);
+}
+
 // units per span of ONE job of n samples: the base length, doubled until the
 // job has at most `cap` spans
 inline uint64_t span_job_units(const SpanRule &r, uint64_t n, uint32_t base, uint32_t cap)
 {
-	const uint64_t nu = span_units_of(r, n);
 	uint64_t uj = base;
-	while ((nu + uj - 1) / uj > cap)
+	while (span_spans_of(r, n, uj) > cap)
 		uj *= 2;
 	return uj;
 }
@@ -187,8 +205,7 @@ inline uint64_t span_count(const SpanRule &r, size_t njobs, Jobs jobs, uint32_t 
 		const uint64_t n = jobs.n(k);
 		if (!n)
 			continue;
-		const uint64_t uj = span_job_units(r, n, base, cap);
-		t += (span_units_of(r, n) + uj - 1) / uj;
+		t += span_spans_of(r, n, span_job_units(r, n, base, cap));
 		if (t >> 63)
 			break;
 	}
@@ -197,7 +214,8 @@ inline uint64_t span_count(const SpanRule &r, size_t njobs, Jobs jobs, uint32_t 
 
 // Cuts valid jobs (the bank's *_jobs_valid; fewer than 2^32 spans) into spans,
 // in the jobs' order.  Start words are numbered by non-empty job, partial sums
-// by span: the workspace of the run has *njobs_live + spans->size() words.  A
+// by span: the workspace of the run has *njobs_live * (1 + r.words) +
+// spans->size() words.  A
 // span's addresses are byte addresses: its first sample is 4 bytes per sample
 // into d_fcw / d_pm and esize into the sample arrays, which the bank's
 // span_place(&span, job, s0 * esize) sets.
@@ -211,7 +229,7 @@ inline void span_cut(const SpanRule &r, size_t njobs, Jobs jobs, uint32_t base,
 		const auto jb = jobs[k];
 		if (jb.n == 0)
 			continue;
-		const uint64_t len = span_job_units(r, jb.n, base, cap) * r.unit;
+		const uint64_t len = span_job_units(r, jb.n, base, cap) * r.unit - r.halo;
 		const uint32_t part0 = (uint32_t)spans->size();
 		uint32_t idx = 0;
 		for (uint64_t s0 = 0; s0 < jb.n; s0 += len, idx++) {

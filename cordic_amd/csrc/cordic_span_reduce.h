@@ -37,6 +37,14 @@ namespace cordic_amd {
 // through this 42 and 223 (profiles/r20/span_bank_isa.txt).
 typedef uint32_t span_words4 __attribute__((ext_vector_type(4), aligned(4)));
 
+// What a job's first span latches besides the start word, into the words
+// behind the partial sums (SpanRule::words): nothing, unless the bank's
+// descriptor has an overload of its own (RxSpan, cordic_fm_rx_bank.h).
+template <typename SPAN>
+__device__ __forceinline__ void span_latch_more(const SPAN &, uint32_t *)
+{
+}
+
 template <typename SPAN, int THREADS>
 __global__ __launch_bounds__(THREADS) void span_reduce(
 		const SPAN *__restrict__ spans, uint32_t nspans,
@@ -76,6 +84,7 @@ __global__ __launch_bounds__(THREADS) void span_reduce(
 				const uint32_t *acc
 					= reinterpret_cast<const uint32_t *>((uintptr_t)d.acc);
 				start[d.start] = d.phase0 + (acc ? *acc : 0u);
+				span_latch_more(d, part + nspans);
 			}
 		}
 		par ^= 1;

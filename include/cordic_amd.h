@@ -1375,6 +1375,193 @@ typedef struct cordic_fmmix_job16 {
 int	cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
 		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank);
 
+/* Tuned FM receiver: the FM mixer and FM demodulation in one kernel.
+ *
+ * The receive half of an FM link -- tune every sample by the running sum of
+ * its tuning words, then magnitude and phase step -- without the tuned I/Q ever
+ * reaching memory.  `plan` is the mixer's (CORDIC_P2R / CORDIC_SP2R), `conv`
+ * the discriminator's core (CORDIC_R2P / CORDIC_SR2P).  Bit for bit, every
+ * output and both words are those of
+ *   cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+ *                      T_x, T_y, ..)
+ *   cordic_fm_demod(conv, n, T_x, T_y, dphase0, d_last, d_omag, d_ofreq, ..)
+ * in sequence:
+ *   start  = phase0 + *d_acc                      (0 for a NULL d_acc; 32 bits)
+ *   p_i    = start + fcw[0] + .. + fcw[i-1] + pm[i]            (mod 2^32)
+ *   (tx_i, ty_i) = what cordic_plan_fm_mix writes for (x_i, y_i, p_i)
+ *   (mag_i, ph_i) = what cordic_r2p writes for (tx_i, ty_i) on conv (its inputs
+ *            taken modulo conv's IW)
+ *   prev   = (dphase0 + *d_last) mod 2^PW(conv)   (0 for a NULL d_last)
+ *   freq_i = sext_PW((ph_i - ph_(i-1)) mod 2^PW),  ph_(-1) = prev
+ *   afterwards: *d_acc = start + fcw[0] + .. + fcw[n-1];  *d_last = ph_(n-1).
+ * Everything the two calls document carries over: phase0 and dphase0 are added
+ * by every call; a job cut into consecutive calls that share d_acc and d_last
+ * gives the bits of one call; a captured call replayed k times continues k
+ * times; n == 0 is CORDIC_OK with nothing touched.
+ *
+ * Status codes, in this order (the mixer's first): CORDIC_ERR_ARGS for a NULL
+ * plan or conv (also with n == 0); CORDIC_ERR_MODE for a plan that is not P2R /
+ * SP2R; then for conv CORDIC_ERR_MODE if it is not R2P / SR2P and
+ * CORDIC_ERR_ARGS if it is not a sane configuration; for the *16 forms then
+ * CORDIC_ERR_CONTAINER unless the plan has IW <= 16 and OW <= 16
+ * (cordic_plan_fm_mix16's rule) and conv has IW, OW and PW <= 16
+ * (cordic_fm_demod16's).  With n > 0 then CORDIC_ERR_ARGS for a NULL d_fcw,
+ * d_xval, d_yval, d_omag, d_ofreq or d_work, a pointer off its grid, an
+ * overlap.  The _info and _workspace functions check the same, in the same
+ * order; _workspace answers 0 where the call would fail.
+ *
+ * Alignment and overlap: the four sample arrays sit on their element's grid (4
+ * bytes, 2 for the *16 forms), d_fcw, d_pm, d_acc and d_last on 4 bytes, d_work
+ * on 16.  No output -- d_omag, d_ofreq, the words at d_acc and d_last, d_work --
+ * may overlap an input or another output: found on the host by the true byte
+ * ranges, with nothing written.  Inputs may alias each other.  Nothing outside
+ * [0, n) of an output is written.
+ *
+ * Two paths, identical bits, under the launch contract of the two calls:
+ *   fused     cordic_plan_fm_mix_info answers 1 for the plan (for the *16
+ *             forms: and WW < 35, cordic_plan_fm_mix16's fused rule),
+ *             cordic_fm_demod_info (cordic_fm_demod16_info) answers 1 for conv,
+ *             and conv carries no CORDIC_FLAG_UNIT_GAIN.  Exactly TWO launches
+ *             on `stream`: a reduction of d_fcw into per-block partial sums
+ *             that also latches start and prev, then the scan with the rotator
+ *             and the converter behind it.  Any arrays on their element's grid
+ *             are served (cordic_fm_demod's 16-byte condition does not apply).
+ *             Nothing is allocated, copied or synchronised, no block waits for
+ *             another, no tile queue: legal inside a stream capture.  *d_acc
+ *             and *d_last are read in launch 1 only and written in launch 2
+ *             only.  20 bytes per sample (24 with d_pm) on int32, 12 (16) on
+ *             int16, against 40 (44) and 24 (28) of the two calls.
+ *   fallback  everything else the two calls accept: cordic_plan_fm_mix
+ *             (cordic_plan_fm_mix16) into two arrays inside d_work, then
+ *             cordic_fm_demod (cordic_fm_demod16) from them -- their launches,
+ *             nothing allocated.
+ * cordic_plan_fm_rx_info / cordic_plan_fm_rx16_info (pure host functions):
+ * *fused = 1 or 0; *tile = 1024, the samples a block of the fused kernel makes
+ * per pass, 0 when not fused; either pointer may be NULL.
+ *
+ * d_work: caller-owned device scratch of at least
+ * cordic_plan_fm_rx_workspace(plan, conv, n) bytes (cordic_plan_fm_rx16_workspace
+ * for the *16 form), not shared by calls that may run at the same time.  Pure
+ * host functions: 0 for n == 0, a multiple of 16, non-decreasing in n; at most
+ * n / 256 + 65536 when fused; otherwise the mixer call's workspace, two arrays
+ * of n samples and the discriminator's workspace, each part on the 16-byte
+ * grid: at most 13 n + 65536 + 128 for cordic_plan_fm_rx and 25 n + 65536 + 256
+ * for cordic_plan_fm_rx16.
+ *
+ * Many short jobs of one plan and one converter go into a receiver bank
+ * (below).
+ */
+size_t	cordic_plan_fm_rx_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n);
+size_t	cordic_plan_fm_rx16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n);
+int	cordic_plan_fm_rx_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile);
+int	cordic_plan_fm_rx16_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile);
+int	cordic_plan_fm_rx(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last,
+		int32_t *d_omag, int32_t *d_ofreq, void *d_work, void *stream);
+int	cordic_plan_fm_rx16(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream);
+
+/* Receiver banks: many tuned-receiver jobs in two launches.
+ *
+ * What FM mixer banks are to cordic_plan_fm_mix, for cordic_plan_fm_rx: the
+ * whole receive chain of a channeliser -- per-channel LO and discriminator --
+ * where a mixer bank into a demodulation bank costs four launches a round and
+ * an intermediate I/Q array.  One cordic_rxbank_run gives, for every job with
+ * n > 0, bit for bit what
+ *   cordic_plan_fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval,
+ *                     d_yval, dphase0, d_last, d_omag, d_ofreq, work, stream)
+ * gives, *d_acc and *d_last afterwards included; phase0 and dphase0 are added
+ * by every run.  A bank whose jobs have both words and phase0 == dphase0 == 0,
+ * run k times on new data in the same arrays, continues every channel k times,
+ * and a captured run replayed k times continues k times.
+ *
+ * Create: the status codes of cordic_plan_fm_rx, in its order (for _create16
+ * the containers of cordic_plan_fm_rx16), behind CORDIC_ERR_ARGS for a NULL
+ * bank pointer or NULL jobs with njobs > 0.  Every other rule is that of
+ * cordic_mixbank_create, word for word: CORDIC_ERR_UNSUPPORTED while the
+ * legacy stream is being captured; CORDIC_ERR_ARGS for 2^28 or more jobs, 2^32
+ * or more spans, and for a job with n > 0 a NULL d_fcw, d_xval, d_yval, d_omag
+ * or d_ofreq, a pointer off its grid (sample arrays 4 bytes, 2 for _create16;
+ * d_fcw, d_pm, d_acc, d_last 4 bytes), reserved != 0, n beyond SIZE_MAX >> 4.
+ * No output range of the bank -- every job's d_omag, d_ofreq and the 4 bytes at
+ * its d_acc and at its d_last -- may overlap another output range or any job's
+ * input range (found by sorting the true byte ranges; two jobs that share a
+ * d_acc or a d_last, or one job whose d_acc is its d_last, overlap); inputs may
+ * alias each other.  njobs == 0 or all-empty jobs give a valid bank whose run
+ * launches and writes nothing.  The bank REFERS to the plan, which must
+ * outlive it, and COPIES conv.  It belongs to the device that was current at
+ * create: CORDIC_ERR_ARGS from run on another device.  It owns its device
+ * memory; run allocates, copies and synchronises nothing, and two runs of ONE
+ * bank must not be in flight at the same time.
+ *
+ * Two paths, identical bits, chosen at create and told by cordic_rxbank_info:
+ *   fused       where cordic_plan_fm_rx_info (cordic_plan_fm_rx16_info for
+ *               _create16) answers 1.  The whole bank is exactly TWO launches
+ *               on `stream`: every job is cut into spans of P passes of 1024
+ *               samples LESS 4 (a span's first vector is the vector in front of
+ *               it, made again and not stored), never across a job's end -- P
+ *               by the bank's size, 1, 2, 4, 8, ...; a job that would have more
+ *               than 4096 spans gets longer ones -- then a reduction of the
+ *               tuning words per span, which also latches every job's start
+ *               phase and the phase in front of its sample 0, and the scan with
+ *               the rotator and the converter behind it walking the spans.  Any
+ *               arrays on their element's grid are served; no block waits for
+ *               another, no tile queue; legal inside a stream capture.  Every
+ *               *d_acc and *d_last is read in the first launch only and
+ *               written in the second only.
+ *   one by one  everything else: run loops cordic_plan_fm_rx (_rx16) over the
+ *               jobs with a workspace allocated at create for the longest job.
+ * Measured (profiles/r20/fm_rx.txt): a round of 256 blocks of 1500 samples
+ * takes 0.49 .. 0.76 of the time of a mixer bank into a demodulation bank; a
+ * bank of 1024 blocks of 2^16 samples runs at 0.97 .. 1.00 of their rate (the
+ * int32 forms 2 .. 3 % below it), where the bytes saved buy nothing.
+ * cordic_rxbank_info (any pointer may be NULL): *samples = the samples of all
+ * jobs; *spans = the spans the second launch walks (0 one by one); *fused = 1 /
+ * 0; *tile = 1024, the samples of a pass, when fused, else 0.  _info and _run
+ * return CORDIC_ERR_ARGS for a NULL bank; cordic_rxbank_destroy(NULL) does
+ * nothing.
+ */
+typedef struct cordic_fmrx_job {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	const int32_t *d_xval, *d_yval;	/* n words each                         */
+	int32_t	*d_omag, *d_ofreq;	/* n words each                         */
+	uint32_t *d_acc, *d_last;	/* optional device words (NULL: none)   */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0, dphase0;
+	uint64_t reserved;		/* 0                                    */
+} cordic_fmrx_job;			/* 88 bytes                             */
+typedef struct cordic_fmrx_job16 {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	const int16_t *d_xval, *d_yval;	/* n shorts each                        */
+	int16_t	*d_omag, *d_ofreq;	/* n shorts each                        */
+	uint32_t *d_acc, *d_last;	/* optional device words (NULL: none)   */
+	uint64_t n;			/* samples; 0 allowed                   */
+	uint32_t phase0, dphase0;
+	uint64_t reserved;		/* 0                                    */
+} cordic_fmrx_job16;			/* 88 bytes                             */
+typedef struct cordic_rxbank cordic_rxbank;
+int	cordic_rxbank_create(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job *jobs, cordic_rxbank **bank);
+int	cordic_rxbank_create16(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job16 *jobs, cordic_rxbank **bank);
+int	cordic_rxbank_run(const cordic_rxbank *bank, void *stream);
+int	cordic_rxbank_info(const cordic_rxbank *bank, uint64_t *samples,
+		uint32_t *spans, int32_t *fused, int32_t *tile);
+void	cordic_rxbank_destroy(cordic_rxbank *bank);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with

@@ -2074,13 +2074,45 @@ class _CFmMixJob(C.Structure):
 _FMMIX_KEYS = ("fcw", "pm", "x", "y", "ox", "oy", "n", "phase0", "acc")
 
 
-class MixBank:
+class _SpanBank:
+    """What MixBank and RxBank share: info, run, close and __del__ on the
+    handle self._h, through the C functions <_prefix>_info, _run and _destroy."""
+
+    _prefix = None
+
+    def info(self):
+        a, b = C.c_uint64(), C.c_uint32()
+        c, d = C.c_int32(), C.c_int32()
+        name = self._prefix + "_info"
+        _check(getattr(lib(), name)(self._h, C.byref(a), C.byref(b), C.byref(c),
+                                    C.byref(d)), name)
+        return dict(samples=a.value, spans=b.value, fused=c.value,
+                    tile=d.value)
+
+    def run(self, stream=None):
+        name = self._prefix + "_run"
+        _check(getattr(lib(), name)(self._h, _stream(stream)), name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(lib(), self._prefix + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MixBank(_SpanBank):
     """cordic_mixbank: many fm_mix jobs of one p2r / sp2r plan, cut once and
     run in two launches.  jobs: tuples (fcw, pm, x, y, ox, oy, n, phase0, acc)
     or dicts with those keys; fcw, x, y, ox, oy are int32 tensors or device
     addresses, pm one more or None, acc a one-word device tensor or None; n
     None: fcw.numel().  The plan must stay open as long as the bank."""
 
+    _prefix = "cordic_mixbank"
     _create = "cordic_mixbank_create"
 
     def __init__(self, plan, jobs):
@@ -2102,30 +2134,6 @@ class MixBank:
         _check(getattr(lib(), self._create)(getattr(plan, "_h", plan), len(jobs),
                                             arr, C.byref(h)), self._create)
         self._h = h
-
-    def info(self):
-        a, b = C.c_uint64(), C.c_uint32()
-        c, d = C.c_int32(), C.c_int32()
-        _check(lib().cordic_mixbank_info(self._h, C.byref(a), C.byref(b),
-                                         C.byref(c), C.byref(d)),
-               "cordic_mixbank_info")
-        return dict(samples=a.value, spans=b.value, fused=c.value,
-                    tile=d.value)
-
-    def run(self, stream=None):
-        _check(lib().cordic_mixbank_run(self._h, _stream(stream)),
-               "cordic_mixbank_run")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().cordic_mixbank_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class MixBank16(MixBank):
@@ -2158,7 +2166,7 @@ _FMRX_KEYS = ("fcw", "pm", "x", "y", "mag", "freq", "n", "phase0", "acc",
               "dphase0", "last")
 
 
-class RxBank:
+class RxBank(_SpanBank):
     """cordic_rxbank: many fm_rx jobs of one p2r / sp2r plan and one r2p /
     sr2p converter, cut once and run in two launches.  jobs: tuples (fcw, pm,
     x, y, mag, freq, n, phase0, acc, dphase0, last) or dicts with those keys;
@@ -2166,6 +2174,7 @@ class RxBank:
     None, acc and last one-word device tensors or None; n None: fcw.numel().
     The plan must stay open as long as the bank; conv is copied."""
 
+    _prefix = "cordic_rxbank"
     _create = "cordic_rxbank_create"
 
     def __init__(self, plan, conv, jobs):
@@ -2191,30 +2200,6 @@ class RxBank:
             getattr(plan, "_h", plan), conv.ref if conv is not None else None,
             len(jobs), arr, C.byref(h)), self._create)
         self._h = h
-
-    def info(self):
-        a, b = C.c_uint64(), C.c_uint32()
-        c, d = C.c_int32(), C.c_int32()
-        _check(lib().cordic_rxbank_info(self._h, C.byref(a), C.byref(b),
-                                        C.byref(c), C.byref(d)),
-               "cordic_rxbank_info")
-        return dict(samples=a.value, spans=b.value, fused=c.value,
-                    tile=d.value)
-
-    def run(self, stream=None):
-        _check(lib().cordic_rxbank_run(self._h, _stream(stream)),
-               "cordic_rxbank_run")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().cordic_rxbank_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class RxBank16(RxBank):

@@ -272,50 +272,71 @@ struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	SpanTable<MixSpan> spans;		// fused
 };
 
-// both creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h)
-static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
-		cordic_mixbank **bank)
+// The create of the two plan-side banks (mixer, receiver), 32- and 16-bit:
+// `jobs` is the bank's view of either job struct (MixJobs, RxJobs), `core_ok`
+// the check of the plan (and converter), `fused` the whole bank's path,
+// `work_bytes` a job's workspace one by one, `finish` what a fused bank still
+// needs behind its span table.  TR (MixBankTraits, RxBankTraits, next to the
+// views): the job check, the span rule, the knobs' names, the blocks per CU.
+// The checks come in this order, each bank's documented order of status codes.
+template <typename TR, typename Bank, typename Jobs, typename Ok, typename Fused,
+	typename Work, typename Finish>
+static int plan_bank_create(const cordic_plan *plan, size_t njobs, Jobs jobs, Bank **bank,
+		Ok core_ok, Fused fused, Work work_bytes, void (*destroy)(Bank *),
+		Finish finish)
 {
 	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
 	if (!bank || (njobs && jobs.none()))
 		return CORDIC_ERR_ARGS;
-	if (int rc = io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan))
+	if (int rc = core_ok(io16))
 		return rc;
-	if (njobs >= ((size_t)1 << 28) || !fmxb_jobs_valid(njobs, jobs))
+	if (njobs >= ((size_t)1 << 28) || !TR::jobs_valid(njobs, jobs))
 		return CORDIC_ERR_ARGS;
 	(void)hipGetLastError();	// (a stale error is not this call's)
-	// the handle keeps its jobs as cordic_fmmix_job, whatever the container
-	std::vector<cordic_fmmix_job> wide;
-	const cordic_fmmix_job *flat = jobs.j32;
+	// the handle keeps its jobs in the 32-bit struct, whatever the container
+	typedef typename decltype(Bank::jobs)::value_type Job;
+	std::vector<Job> wide;
+	const Job *flat = jobs.j32;
 	if (io16) {
 		wide.reserve(njobs);
 		for (size_t k = 0; k < njobs; k++)
 			wide.push_back(jobs[k]);
 		flat = wide.data();
 	}
-	cordic_mixbank *b = nullptr;
-	if (int rc = bank_begin(njobs, flat, io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan),
-			[&](size_t n) {
-				return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(false, n);
-			}, &b))
+	Bank *b = nullptr;
+	if (int rc = bank_begin(njobs, flat, fused(io16),
+			[&](size_t n) { return work_bytes(io16, n); }, &b))
 		return rc;
 	b->plan = plan;
 	b->io16 = io16;
-	if (!b->fused) {
-		*bank = b;
-		return CORDIC_OK;
+	int rc = CORDIC_OK;
+	if (b->fused) {
+		uint64_t passes = 0;
+		for (size_t k = 0; k < njobs; k++)
+			passes += span_units_of(TR::rule, jobs.n(k));
+		rc = span_table_build(&b->spans, TR::passes, TR::max_spans, TR::rule, passes,
+			b->cus, TR::blocks_per_cu, njobs, jobs, &b->passes);
 	}
-	uint64_t passes = 0;
-	for (size_t k = 0; k < njobs; k++)
-		passes += span_units_of(kFmxbRule, jobs.n(k));
-	if (int rc = span_table_build(&b->spans, "CORDIC_FMXB_PASSES",
-			"CORDIC_FMXB_MAX_SPANS", kFmxbRule, passes, b->cus, kFmxbBlocksPerCu,
-			njobs, jobs, &b->passes)) {
-		cordic_mixbank_destroy(b);
+	if (!rc)
+		rc = finish(b);
+	if (rc) {
+		destroy(b);
 		return rc;
 	}
 	*bank = b;
 	return CORDIC_OK;
+}
+
+// both creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h)
+static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
+		cordic_mixbank **bank)
+{
+	return plan_bank_create<MixBankTraits>(plan, njobs, jobs, bank,
+		[&](bool io16) { return io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan); },
+		[&](bool io16) { return io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan); },
+		[&](bool io16, size_t n) {
+			return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(false, n);
+		}, cordic_mixbank_destroy, [](cordic_mixbank *) { return CORDIC_OK; });
 }
 
 int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
@@ -523,51 +544,19 @@ struct cordic_rxbank : BankHandle<cordic_fmrx_job> {
 	uint32_t *d_conv = nullptr;		// fused: conv's kernel parameters
 };
 
-// both creates: `jobs` is either job struct (RxJobs, cordic_fm_rx_bank.h)
+// both creates: `jobs` is either job struct (RxJobs, cordic_fm_rx_bank.h); a
+// fused bank uploads the converter's kernel parameters behind its span table
 static int rxbank_create(const cordic_plan *plan, const cordic_config *conv,
 		size_t njobs, RxJobs jobs, cordic_rxbank **bank)
 {
-	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
-	if (!bank || (njobs && jobs.none()))
-		return CORDIC_ERR_ARGS;
-	if (int rc = fm_rx_ok(plan, conv, io16))
-		return rc;
-	if (njobs >= ((size_t)1 << 28) || !fmrxb_jobs_valid(njobs, jobs))
-		return CORDIC_ERR_ARGS;
-	(void)hipGetLastError();	// (a stale error is not this call's)
-	// the handle keeps its jobs as cordic_fmrx_job, whatever the container
-	std::vector<cordic_fmrx_job> wide;
-	const cordic_fmrx_job *flat = jobs.j32;
-	if (io16) {
-		wide.reserve(njobs);
-		for (size_t k = 0; k < njobs; k++)
-			wide.push_back(jobs[k]);
-		flat = wide.data();
-	}
-	cordic_rxbank *b = nullptr;
-	if (int rc = bank_begin(njobs, flat, fm_rx_fused(plan, conv, io16),
-			[&](size_t n) { return fm_rx_work_bytes(plan, conv, n, io16); }, &b))
-		return rc;
-	b->plan = plan;
-	b->conv = *conv;
-	b->io16 = io16;
-	if (!b->fused) {
-		*bank = b;
-		return CORDIC_OK;
-	}
-	uint64_t passes = 0;
-	for (size_t k = 0; k < njobs; k++)
-		passes += span_units_of(kFmrxbRule, jobs.n(k));
-	int rc = span_table_build(&b->spans, "CORDIC_FMRXB_PASSES", "CORDIC_FMRXB_MAX_SPANS",
-			kFmrxbRule, passes, b->cus, kFmrxbBlocksPerCu, njobs, jobs, &b->passes);
-	if (!rc)
-		rc = fmrxb_upload_conv(b->conv, &b->d_conv);
-	if (rc) {
-		cordic_rxbank_destroy(b);
-		return rc;
-	}
-	*bank = b;
-	return CORDIC_OK;
+	return plan_bank_create<RxBankTraits>(plan, njobs, jobs, bank,
+		[&](bool io16) { return fm_rx_ok(plan, conv, io16); },
+		[&](bool io16) { return fm_rx_fused(plan, conv, io16); },
+		[&](bool io16, size_t n) { return fm_rx_work_bytes(plan, conv, n, io16); },
+		cordic_rxbank_destroy, [&](cordic_rxbank *b) {
+			b->conv = *conv;
+			return b->fused ? fmrxb_upload_conv(b->conv, &b->d_conv) : CORDIC_OK;
+		});
 }
 
 int cordic_rxbank_create(const cordic_plan *plan, const cordic_config *conv,

@@ -103,7 +103,9 @@ int	launch_fmx_narrow(size_t n, const int32_t *d_wox, const int32_t *d_woy,
 // ---- device side: what fm_mix_xydir (cordic_fm_mix.hip) and the bank's
 // fm_mixbank_xydir (cordic_fm_mix_bank.hip) are both made of -- the staging of
 // the direction tables, the per-vector body of the rotator, the wave scan and
-// the pass loop over a contiguous run of samples.
+// the pass loop over a contiguous run of samples -- and what they share with
+// the receiver's kernels (cordic_fm_rx.hip, cordic_fm_rx_bank.hip): the block's
+// prologue and, on the host, the choice of the instance.
 #include "cordic_xydir.h"
 
 namespace cordic_amd {
@@ -379,6 +381,42 @@ __device__ __forceinline__ RotRegs rot_regs(const CoreParams &kp, const DirArgs 
 	return r;
 }
 
+// ---- the block's prologue, of all four launch-2 kernels (fm_mix_xydir,
+// fm_mixbank_xydir, fm_rx_xydir, fm_rxbank_xydir): one piece for each side of
+// the barrier, which is the caller's -- a single call puts its front_sum
+// between the two, a bank has its own per span.  The kernels keep five lines
+// of their own in front: the DYNAMIC block `lds` (the table lookups address LDS
+// by byte offset from 0, which a static __shared__ object would displace), tid,
+// wave, the two arrays that dx_lds_layout fills, and ex behind the tables.
+// Held in a struct that block_begin returns, or filled through a reference by a
+// dx_lds_layout called from here, hipcc makes other code of them
+// (profiles/r21/fm_fold_isa.txt).
+//
+// In front of the barrier: the fold's rows and the groups' tables into LDS.
+template <int LJ, int NLIVE, typename IO>
+__device__ __forceinline__ void block_begin(const CoreParams &kp, const DirArgs &da,
+		uint32_t *lds, const uint32_t (&bk_base)[kDxMaxLevels],
+		const uint32_t (&lf_base)[kDxMaxLevels], const unsigned tid)
+{
+	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
+	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
+		"16-bit ports and WW 35: the fallback, or one by one (fmx_is_fused16)");
+	constexpr int kN = dx_levels(NLIVE);
+	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
+	stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+}
+
+// Behind it: the trap on an LDS block that does not begin at 0, and the
+// rotator's registers.
+template <int LJ, int NLIVE>
+__device__ __forceinline__ RotRegs block_ready(const CoreParams &kp, const DirArgs &da,
+		const uint32_t *lds)
+{
+	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
+		__builtin_trap();
+	return rot_regs<LJ, NLIVE>(kp, da);
+}
+
 // The pass loop: samples [lo, hi) of the six arrays, 1024 per pass, 4 per lane.
 // carry: in, the phase of sample lo without its pm; out, that of sample hi.
 // par: the parity of the exchange words ex[0 .. 8), which are double-buffered
@@ -501,9 +539,51 @@ inline size_t blocks_per_cu(size_t lds)
 	return per_cu > kFmxBlocksPerCu ? kFmxBlocksPerCu : per_cu;
 }
 
+// ---- which instance serves a plan, for all four launch-2 kernels
+// <LJ, container> of a core of working width ww on samples of esize bytes: the
+// one home of "WW 35 is LJ 29" and "no Io16 at WW 35" (fmx_is_fused16).  The
+// receiver's units, compiled once per value, index their entry points by it.
+enum Unit { kUnitNone = -1, kUnitLj30 = 0, kUnitLj29 = 1, kUnitIo16 = 2 };
+inline Unit unit_of(int ww, size_t esize)
+{
+	return esize == 2 ? (ww < 35 ? kUnitIo16 : kUnitNone)
+		: ww == 35 ? kUnitLj29 : kUnitLj30;
+}
+
+// Calls f(integral_constant<int, LJ>, IO) for the unit; false: none, or f's
+template <typename F>
+bool with_unit(Unit u, F &&f)
+{
+	switch (u) {
+	case kUnitLj30: return f(std::integral_constant<int, 30>{}, Io32{});
+	case kUnitLj29: return f(std::integral_constant<int, 29>{}, Io32{});
+	case kUnitIo16: return f(std::integral_constant<int, 30>{}, Io16{});
+	default: return false;
+	}
+}
+
 // the stage counts the job-set instances of rotator_xydir carry
 // (cordic_jobs_xydir.hip)
 #define FMX_STAGES(X) X(13) X(16) X(19) X(20) X(24) X(27) X(29)
+
+// Calls f(integral_constant<int, N>) for N = nlive; false, and no call, where
+// no kernel is instantiated for nlive or the tables have another number of
+// groups than the instance looks up (the shape of fmd::with_instance).
+template <typename F>
+bool with_stages(int nlive, int ngroups, F &&f)
+{
+	switch (nlive) {
+#define X(N) case N: \
+	if (ngroups != dx_levels(N)) \
+		return false; \
+	f(std::integral_constant<int, N>{}); \
+	return true;
+	FMX_STAGES(X)
+#undef X
+	default:
+		return false;
+	}
+}
 
 } // namespace fmx
 } // namespace cordic_amd

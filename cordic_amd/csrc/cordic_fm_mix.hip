@@ -43,10 +43,17 @@
 // and A/B knob like CORDIC_FMD_MAX_BLOCKS) caps the grid at n blocks, so that
 // a short call walks many passes per block.  The bits do not depend on it.
 //
-// xydir_vector, the wave scan, the staging of the tables and the pass loop are
-// device functions in cordic_fm_mix.h, which the bank's kernel
-// (cordic_fm_mix_bank.hip) is made of as well; the counts below are the same
-// before and after they moved there.
+// xydir_vector, the wave scan, the pass loop and the block's prologue
+// (block_begin in front of the barrier: the static_asserts and the staging of
+// the tables; block_ready behind it: the trap on the LDS offset and the
+// rotator's registers) are device functions in cordic_fm_mix.h, which the
+// bank's kernel (cordic_fm_mix_bank.hip) and the receiver's two
+// (cordic_fm_rx.hip, cordic_fm_rx_bank.hip) are made of as well.  The host
+// side's choice of the instance lives there too: fmx::unit_of (<LJ, container>
+// of a core), fmx::with_unit and fmx::with_stages (the one switch over the
+// stage counts).  The call check is iq_call_ok and the span of a block
+// call_span, both cordic_hostargs.h.  The counts below are the same before and
+// after (profiles/r21/fm_fold_isa.txt).
 //
 // Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
 // .private_segment_fixed_size is 0 for every instance: nothing spills):
@@ -108,33 +115,22 @@ template <int LJ, int NLIVE, typename IO>
 __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da,
 		FmxArgs a)
 {
-	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
-	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
-		"16-bit ports and WW 35: the fallback (fmx_is_fused16)");
 	typedef typename IO::ielem ielem;
-	constexpr int kN = dx_levels(NLIVE);
-	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 	const unsigned tid = threadIdx.x;
 	// (the same in all of a wave's lanes: said so, it stays in a scalar)
 	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
 	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
 	dx_lds_layout(da.dx, bk_base, lf_base);
-
-	// ---- prologue: the fold's rows and the groups' tables, and the waves'
-	// shares of the partials in front of this block (ex[8 .. 12); ex[0 .. 8)
-	// are pass_loop's exchange words)
-	stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	// ---- prologue (fmx::block_begin / block_ready): the tables, and between
+	// the two the waves' shares of the partials in front of this block (ex[8 ..
+	// 12); ex[0 .. 8) are pass_loop's exchange words)
+	block_begin<LJ, NLIVE, IO>(kp, da, lds, bk_base, lf_base, tid);
 	uint32_t *ex = lds + a.xw / 4u;
 	front_sum(a.work + 4, blockIdx.x, ex, tid, wave);
 	__syncthreads();
+	const RotRegs rr = block_ready<LJ, NLIVE>(kp, da, lds);
 
-	// LDS is addressed by byte offset from 0: no static LDS in this kernel
-	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
-		__builtin_trap();
-
-	const RotRegs rr = rot_regs<LJ, NLIVE>(kp, da);
 	const size_t lo = (size_t)blockIdx.x * a.span;	// < n by the grid
 	const size_t hi = (a.n - lo < a.span) ? a.n : lo + a.span;
 	// the phase of sample lo, without its pm
@@ -149,35 +145,6 @@ __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da
 }
 
 // ---------------------------------------------------------------- host side
-template <int LJ, typename IO>
-static bool launch_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const FmxArgs &a)
-{
-	switch (nlive) {
-#define X(N) case N: \
-	if (da.dx.n != dx_levels(N)) \
-		return false; \
-	hipLaunchKernelGGL((fm_mix_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
-		kp, da, a); \
-	return true;
-	FMX_STAGES(X)
-#undef X
-	default:
-		return false;
-	}
-}
-
-static bool has_instance(int nlive, int ngroups)
-{
-	switch (nlive) {
-#define X(N) case N: return ngroups == dx_levels(N);
-	FMX_STAGES(X)
-#undef X
-	default:
-		return false;
-	}
-}
-
 // the 16-bit fallback's elementwise kernels
 __global__ __launch_bounds__(kBlock) void fmx_widen(size_t n,
 		const int16_t *__restrict__ x, const int16_t *__restrict__ y,
@@ -219,14 +186,14 @@ bool fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 	const dev::CoreParams kp = make_params_jobs(cfg);
 	return kp.post_mul == 0 && kp.in_shl >= 1 && kp.in_shl <= 30
 		&& fmx::lds_bytes(dx, nullptr) <= 64 * 1024
-		&& fmx::has_instance(cfg.nlive, dx.n);
+		&& fmx::with_stages(cfg.nlive, dx.n, [](auto) {});
 }
 
 bool fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx)
 {
 	// (WW 35 is LJ = 29, which has no Io16 instance: with ports of at most 16
 	// bits it means 19 or more extra bits)
-	return cfg.ww < 35 && fmx_is_fused(cfg, d_dir, dx);
+	return fmx::unit_of(cfg.ww, 2) != fmx::kUnitNone && fmx_is_fused(cfg, d_dir, dx);
 }
 
 int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
@@ -234,23 +201,8 @@ int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
 		size_t work_bytes)
 {
-	using namespace fmx;
-	if (!d_fcw || !d_xval || !d_yval || !d_oxval || !d_oyval || !d_work
-			|| n > (~(size_t)0 >> 4))
-		return CORDIC_ERR_ARGS;
-	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
-		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc);
-	const uintptr_t samples = reinterpret_cast<uintptr_t>(d_xval)
-		| reinterpret_cast<uintptr_t>(d_yval) | reinterpret_cast<uintptr_t>(d_oxval)
-		| reinterpret_cast<uintptr_t>(d_oyval);
-	if ((words & 3u) || (samples & (esize - 1))
-			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
-		return CORDIC_ERR_ARGS;
-	const Range out[4] = {range_of(d_oxval, n * esize), range_of(d_oyval, n * esize),
-		range_of(d_acc, 4), range_of(d_work, work_bytes)};
-	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
-		range_of(d_xval, n * esize), range_of(d_yval, n * esize)};
-	return outputs_overlap(out, in) ? CORDIC_ERR_ARGS : CORDIC_OK;
+	return iq_call_ok(n, d_acc, nullptr, d_fcw, d_pm, d_xval, d_yval, d_oxval, d_oyval,
+		esize, d_work, work_bytes) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
@@ -276,21 +228,21 @@ int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 	if (cap > kFmxMaxBlocks)
 		cap = kFmxMaxBlocks;
 	cap = env_block_cap("CORDIC_FMX_MAX_BLOCKS", cap);
-	const size_t npass = (n + kFmxPass - 1) / kFmxPass;
-	const size_t per_block = (npass + cap - 1) / cap;
-	const size_t span = per_block * kFmxPass;
-	const unsigned grid = (unsigned)((npass + per_block - 1) / per_block);
+	const CallSpan cs = call_span(n, cap, kFmxPass, 0);
+	const size_t span = cs.span;
+	const unsigned grid = (unsigned)cs.grid;
 	uint32_t *work = static_cast<uint32_t *>(d_work);
 	launch_fm_reduce(grid, d_fcw, n, span, phase0, d_acc, work, st);
 	const FmxArgs a{d_fcw, d_pm, d_acc, work, d_xval, d_yval, d_oxval, d_oyval, n,
 		span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = esize == 2
-		? cfg.ww < 35 && launch_lj<30, Io16>(cfg.nlive, grid, lds, st, kp, da, a)
-		: cfg.ww == 35
-			? launch_lj<29, Io32>(cfg.nlive, grid, lds, st, kp, da, a)
-			: launch_lj<30, Io32>(cfg.nlive, grid, lds, st, kp, da, a);
+	const bool done = with_unit(unit_of(cfg.ww, esize), [&](auto lj, auto io) {
+		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
+			hipLaunchKernelGGL((fm_mix_xydir<decltype(lj)::value, decltype(nl)::value,
+				decltype(io)>), dim3(grid), dim3(kBlock), lds, st, kp, da, a);
+		});
+	});
 	return tnco::finish(done);
 }
 

@@ -90,5 +90,15 @@ int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
 		uint32_t *d_part, int cus, bool io16, void *stream);
 
+// what the create of the plan-side banks (plan_bank_create, cordic_abi.cpp)
+// asks of a bank besides its view of the jobs
+struct MixBankTraits {
+	static bool jobs_valid(size_t njobs, MixJobs jobs) { return fmxb_jobs_valid(njobs, jobs); }
+	static constexpr const SpanRule &rule = kFmxbRule;
+	static constexpr const char *passes = "CORDIC_FMXB_PASSES";
+	static constexpr const char *max_spans = "CORDIC_FMXB_MAX_SPANS";
+	static constexpr int blocks_per_cu = kFmxbBlocksPerCu;
+};
+
 } // namespace cordic_amd
 #endif

@@ -9,9 +9,10 @@
 //      descriptor's head are described for both prefix-sum banks): a span of
 //      one pass is one pass of one block, 256 lanes, one 16-byte load each.
 //   2. fm_mixbank_xydir<LJ, NLIVE>: at most the resident blocks.  A block
-//      stages the plan's direction tables ONCE, then walks spans b, b + grid,
-//      ... in the table's order, which is the jobs' own.  Per span the
-//      descriptor arrives as scalar loads; the block adds the job's partials in
+//      stages the plan's direction tables ONCE (fmx::block_begin / block_ready,
+//      the single call's prologue), then walks spans b, b + grid, ... in the
+//      table's order, which is the jobs' own.  Per span the descriptor arrives
+//      as scalar loads; the block adds the job's partials in
 //      front of the span to the job's start word (front_sum, as the single
 //      call's prologue; skipped for a job's first span) and runs pass_loop
 //      (cordic_fm_mix.h), the loop fm_mix_xydir runs as well: 16-byte accesses
@@ -100,28 +101,17 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 		const uint32_t *__restrict__ start, const uint32_t *__restrict__ part,
 		uint32_t xw)
 {
-	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
-	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
-		"16-bit ports and WW 35: one by one (fmx_is_fused16)");
 	typedef typename IO::ielem ielem;
-	constexpr int kN = dx_levels(NLIVE);
-	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 	const unsigned tid = threadIdx.x;
 	// (the same in all of a wave's lanes: said so, it stays in a scalar)
 	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
 	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
 	dx_lds_layout(da.dx, bk_base, lf_base);
-	stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	block_begin<LJ, NLIVE, IO>(kp, da, lds, bk_base, lf_base, tid);
 	uint32_t *ex = lds + xw / 4u;
 	__syncthreads();
-
-	// LDS is addressed by byte offset from 0: no static LDS in this kernel
-	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
-		__builtin_trap();
-
-	const RotRegs rr = rot_regs<LJ, NLIVE>(kp, da);
+	const RotRegs rr = block_ready<LJ, NLIVE>(kp, da, lds);
 	unsigned par = 0;
 	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
 		const MixSpan d = spans[t];
@@ -142,25 +132,6 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 			carry, par, ex, tid, wave, IO{});
 		if ((d.flags & kSpanLast) && d.acc && tid == 0)
 			*reinterpret_cast<uint32_t *>((uintptr_t)d.acc) = carry;
-	}
-}
-
-template <int LJ, typename IO>
-static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const MixSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part, uint32_t xw)
-{
-	switch (nlive) {
-#define X(N) case N: \
-	if (da.dx.n != dx_levels(N)) \
-		return false; \
-	hipLaunchKernelGGL((fm_mixbank_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
-		kp, da, spans, nspans, start, part, xw); \
-	return true;
-	FMX_STAGES(X)
-#undef X
-	default:
-		return false;
 	}
 }
 
@@ -185,14 +156,14 @@ int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 	const unsigned grid = g.walk;
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = io16
-		? cfg.ww < 35 && launch_bank_lj<30, Io16>(cfg.nlive, grid, lds, st, kp, da,
-			d_spans, nspans, d_start, d_part, xw)
-		: cfg.ww == 35
-			? launch_bank_lj<29, Io32>(cfg.nlive, grid, lds, st, kp, da, d_spans,
-				nspans, d_start, d_part, xw)
-			: launch_bank_lj<30, Io32>(cfg.nlive, grid, lds, st, kp, da, d_spans,
-				nspans, d_start, d_part, xw);
+	const bool done = with_unit(unit_of(cfg.ww, io16 ? 2 : 4), [&](auto lj, auto io) {
+		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
+			hipLaunchKernelGGL((fm_mixbank_xydir<decltype(lj)::value,
+				decltype(nl)::value, decltype(io)>), dim3(grid), dim3(kBlock), lds, st,
+				kp, da, d_spans, nspans, (const uint32_t *)d_start,
+				(const uint32_t *)d_part, xw);
+		});
+	});
 	return tnco::finish(done);
 }
 

@@ -286,12 +286,9 @@ struct RxArgs {
 	size_t	n, span;		// span: samples per block, whole passes less the halo
 	uint32_t xw;			// LDS byte offset of the exchange words
 };
-bool	launch_rx_lj30(int nlive, unsigned grid, size_t lds, hipStream_t st,
+typedef bool RxLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxArgs &a);
-bool	launch_rx_lj29(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a);
-bool	launch_rx_io16(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a);
+RxLaunch launch_rx_lj30, launch_rx_lj29, launch_rx_io16;	// by fmx::Unit
 
 // ---- host side of both units
 // the tables and the exchange words behind them

@@ -16,7 +16,8 @@
 //      converter's kernel parameters behind them.  A job's first and last
 //      span run in different blocks of launch 2, and the last one writes
 //      *d_last: so launch 2 may not read it.
-//   2. fm_rx_xydir<LJ, NLIVE, IO>: the mixer's prologue (tables into LDS, the
+//   2. fm_rx_xydir<LJ, NLIVE, IO>: the mixer's prologue (fmx::block_begin /
+//      block_ready, cordic_fm_mix.h: tables into LDS, the trap; between them the
 //      partials in front added to the start), then fmrx::pass_loop
 //      (cordic_fm_rx.h): scan, fmx::xydir_vector, fmd::pol_lj_vector on its
 //      registers, the differences, two stores.
@@ -48,7 +49,8 @@
 // The unit is compiled three times, one <LJ, container> each, so that the
 // three build beside each other: as itself (<30, Io32>, launch 1 and the host
 // side), as cordic_fm_rx_lj29.hip (<29, Io32>) and as cordic_fm_rx_io16.hip
-// (<30, Io16>).
+// (<30, Io16>).  Each defines ONE entry point, FMRX_LAUNCH, around
+// fmx::with_stages; launch_fm_rx indexes the three by fmx::unit_of.
 //
 // Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
 // .private_segment_fixed_size is 0 for every instance: nothing spills to
@@ -94,32 +96,21 @@ template <int LJ, int NLIVE, typename IO>
 __global__ __launch_bounds__(kBlock) void fm_rx_xydir(CoreParams kp, DirArgs da,
 		RxArgs a)
 {
-	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
-	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
-		"16-bit ports and WW 35: the fallback (fmx_is_fused16)");
 	typedef typename IO::ielem ielem;
-	constexpr int kN = dx_levels(NLIVE);
-	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 	const unsigned tid = threadIdx.x;
 	// (the same in all of a wave's lanes: said so, it stays in a scalar)
 	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
 	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
 	dx_lds_layout(da.dx, bk_base, lf_base);
-
-	// ---- prologue, the mixer's: the tables, and the waves' shares of the
-	// partials in front of this block (ex[8 .. 12))
-	fmx::stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	// ---- prologue, the mixer's (fmx::block_begin / block_ready): the tables,
+	// and the waves' shares of the partials in front of this block (ex[8 .. 12))
+	fmx::block_begin<LJ, NLIVE, IO>(kp, da, lds, bk_base, lf_base, tid);
 	uint32_t *ex = lds + a.xw / 4u;
 	fmx::front_sum(a.work + 4, blockIdx.x, ex, tid, wave);
 	__syncthreads();
+	const fmx::RotRegs rr = fmx::block_ready<LJ, NLIVE>(kp, da, lds);
 
-	// LDS is addressed by byte offset from 0: no static LDS in this kernel
-	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
-		__builtin_trap();
-
-	const fmx::RotRegs rr = fmx::rot_regs<LJ, NLIVE>(kp, da);
 	// the converter's parameters: launch 1 left them in the workspace
 	const uint32_t *ckmem = a.work + kFmrxConvAt / 4;
 	const fmd::LaneConsts ln(conv_params(ckmem, false));
@@ -138,43 +129,31 @@ __global__ __launch_bounds__(kBlock) void fm_rx_xydir(CoreParams kp, DirArgs da,
 		*a.acc = carry;
 }
 
-template <int LJ, typename IO>
-static bool launch_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
-{
-	switch (nlive) {
-#define X(N) case N: \
-	if (da.dx.n != dx_levels(N)) \
-		return false; \
-	hipLaunchKernelGGL((fm_rx_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
-		kp, da, a); \
-	return true;
-	FMX_STAGES(X)
-#undef X
-	default:
-		return false;
-	}
-}
-
+// this unit's <LJ, container> and entry point
 #if CORDIC_FMRX_UNIT == 29
-bool launch_rx_lj29(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
-{
-	return launch_lj<29, Io32>(nlive, grid, lds, st, kp, da, a);
-}
+#define FMRX_LAUNCH launch_rx_lj29
+constexpr int kUnitLj = 29;
+typedef Io32 UnitIo;
 #elif CORDIC_FMRX_UNIT == 16
-bool launch_rx_io16(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
-{
-	return launch_lj<30, Io16>(nlive, grid, lds, st, kp, da, a);
-}
+#define FMRX_LAUNCH launch_rx_io16
+constexpr int kUnitLj = 30;
+typedef Io16 UnitIo;
 #else
-bool launch_rx_lj30(int nlive, unsigned grid, size_t lds, hipStream_t st,
+#define FMRX_LAUNCH launch_rx_lj30
+constexpr int kUnitLj = 30;
+typedef Io32 UnitIo;
+#endif
+
+bool FMRX_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
 {
-	return launch_lj<30, Io32>(nlive, grid, lds, st, kp, da, a);
+	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
+		hipLaunchKernelGGL((fm_rx_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
+			dim3(grid), dim3(kBlock), lds, st, kp, da, a);
+	});
 }
 
+#if CORDIC_FMRX_UNIT == 30
 // Four consecutive words at any 4-byte-aligned address: one dwordx4 load
 // (span_words4, cordic_span_reduce.h)
 typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -244,23 +223,8 @@ int fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
 		size_t esize, const void *d_work, size_t work_bytes)
 {
-	if (!d_fcw || !d_xval || !d_yval || !d_omag || !d_ofreq || !d_work
-			|| n > (~(size_t)0 >> 4))
-		return CORDIC_ERR_ARGS;
-	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
-		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc)
-		| reinterpret_cast<uintptr_t>(d_last);
-	const uintptr_t samples = reinterpret_cast<uintptr_t>(d_xval)
-		| reinterpret_cast<uintptr_t>(d_yval) | reinterpret_cast<uintptr_t>(d_omag)
-		| reinterpret_cast<uintptr_t>(d_ofreq);
-	if ((words & 3u) || (samples & (esize - 1))
-			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
-		return CORDIC_ERR_ARGS;
-	const Range out[5] = {range_of(d_omag, n * esize), range_of(d_ofreq, n * esize),
-		range_of(d_acc, 4), range_of(d_last, 4), range_of(d_work, work_bytes)};
-	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
-		range_of(d_xval, n * esize), range_of(d_yval, n * esize)};
-	return outputs_overlap(out, in) ? CORDIC_ERR_ARGS : CORDIC_OK;
+	return iq_call_ok(n, d_acc, d_last, d_fcw, d_pm, d_xval, d_yval, d_omag, d_ofreq,
+		esize, d_work, work_bytes) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
@@ -285,15 +249,13 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 	if (cap > kFmrxMaxBlocks)
 		cap = kFmrxMaxBlocks;
 	cap = env_block_cap("CORDIC_FMRX_MAX_BLOCKS", cap);
-	// a span of p passes yields 1024 p - 4 samples: p for at most `cap` spans
-	// (a one-pass span yields 1020, a p-pass span at least 1020 p)
-	const size_t yield1 = kFmrxPass - kFmrxHalo;
-	const size_t npass = (n + yield1 - 1) / yield1;
-	const size_t per_block = (npass + cap - 1) / cap;
-	const size_t span = per_block * kFmrxPass - kFmrxHalo;
-	const unsigned grid = (unsigned)((n + span - 1) / span);
+	const CallSpan cs = call_span(n, cap, kFmrxPass, kFmrxHalo);
+	const size_t span = cs.span;
+	const unsigned grid = (unsigned)cs.grid;
 	// the instance first: nothing is enqueued for a core without one
-	if (!fmx_is_fused(cfg, d_dir, dx) || (esize == 2 && cfg.ww >= 35))
+	static RxLaunch *const units[3] = {launch_rx_lj30, launch_rx_lj29, launch_rx_io16};
+	const fmx::Unit u = fmx::unit_of(cfg.ww, esize);
+	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	uint32_t *work = static_cast<uint32_t *>(d_work);
 	const uint32_t pmask = 0xffffffffu >> (32 - conv.pw);
@@ -307,11 +269,7 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 		n, span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = esize == 2
-		? cfg.ww < 35 && launch_rx_io16(cfg.nlive, grid, lds, st, kp, da, a)
-		: cfg.ww == 35
-			? launch_rx_lj29(cfg.nlive, grid, lds, st, kp, da, a)
-			: launch_rx_lj30(cfg.nlive, grid, lds, st, kp, da, a);
+	const bool done = units[u](cfg.nlive, grid, lds, st, kp, da, a);
 	return tnco::finish(done);
 }
 #endif

@@ -108,5 +108,14 @@ int	launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
 		void *stream);
 
+// (as MixBankTraits, cordic_fm_mix_bank.h)
+struct RxBankTraits {
+	static bool jobs_valid(size_t njobs, RxJobs jobs) { return fmrxb_jobs_valid(njobs, jobs); }
+	static constexpr const SpanRule &rule = kFmrxbRule;
+	static constexpr const char *passes = "CORDIC_FMRXB_PASSES";
+	static constexpr const char *max_spans = "CORDIC_FMRXB_MAX_SPANS";
+	static constexpr int blocks_per_cu = kFmrxbBlocksPerCu;
+};
+
 } // namespace cordic_amd
 #endif

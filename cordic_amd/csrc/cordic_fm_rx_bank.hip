@@ -9,7 +9,8 @@
 //      into a workspace word; a job's first span latches the start word and,
 //      by span_latch_more below, dphase0 + *d_last.
 //   2. fm_rxbank_xydir<LJ, NLIVE, IO>: at most the resident blocks.  A block
-//      stages the plan's direction tables ONCE, then walks spans b, b + grid,
+//      stages the plan's direction tables ONCE (fmx::block_begin / block_ready,
+//      cordic_fm_mix.h), then walks spans b, b + grid,
 //      ...: the job's partials in front of the span added to its start word
 //      (front_sum; skipped for a job's first span), then fmrx::pass_loop
 //      (cordic_fm_rx.h), the loop of the single call.  A span that is not its
@@ -38,7 +39,8 @@
 //
 // The unit is compiled three times, one <LJ, container> each: as itself (<30,
 // Io32>, launch 1 and the host side), as cordic_fm_rx_bank_lj29.hip and as
-// cordic_fm_rx_bank_io16.hip.
+// cordic_fm_rx_bank_io16.hip.  Each defines ONE entry point, FMRXB_LAUNCH,
+// around fmx::with_stages; launch_fmrx_bank indexes the three by fmx::unit_of.
 //
 // Registers: the table in DESIGN.md section 4.8 and profiles/r20/fm_rx.txt.
 #include <hip/hip_runtime.h>
@@ -50,6 +52,7 @@
 #include "cordic_jobs_fused.h"
 #include "cordic_table_nco.h"
 #include "cordic_hostargs.h"
+#include "cordic_devmem.h"
 #include "cordic_fm_rx.h"
 #include "cordic_fm_rx_bank.h"
 #include "cordic_span_reduce.h"
@@ -80,7 +83,7 @@ typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
 		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw);
-BankLaunch launch_rxbank_lj30, launch_rxbank_lj29, launch_rxbank_io16;
+BankLaunch launch_rxbank_lj30, launch_rxbank_lj29, launch_rxbank_io16;	// by fmx::Unit
 
 // launch 2 (see the head of this file)
 template <int LJ, int NLIVE, typename IO>
@@ -89,28 +92,17 @@ __global__ __launch_bounds__(kBlock) void fm_rxbank_xydir(CoreParams kp, DirArgs
 		const uint32_t *__restrict__ start, const uint32_t *__restrict__ part,
 		const uint32_t *__restrict__ prev, const uint32_t *ckmem, uint32_t xw)
 {
-	static_assert(LJ == 29 || LJ == 30, "WW <= 35 cores");
-	static_assert(LJ == 30 || sizeof(typename IO::ielem) == 4,
-		"16-bit ports and WW 35: one by one (fmx_is_fused16)");
 	typedef typename IO::ielem ielem;
-	constexpr int kN = dx_levels(NLIVE);
-	static_assert(kN >= 1 && kN <= kDxMaxLevels, "no group to look up");
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 	const unsigned tid = threadIdx.x;
 	// (the same in all of a wave's lanes: said so, it stays in a scalar)
 	const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
 	uint32_t bk_base[kDxMaxLevels] = {}, lf_base[kDxMaxLevels] = {};
 	dx_lds_layout(da.dx, bk_base, lf_base);
-	fmx::stage_tables<LJ, NLIVE>(kp, da, lds, bk_base, lf_base, tid);
+	fmx::block_begin<LJ, NLIVE, IO>(kp, da, lds, bk_base, lf_base, tid);
 	uint32_t *ex = lds + xw / 4u;
 	__syncthreads();
-
-	// LDS is addressed by byte offset from 0: no static LDS in this kernel
-	if ((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds != 0u)
-		__builtin_trap();
-
-	const fmx::RotRegs rr = fmx::rot_regs<LJ, NLIVE>(kp, da);
+	const fmx::RotRegs rr = fmx::block_ready<LJ, NLIVE>(kp, da, lds);
 	const fmd::LaneConsts ln(conv_params(ckmem, false));
 	unsigned par = 0;
 	for (uint32_t t = blockIdx.x; t < nspans; t += gridDim.x) {
@@ -138,54 +130,32 @@ __global__ __launch_bounds__(kBlock) void fm_rxbank_xydir(CoreParams kp, DirArgs
 	}
 }
 
-template <int LJ, typename IO>
-static bool launch_bank_lj(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw)
-{
-	switch (nlive) {
-#define X(N) case N: \
-	if (da.dx.n != dx_levels(N)) \
-		return false; \
-	hipLaunchKernelGGL((fm_rxbank_xydir<LJ, N, IO>), dim3(grid), dim3(kBlock), lds, st, \
-		kp, da, spans, nspans, start, part, prev, ckmem, xw); \
-	return true;
-	FMX_STAGES(X)
-#undef X
-	default:
-		return false;
-	}
-}
-
+// this unit's <LJ, container> and entry point
 #if CORDIC_FMRXB_UNIT == 29
-bool launch_rxbank_lj29(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw)
-{
-	return launch_bank_lj<29, Io32>(nlive, grid, lds, st, kp, da, spans, nspans, start,
-		part, prev, ckmem, xw);
-}
+#define FMRXB_LAUNCH launch_rxbank_lj29
+constexpr int kUnitLj = 29;
+typedef Io32 UnitIo;
 #elif CORDIC_FMRXB_UNIT == 16
-bool launch_rxbank_io16(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw)
-{
-	return launch_bank_lj<30, Io16>(nlive, grid, lds, st, kp, da, spans, nspans, start,
-		part, prev, ckmem, xw);
-}
+#define FMRXB_LAUNCH launch_rxbank_io16
+constexpr int kUnitLj = 30;
+typedef Io16 UnitIo;
 #else
-bool launch_rxbank_lj30(int nlive, unsigned grid, size_t lds, hipStream_t st,
+#define FMRXB_LAUNCH launch_rxbank_lj30
+constexpr int kUnitLj = 30;
+typedef Io32 UnitIo;
+#endif
+
+bool FMRXB_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
 		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw)
 {
-	return launch_bank_lj<30, Io32>(nlive, grid, lds, st, kp, da, spans, nspans, start,
-		part, prev, ckmem, xw);
+	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
+		hipLaunchKernelGGL((fm_rxbank_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
+			dim3(grid), dim3(kBlock), lds, st, kp, da, spans, nspans, start, part, prev,
+			ckmem, xw);
+	});
 }
-#endif
 
 } // namespace fmrx
 
@@ -193,15 +163,7 @@ bool launch_rxbank_lj30(int nlive, unsigned grid, size_t lds, hipStream_t st,
 int fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv)
 {
 	const dev::CoreParams ck = make_params_jobs(conv);
-	*d_conv = nullptr;
-	if (hipMalloc((void **)d_conv, sizeof ck) == hipSuccess
-			&& hipMemcpy(*d_conv, &ck, sizeof ck, hipMemcpyHostToDevice) == hipSuccess)
-		return CORDIC_OK;
-	if (*d_conv)
-		(void)hipFree(*d_conv);
-	*d_conv = nullptr;
-	(void)hipGetLastError();
-	return CORDIC_ERR_DEVICE;
+	return dev_upload(&ck, sizeof ck, d_conv) ? CORDIC_OK : CORDIC_ERR_DEVICE;
 }
 
 int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
@@ -222,15 +184,16 @@ int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 	// launch 1 has 8 waves a SIMD: 8 blocks of 4 waves a CU
 	const SpanGrids g = span_grids(nspans, cus, 8, "CORDIC_FMRXB_MAX_BLOCKS", per_cu);
 	// the instance first: nothing is enqueued for a core without one
-	BankLaunch *go = io16 ? (cfg.ww < 35 ? launch_rxbank_io16 : nullptr)
-		: cfg.ww == 35 ? launch_rxbank_lj29 : launch_rxbank_lj30;
-	if (!go || !fmx_is_fused(cfg, d_dir, dx))
+	static BankLaunch *const units[3] = {launch_rxbank_lj30, launch_rxbank_lj29,
+		launch_rxbank_io16};
+	const fmx::Unit u = fmx::unit_of(cfg.ww, io16 ? 2 : 4);
+	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	hipLaunchKernelGGL((span_reduce<RxSpan, 256>), dim3(g.reduce), dim3(256), 0, st,
 		d_spans, nspans, d_start, d_part);
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	return tnco::finish(go(cfg.nlive, g.walk, lds, st, kp, da, d_spans, nspans,
+	return tnco::finish(units[u](cfg.nlive, g.walk, lds, st, kp, da, d_spans, nspans,
 		d_start, d_part, d_prev, d_conv, xw));
 }
 #endif

@@ -1,6 +1,7 @@
 // cordic_hostargs.h -- argument checks that the FM units' entry points share
 // (cordic_fm_demod.hip, cordic_fm_mix.hip, cordic_table_fm.hip): byte ranges and
-// the rule "no output range over another output or any input", and the
+// the rule "no output range over another output or any input", the whole check
+// of an I/Q call with tuning words, the span of a single call's block and the
 // environment's cap on a grid.  Plain C++ that touches no device, so that a
 // stand-alone program can run it under a sanitizer (tests/test_hostargs.py).
 // (A bank of many jobs sorts its ranges instead: BankRanges, cordic_bank_host.h.)
@@ -49,6 +50,53 @@ inline bool outputs_overlap(const Range (&out)[NOUT], const Range (&in)[NIN],
 				return true;
 	}
 	return false;
+}
+
+// The check of an I/Q call with per-sample tuning words (the FM mixer, the
+// tuned FM receiver), n > 0 samples of `esize` bytes (4 or 2): d_fcw, the two
+// sample inputs, the two sample outputs and d_work are there (d_pm, d_acc and
+// d_last may be NULL), n <= SIZE_MAX >> 4, the words on the grid of 4, the
+// sample arrays on that of esize, d_work on that of 16, and no output range --
+// the two arrays, the words at d_acc and d_last, the `work_bytes` of d_work --
+// over another output or any input, by the true byte ranges.
+inline bool iq_call_ok(size_t n, const void *d_acc, const void *d_last,
+		const void *d_fcw, const void *d_pm, const void *d_x, const void *d_y,
+		const void *d_o0, const void *d_o1, size_t esize, const void *d_work,
+		size_t work_bytes)
+{
+	if (!d_fcw || !d_x || !d_y || !d_o0 || !d_o1 || !d_work || n > (~(size_t)0 >> 4))
+		return false;
+	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
+		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc)
+		| reinterpret_cast<uintptr_t>(d_last);
+	const uintptr_t samples = reinterpret_cast<uintptr_t>(d_x)
+		| reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_o0)
+		| reinterpret_cast<uintptr_t>(d_o1);
+	if ((words & 3u) || (samples & (esize - 1))
+			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
+		return false;
+	const Range out[5] = {range_of(d_o0, n * esize), range_of(d_o1, n * esize),
+		range_of(d_acc, 4), range_of(d_last, 4), range_of(d_work, work_bytes)};
+	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
+		range_of(d_x, n * esize), range_of(d_y, n * esize)};
+	return !outputs_overlap(out, in);
+}
+
+// The span of a single call of n > 0 samples on at most `cap` blocks: every
+// block owns `span` consecutive samples -- whole passes of `pass`, less the
+// `halo` samples in front that a receiver's block computes again -- and the
+// last one what is left; grid <= cap.  A span of p passes yields p * pass -
+// halo samples, at least p * (pass - halo): p for at most `cap` spans.
+struct CallSpan {
+	size_t	span, grid;
+};
+inline CallSpan call_span(size_t n, size_t cap, size_t pass, size_t halo)
+{
+	const size_t yield1 = pass - halo;
+	const size_t npass = (n + yield1 - 1) / yield1;
+	const size_t per_block = (npass + cap - 1) / cap;
+	const size_t span = per_block * pass - halo;
+	return CallSpan{span, (n + span - 1) / span};
 }
 
 // min(cap, the value of the environment variable `name`) for values >= 1; read

@@ -411,3 +411,30 @@ def test_the_rx_rule_and_the_job_checks_under_address_and_ub_sanitizers(tmp_path
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "rx bank host ok" in r.stdout
+
+
+def test_the_prologue_and_the_chooser_are_shared_not_pasted():
+    """one block prologue and one instance chooser for fm_mix_xydir,
+    fm_mixbank_xydir, fm_rx_xydir and fm_rxbank_xydir, in cordic_fm_mix.h"""
+    csrc = os.path.join(ROOT, "cordic_amd", "csrc")
+    names = ("cordic_fm_mix.h", "cordic_fm_rx.h", "cordic_fm_demod.h", "cordic_fm_mix.hip",
+             "cordic_fm_mix_bank.hip", "cordic_fm_rx.hip", "cordic_fm_rx_bank.hip")
+    text = {n: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, n)).read()) for n in names}
+
+    def places(pattern):
+        return [n for n in names for _ in re.finditer(pattern, text[n])]
+
+    # the switch over the stage counts (the macro's own definition aside)
+    assert places(r"(?<!#define )FMX_STAGES\(X\)") == ["cordic_fm_mix.h"]
+    assert places(r"__builtin_trap") == ["cordic_fm_mix.h"]
+    # the staging of the tables: one call (its definition has no `<` behind the name)
+    assert places(r"\bstage_tables<") == ["cordic_fm_mix.h"]
+    # every kernel goes through the two pieces, and every launcher through the switch
+    for unit in names[3:]:
+        assert len(re.findall(r"\bblock_begin<LJ, NLIVE, IO>\(", text[unit])) == 1, unit
+        assert len(re.findall(r"\bblock_ready<LJ, NLIVE>\(", text[unit])) == 1, unit
+        assert len(re.findall(r"\bwith_stages\(", text[unit])) >= 1, unit
+        assert "static_assert(LJ ==" not in text[unit], unit
+        assert not re.search(r"switch\s*\(nlive\)", text[unit]), unit
+    # "WW 35 is LJ 29" and "no Io16 at WW 35" have one home
+    assert places(r"ww\s*(==|<|>=)\s*35") == ["cordic_fm_mix.h"] * 2

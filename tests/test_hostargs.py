@@ -16,6 +16,111 @@ static int failures;
 #define EXPECT(c) do { if (!(c)) { std::printf("line %d: %s\n", __LINE__, #c); \
 	failures++; } } while (0)
 
+// the I/Q call check at n = 64 on samples of es bytes: every array 1 KiB apart
+// on the 16-byte grid, the words and the workspace behind them
+static void iq_calls(const size_t es)
+{
+	alignas(16) static unsigned char a[16384];
+	const size_t n = 64, wb = 256;
+	unsigned char *f = a + 1024, *m = a + 2048, *x = a + 3072, *y = a + 4096,
+		*o0 = a + 5120, *o1 = a + 6144, *acc = a + 7168, *last = a + 7184,
+		*w = a + 8192;
+	auto ok = [&](const void *pacc, const void *plast, const void *pf, const void *pm,
+			const void *px, const void *py, const void *p0, const void *p1,
+			const void *pw, size_t nn = 64) {
+		return iq_call_ok(nn, pacc, plast, pf, pm, px, py, p0, p1, es, pw, wb);
+	};
+	EXPECT(ok(acc, last, f, m, x, y, o0, o1, w));
+	EXPECT(ok(acc, last, f, m, x, x, o0, o1, w));		// x aliased to y
+	EXPECT(ok(acc, last, f, nullptr, x, y, o0, o1, w));	// the optional ones
+	EXPECT(ok(nullptr, last, f, m, x, y, o0, o1, w));
+	EXPECT(ok(acc, nullptr, f, m, x, y, o0, o1, w));
+	EXPECT(ok(nullptr, nullptr, f, nullptr, x, y, o0, o1, w));
+	// each required pointer
+	EXPECT(!ok(acc, last, nullptr, m, x, y, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m, nullptr, y, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, nullptr, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, nullptr, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, nullptr, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1, nullptr));
+	// a word pointer off the 4-byte grid
+	EXPECT(!ok(acc + 2, last, f, m, x, y, o0, o1, w));
+	EXPECT(!ok(acc, last + 1, f, m, x, y, o0, o1, w));
+	EXPECT(!ok(acc, last, f + 2, m, x, y, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m + 1, x, y, o0, o1, w));
+	// a sample pointer off the grid of es, and on it
+	const size_t off = es / 2;
+	EXPECT(!ok(acc, last, f, m, x + off, y, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y + off, o0, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0 + off, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1 + off, w));
+	EXPECT(ok(acc, last, f, m, x + es, y + es, o0 + es, o1 + es, w));
+	// d_work off the 16-byte grid
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1, w + 8));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1, w + 4));
+	// an output beginning one element inside each kind of input
+	EXPECT(!ok(acc, last, f, m, x, y, f + 4 * (n - 1), o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, m + 4 * (n - 1), w));
+	EXPECT(!ok(acc, last, f, m, x, y, x + es * (n - 1), o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, y + es * (n - 1), w));
+	// ... and touching it, one element on
+	EXPECT(ok(acc, last, f, m, x, y, f + 4 * n, o1, w));
+	EXPECT(ok(acc, last, f, m, x, y, o0, m + 4 * n, w));
+	EXPECT(ok(acc, last, f, m, x, y, x + es * n, o1, w));
+	EXPECT(ok(acc, last, f, m, x, y, o0, y + es * n, w));
+	// the two outputs over each other by one element, and touching
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o0 + es * (n - 1), w));
+	EXPECT(ok(acc, last, f, m, x, y, o0, o0 + es * n, w));
+	// d_last inside omag, and just behind it
+	EXPECT(!ok(acc, o0 + es * n - 4, f, m, x, y, o0, o1, w));
+	EXPECT(ok(acc, o0 + es * n, f, m, x, y, o0, o1, w));
+	EXPECT(!ok(o1 + 4, last, f, m, x, y, o0, o1, w));	// d_acc inside ofreq
+	EXPECT(!ok(acc, x + 4, f, m, x, y, o0, o1, w));		// d_last inside an input
+	EXPECT(!ok(acc, acc, f, m, x, y, o0, o1, w));		// d_acc == d_last
+	EXPECT(ok(acc, acc + 4, f, m, x, y, o0, o1, w));
+	// the work_bytes of d_work reach the first output, and end where it begins
+	EXPECT(!ok(acc, last, f, m, x, y, w + wb - 16, o1, w));
+	EXPECT(ok(acc, last, f, m, x, y, w + wb, o1, w));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1, o0 - wb + 16));
+	EXPECT(ok(acc, last, f, m, x, y, o0, o1, o0 - wb));
+	// the longest call, and one sample more (nothing is dereferenced)
+	EXPECT(!ok(nullptr, nullptr, f, nullptr, x, x, o0, o0, w, (~(size_t)0 >> 4) + 1));
+	EXPECT(!ok(acc, last, f, m, x, y, o0, o1, w, (~(size_t)0 >> 4) + 1));
+}
+
+// call_span against the two formulas the launchers had, written out
+static void spans()
+{
+	const size_t big = ~(size_t)0 >> 4;
+	const size_t ns[] = {1, 3, 4, 5, 1019, 1020, 1021, 1023, 1024, 1025, 2039, 2040, 2041,
+		2048, 4097, 3 * 1020, 3 * 1020 + 1, ((size_t)1 << 20) + 7, (size_t)1 << 28, big};
+	const size_t caps[] = {1, 2, 3, 7, 1024, 4096};
+	for (size_t n : ns)
+		for (size_t cap : caps) {
+			{	// the mixer's
+				const size_t npass = (n + 1024 - 1) / 1024;
+				const size_t per = (npass + cap - 1) / cap;
+				const size_t span = per * 1024;
+				const size_t grid = (npass + per - 1) / per;
+				const CallSpan cs = call_span(n, cap, 1024, 0);
+				EXPECT(cs.span == span && cs.grid == grid);
+				EXPECT(cs.grid <= cap);
+				EXPECT((cs.grid - 1) * cs.span < n && (n - 1) / cs.span < cs.grid);
+			}
+			{	// the receiver's
+				const size_t yield1 = 1020;
+				const size_t npass = (n + yield1 - 1) / yield1;
+				const size_t per = (npass + cap - 1) / cap;
+				const size_t span = per * 1024 - 4;
+				const size_t grid = (n + span - 1) / span;
+				const CallSpan cs = call_span(n, cap, 1024, 4);
+				EXPECT(cs.span == span && cs.grid == grid);
+				EXPECT(cs.grid <= cap);
+				EXPECT((cs.grid - 1) * cs.span < n && (n - 1) / cs.span < cs.grid);
+			}
+		}
+}
+
 int main()
 {
 	static unsigned char a[4096];
@@ -128,6 +233,9 @@ int main()
 		unsetenv(name);
 		EXPECT(env_block_cap(name, 3) == 3);
 	}
+	iq_calls(4);
+	iq_calls(2);
+	spans();
 	if (!failures)
 		std::printf("hostargs ok\n");
 	return failures ? 1 : 0;

@@ -324,6 +324,29 @@ ABI = {
                                        C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_mix_decim_workspace": (C.c_size_t, [C.c_void_p, C.c_size_t,
+                                                        C.c_uint32]),
+    "cordic_plan_fm_mix_decim": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "cordic_plan_fm_mix_decim16_workspace": (C.c_size_t, [C.c_void_p,
+                                                          C.c_size_t,
+                                                          C.c_uint32]),
+    "cordic_plan_fm_mix_decim16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                             C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "cordic_mixbank_create_decim": (C.c_int, [C.c_void_p, C.c_uint32,
+                                              C.c_size_t, C.c_void_p,
+                                              C.POINTER(C.c_void_p)]),
+    "cordic_mixbank_create_decim16": (C.c_int, [C.c_void_p, C.c_uint32,
+                                                C.c_size_t, C.c_void_p,
+                                                C.POINTER(C.c_void_p)]),
     "cordic_mixbank_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.POINTER(C.c_void_p)]),
     "cordic_mixbank_create16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
@@ -682,6 +705,52 @@ class Plan:
             self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
             _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
             "cordic_plan_fm_mix16")
+
+    def fm_mix_decim_workspace(self, n, log2r):
+        """cordic_plan_fm_mix_decim_workspace: bytes of device scratch an
+        fm_mix_decim call of n samples at R = 2**log2r needs on this plan
+        (16-byte aligned); 0 where the call would fail"""
+        return int(lib().cordic_plan_fm_mix_decim_workspace(self._h, n, log2r))
+
+    def fm_mix_decim16_workspace(self, n, log2r):
+        """cordic_plan_fm_mix_decim16_workspace: the same for fm_mix_decim16"""
+        return int(lib().cordic_plan_fm_mix_decim16_workspace(self._h, n, log2r))
+
+    def _fm_mix_decim(self, name, log2r, fcw, x, y, ox, oy, work, pm, n, phase0,
+                      acc, stream):
+        n = x.numel() if n is None else n
+        if work is None and n:
+            raise TypeError("work: a device buffer of %s_workspace(n, log2r) "
+                            "bytes" % name)
+        need = getattr(self, name + "_workspace")(n, log2r)
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and need and work.numel() * work.element_size() < need:
+            raise ValueError("work: %d bytes, %s_workspace(%d, %d) = %d"
+                             % (work.numel() * work.element_size(), name, n,
+                                log2r, need))
+        cname = "cordic_plan_" + name
+        _check(getattr(lib(), cname)(
+            self._h, n, log2r, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff,
+            _ptr(acc), _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work),
+            _stream(stream)), cname)
+
+    def fm_mix_decim(self, log2r, fcw, x, y, ox, oy, work=None, pm=None, n=None,
+                     phase0=0, acc=None, stream=None):
+        """cordic_plan_fm_mix_decim: fm_mix with an integrate-and-dump by R =
+        2**log2r behind the rotator -- ox[j], oy[j] = floor(the sum of the R
+        tuned samples jR .. jR + R - 1 / R), n >> log2r elements each; n a
+        multiple of R, log2r in 0 .. 8 (0: fm_mix itself).  work: device
+        scratch of fm_mix_decim_workspace(n, log2r) bytes, the caller's."""
+        self._fm_mix_decim("fm_mix_decim", log2r, fcw, x, y, ox, oy, work, pm, n,
+                           phase0, acc, stream)
+
+    def fm_mix_decim16(self, log2r, fcw, x, y, ox, oy, work=None, pm=None,
+                       n=None, phase0=0, acc=None, stream=None):
+        """cordic_plan_fm_mix_decim16: fm_mix_decim on int16 x, y, ox, oy
+        (cores with IW and OW <= 16); fcw, pm and acc stay 32-bit words."""
+        _same16("cordic_plan_fm_mix_decim16", x, y, ox, oy)
+        self._fm_mix_decim("fm_mix_decim16", log2r, fcw, x, y, ox, oy, work, pm,
+                           n, phase0, acc, stream)
 
     def fm_rx_workspace(self, conv, n):
         """cordic_plan_fm_rx_workspace: bytes of device scratch an fm_rx call
@@ -2110,12 +2179,16 @@ class MixBank(_SpanBank):
     run in two launches.  jobs: tuples (fcw, pm, x, y, ox, oy, n, phase0, acc)
     or dicts with those keys; fcw, x, y, ox, oy are int32 tensors or device
     addresses, pm one more or None, acc a one-word device tensor or None; n
-    None: fcw.numel().  The plan must stay open as long as the bank."""
+    None: fcw.numel().  The plan must stay open as long as the bank.
+    log2r = k > 0 (cordic_mixbank_create_decim): a bank of fm_mix_decim jobs
+    -- one k for the whole bank, every n a multiple of 2**k, ox and oy of
+    n >> k elements."""
 
     _prefix = "cordic_mixbank"
     _create = "cordic_mixbank_create"
+    _create_decim = "cordic_mixbank_create_decim"
 
-    def __init__(self, plan, jobs):
+    def __init__(self, plan, jobs, log2r=None):
         jobs = [tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict)
                 else tuple(jb) for jb in jobs]
         self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
@@ -2131,8 +2204,14 @@ class MixBank(_SpanBank):
             arr[k].n = fcw.numel() if n is None else n
             arr[k].phase0 = (phase0 or 0) & 0xffffffff
         h = C.c_void_p()
-        _check(getattr(lib(), self._create)(getattr(plan, "_h", plan), len(jobs),
-                                            arr, C.byref(h)), self._create)
+        if log2r is None:
+            _check(getattr(lib(), self._create)(getattr(plan, "_h", plan),
+                                                len(jobs), arr, C.byref(h)),
+                   self._create)
+        else:
+            _check(getattr(lib(), self._create_decim)(
+                getattr(plan, "_h", plan), log2r, len(jobs), arr, C.byref(h)),
+                self._create_decim)
         self._h = h
 
 
@@ -2143,13 +2222,14 @@ class MixBank16(MixBank):
     MixBank's."""
 
     _create = "cordic_mixbank_create16"
+    _create_decim = "cordic_mixbank_create_decim16"
 
-    def __init__(self, plan, jobs):
+    def __init__(self, plan, jobs, log2r=None):
         for jb in jobs:
             jb = tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict) \
                 else tuple(jb)
             _same16(self._create, *jb[2:6])
-        MixBank.__init__(self, plan, jobs)
+        MixBank.__init__(self, plan, jobs, log2r)
 
 
 class _CFmRxJob(C.Structure):

@@ -263,12 +263,113 @@ int cordic_plan_fm_mix16(const cordic_plan *plan, size_t n, const uint32_t *d_fc
 	return launch_fmx_narrow(n, wox, woy, d_oxval, d_oyval, stream);
 }
 
+// ---- the decimating mixer: integrate-and-dump by 2^log2r behind the rotator
+// (cordic_fm_mix.h), on either container.  CORDIC_FMXD_FALLBACK=1 in the
+// environment (read at every single call and workspace query; a test and A/B
+// knob) sends a fused plan's single call through the fallback.  The workspace
+// grows with it and a call cannot see the size of the caller's buffer, so it
+// has to be set before the query as well as before the call, as
+// tools/bench_fm_mix_decim.py does.  Banks ignore it.
+static bool fm_mix_decim_fused(const cordic_plan *plan, bool io16)
+{
+	const char *e = std::getenv("CORDIC_FMXD_FALLBACK");
+	if (e && e[0] == '1')
+		return false;
+	return io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan);
+}
+
+// a plan that the call accepts; 0 where the call would fail
+static size_t fm_mix_decim_work_bytes(const cordic_plan *plan, bool io16, bool fused,
+		size_t n, uint32_t log2r)
+{
+	const size_t mix = io16 ? fm_mix16_work_bytes(plan, n)
+		: fmx_work_bytes(fm_mix_fused(plan), n);
+	if (!fmxd_shape_ok(n, log2r))
+		return 0;
+	return log2r ? fmxd_work_bytes(fused, mix, n, io16 ? 2 : 4) : mix;
+}
+
+static int fm_mix_decim(const cordic_plan *plan, bool io16, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const void *d_xval, const void *d_yval, void *d_oxval, void *d_oyval,
+		void *d_work, void *stream, bool fused)
+{
+	if (!fmxd_shape_ok(n, log2r))
+		return CORDIC_ERR_ARGS;
+	if (log2r == 0 || n == 0) {	// the mixer itself: its bits, its launches
+		if (io16)
+			return cordic_plan_fm_mix16(plan, n, d_fcw, d_pm, phase0, d_acc,
+				static_cast<const int16_t *>(d_xval), static_cast<const int16_t *>(d_yval),
+				static_cast<int16_t *>(d_oxval), static_cast<int16_t *>(d_oyval), d_work,
+				stream);
+		return cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc,
+			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
+			static_cast<int32_t *>(d_oxval), static_cast<int32_t *>(d_oyval), d_work,
+			stream);
+	}
+	const size_t esize = io16 ? 2 : 4;
+	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval, d_oyval,
+			esize, d_work, fm_mix_decim_work_bytes(plan, io16, fused, n, log2r), log2r))
+		return rc;
+	if (fused)
+		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm, phase0,
+			d_acc, d_xval, d_yval, d_oxval, d_oyval, esize, d_work, stream, log2r);
+	// the fallback: the mixer's call into two full-rate arrays behind its own
+	// workspace, then the sums
+	unsigned char *w = static_cast<unsigned char *>(d_work);
+	const size_t at = io16 ? fm_mix16_work_bytes(plan, n)
+		: fmx_work_bytes(fm_mix_fused(plan), n);
+	void *tx = w + at, *ty = w + at + fmxd_array_bytes(n, esize);
+	if (int rc = fm_mix_decim(plan, io16, n, 0, d_fcw, d_pm, phase0, d_acc, d_xval,
+			d_yval, tx, ty, d_work, stream, false))
+		return rc;
+	return launch_fmx_decimate(n, log2r, esize, tx, ty, d_oxval, d_oyval, stream);
+}
+
+size_t cordic_plan_fm_mix_decim_workspace(const cordic_plan *plan, size_t n, uint32_t log2r)
+{
+	if (fm_mix_plan_ok(plan) != CORDIC_OK)
+		return 0;
+	return fm_mix_decim_work_bytes(plan, false, fm_mix_decim_fused(plan, false), n, log2r);
+}
+
+size_t cordic_plan_fm_mix_decim16_workspace(const cordic_plan *plan, size_t n,
+		uint32_t log2r)
+{
+	if (fm_mix16_plan_ok(plan) != CORDIC_OK)
+		return 0;
+	return fm_mix_decim_work_bytes(plan, true, fm_mix_decim_fused(plan, true), n, log2r);
+}
+
+int cordic_plan_fm_mix_decim(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval, int32_t *d_oxval,
+		int32_t *d_oyval, void *d_work, void *stream)
+{
+	if (int rc = fm_mix_plan_ok(plan))
+		return rc;
+	return fm_mix_decim(plan, false, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+		d_oxval, d_oyval, d_work, stream, fm_mix_decim_fused(plan, false));
+}
+
+int cordic_plan_fm_mix_decim16(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval, int16_t *d_oxval,
+		int16_t *d_oyval, void *d_work, void *stream)
+{
+	if (int rc = fm_mix16_plan_ok(plan))
+		return rc;
+	return fm_mix_decim(plan, true, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+		d_oxval, d_oyval, d_work, stream, fm_mix_decim_fused(plan, true));
+}
+
 // ---- FM mixer banks: many of those jobs in two launches
 // (cordic_fm_mix_bank.h)
 struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
 	bool	io16 = false;			// the jobs' sample arrays hold int16
 	uint32_t passes = 0;
+	uint32_t log2r = 0;			// > 0: a decimating bank
 	SpanTable<MixSpan> spans;		// fused
 };
 
@@ -335,8 +436,11 @@ static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
 		[&](bool io16) { return io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan); },
 		[&](bool io16) { return io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan); },
 		[&](bool io16, size_t n) {
-			return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(false, n);
-		}, cordic_mixbank_destroy, [](cordic_mixbank *) { return CORDIC_OK; });
+			return fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r);
+		}, cordic_mixbank_destroy, [&](cordic_mixbank *b) {
+			b->log2r = jobs.log2r;
+			return CORDIC_OK;
+		});
 }
 
 int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
@@ -349,6 +453,18 @@ int cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
 		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
 {
 	return mixbank_create(plan, njobs, jobs, bank);
+}
+
+int cordic_mixbank_create_decim(const cordic_plan *plan, uint32_t log2r, size_t njobs,
+		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
+{
+	return mixbank_create(plan, njobs, MixJobs(jobs, log2r), bank);
+}
+
+int cordic_mixbank_create_decim16(const cordic_plan *plan, uint32_t log2r, size_t njobs,
+		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
+{
+	return mixbank_create(plan, njobs, MixJobs(jobs, log2r), bank);
 }
 
 void cordic_mixbank_destroy(cordic_mixbank *bank)
@@ -381,17 +497,12 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 	return bank_run(*bank, [&] {
 		const SpanTable<MixSpan> &t = bank->spans;
 		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, t.d_spans, t.nspans,
-			t.start(), t.part(), bank->cus, bank->io16, stream);
+			t.start(), t.part(), bank->cus, bank->io16, stream, bank->log2r);
 	}, [&](const cordic_fmmix_job &jb) {
-		if (bank->io16)
-			return cordic_plan_fm_mix16(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm,
-				jb.phase0, jb.d_acc, reinterpret_cast<const int16_t *>(jb.d_xval),
-				reinterpret_cast<const int16_t *>(jb.d_yval),
-				reinterpret_cast<int16_t *>(jb.d_oxval),
-				reinterpret_cast<int16_t *>(jb.d_oyval), bank->d_work, stream);
-		return cordic_plan_fm_mix(plan, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
-			jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval, bank->d_work,
-			stream);
+		// (log2r 0: the mixer's own call, cordic_plan_fm_mix or _mix16)
+		return fm_mix_decim(plan, bank->io16, (size_t)jb.n, bank->log2r, jb.d_fcw,
+			jb.d_pm, jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval,
+			bank->d_work, stream, false);
 	});
 }
 

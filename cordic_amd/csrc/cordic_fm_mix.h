@@ -8,8 +8,10 @@
 // The launcher and the host checks for cordic_abi.cpp, where the plan and with
 // it the three entry points live; the fallback (cordic_phase_accumulate into
 // the workspace, then cordic_plan_p2r) is put together there, and so is the
-// 16-bit fallback (widen, the 32-bit call, narrow).  Behind them, for
-// hipcc only, the device functions that the kernel of this call and the kernel
+// 16-bit fallback (widen, the 32-bit call, narrow).  The decimating mixer
+// (cordic_plan_fm_mix_decim, _decim16: R = 2^k tuned samples summed, one kept)
+// is the same launcher with k, its workspace and its fallback's launch.  Behind
+// them, for hipcc only, the device functions that the kernel of this call and the kernel
 // of the FM mixer banks (cordic_fm_mix_bank.hip) share.
 //
 // Neither unit holds a kernel of the DESIGN section 4.4 sweep (no swept
@@ -75,19 +77,49 @@ static_assert(kFmxWorkBytes % 16 == 0, "the widened arrays sit on the 16-byte gr
 // Alignment -- the four sample arrays on the grid of `esize`, their element
 // size in bytes (4 or 2), the words on that of 4, d_work on that of 16 -- and
 // no output range (d_acc and the `work_bytes` of d_work included) over
-// anything else, by the true byte ranges; nothing is launched.  n > 0.
+// anything else, by the true byte ranges; nothing is launched.  n > 0.  log2r:
+// the two outputs hold n >> log2r elements (the decimating mixer).
 int	fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
-		size_t work_bytes);
+		size_t work_bytes, uint32_t log2r = 0);
 
 // The fused path: two launches on `stream` (fm_reduce, then fm_mix_xydir),
 // nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
 // The caller has checked fmx_is_fused / fmx_is_fused16 and fmx_check_call.
+// log2r = k in 1 .. 8: launch 2 is fm_mix_decim_xydir (cordic_fm_mix_decim.hip),
+// which writes n >> k sums; n is a multiple of 2^k.
 int	launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
 		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
-		void *d_oyval, size_t esize, void *d_work, void *stream);
+		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r = 0);
+
+// ---- the decimating mixer (cordic_plan_fm_mix_decim, _decim16), k = log2r in
+// 1 .. 8 and n a multiple of 2^k.  Fused where the mixer is, with the mixer's
+// workspace.  Its fallback is the mixer's call -- whatever path that takes --
+// into two full-rate arrays inside d_work and one elementwise launch behind
+// it: [the mixer call's workspace | tx | ty], each part on the 16-byte grid.
+constexpr size_t fmxd_array_bytes(size_t n, size_t esize)
+{
+	return (n * esize + 15) & ~(size_t)15;
+}
+// mix_bytes: the mixer call's own workspace for n samples of that container
+constexpr size_t fmxd_work_bytes(bool fused, size_t mix_bytes, size_t n, size_t esize)
+{
+	return !n ? 0 : fused ? kFmxWorkBytes : mix_bytes + 2 * fmxd_array_bytes(n, esize);
+}
+
+// log2r <= 8 and n a multiple of 2^log2r
+constexpr bool fmxd_shape_ok(uint64_t n, uint32_t log2r)
+{
+	return log2r <= 8 && !(n & (((uint64_t)1 << log2r) - 1));
+}
+
+// The fallback's launch, on `stream`: d_ox[j], d_oy[j] = floor(the sum of 2^k
+// consecutive elements of d_tx, d_ty / 2^k), j < n >> k; arrays of int32
+// (esize 4) or int16 (2) at any element alignment.
+int	launch_fmx_decimate(size_t n, uint32_t log2r, size_t esize, const void *d_tx,
+		const void *d_ty, void *d_ox, void *d_oy, void *stream);
 
 // The two elementwise launches of the 16-bit fallback, on `stream`: x and y
 // into int32 arrays, ox and oy back into shorts (the low 16 bits: the 32-bit
@@ -112,6 +144,18 @@ namespace cordic_amd {
 namespace fmx {
 
 using namespace dev;
+
+// the arguments of launch 2 of a single call (fm_mix_xydir, and
+// fm_mix_decim_xydir of cordic_fm_mix_decim.hip)
+struct FmxArgs {
+	const uint32_t *fcw, *pm;	// pm may be NULL
+	uint32_t *acc;			// may be NULL
+	const uint32_t *work;		// fm_reduce's: [0] start, [4 + b] partials
+	const void *x, *y;		// int32 or int16, by the kernel's container
+	void	*ox, *oy;
+	size_t	n, span;		// span: samples per block, whole passes
+	uint32_t xw;			// LDS byte offset of the 12 exchange words
+};
 
 typedef const __attribute__((address_space(3))) u32x4 lds_entry;
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -293,6 +337,73 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v)
 	return v;
 }
 
+// ---- the decimating mixer's integrate-and-dump (pass_loop with DECIM), by R =
+// 2^k, 1 <= k <= 8 (wave-uniform).
+//
+// The sum of v over this lane and the g - 1 lanes in front of it, g = 1, 2, 4,
+// .. 64 (wave-uniform), for the LAST lane of every aligned group of g: the
+// inclusive wave scan less its value a group in front, which one ds_bpermute
+// fetches (no LDS is addressed); the wave's first group has nothing in front.
+// The scan wraps modulo 2^32 and the difference undoes it.  Every lane of the
+// wave runs this (DPP and the permute read inactive lanes as garbage).
+__device__ __forceinline__ uint32_t group_sum(uint32_t v, const uint32_t g,
+		const unsigned lane)
+{
+	const uint32_t s = wave_scan(v);
+	const uint32_t p = (uint32_t)__builtin_amdgcn_ds_bpermute(
+		(int)(((lane - g) & 63u) << 2), (int)s);
+	return s - (lane >= g ? p : 0u);
+}
+
+// rx / ry: this lane's 4 tuned samples, numbers i .. i + 3 of the job (i a
+// multiple of 4); hi: the job's or span's end, a multiple of R.  Writes
+// ox[i >> k], oy[i >> k] = floor(sum of the group / R) for every group in front
+// of hi, from the lane that holds the group's last sample, and nothing else.  A
+// group is 2^(k-2) neighbouring lanes (k = 1: half a lane), never more than a
+// wave, and lies wholly in front of hi or wholly behind.  The exact sum has OW
+// + k bits; it travels as sum(v >> k), below 2^31 in magnitude, and sum(v & (R
+// - 1)), below 2^16: floor(S / R) = the first + (the second >> k).  Plain
+// stores: non-temporal ones measured the same (profiles/r22/ab_nt_stores.txt).
+template <typename T>
+__device__ __forceinline__ void store_decim(const i32x4 &rx, const i32x4 &ry, T *ox,
+		T *oy, const size_t i, const size_t hi, const uint32_t k, const unsigned tid)
+{
+	if (k == 1) {		// two outputs per lane
+		const size_t o = i >> 1;
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			if (i + 2 * h < hi) {
+				const int32_t a = rx[2 * h], b = rx[2 * h + 1];
+				const int32_t c = ry[2 * h], d = ry[2 * h + 1];
+				ox[o + h] = (T)((a >> 1) + (b >> 1) + (((a & 1) + (b & 1)) >> 1));
+				oy[o + h] = (T)((c >> 1) + (d >> 1) + (((c & 1) + (d & 1)) >> 1));
+			}
+		}
+		return;
+	}
+	const uint32_t low = (1u << k) - 1u;
+	uint32_t hx = 0, lx = 0, hy = 0, ly = 0;
+#pragma unroll
+	for (int v = 0; v < kVec; v++) {
+		hx += (uint32_t)(rx[v] >> k);
+		lx += (uint32_t)rx[v] & low;
+		hy += (uint32_t)(ry[v] >> k);
+		ly += (uint32_t)ry[v] & low;
+	}
+	const uint32_t g = 1u << (k - 2);	// lanes of a group
+	const unsigned lane = tid & 63u;
+	if (k > 2) {
+		hx = group_sum(hx, g, lane);
+		lx = group_sum(lx, g, lane);
+		hy = group_sum(hy, g, lane);
+		ly = group_sum(ly, g, lane);
+	}
+	if ((lane & (g - 1u)) == g - 1u && i < hi) {
+		ox[i >> k] = (T)(int32_t)(hx + (lx >> k));
+		oy[i >> k] = (T)(int32_t)(hy + (ly >> k));
+	}
+}
+
 // The block's prologue: the fold's rows and the groups' tables into LDS
 // (cordic_xydir.h:97-139).  The caller's barrier follows.
 template <int LJ, int NLIVE>
@@ -430,13 +541,22 @@ __device__ __forceinline__ RotRegs block_ready(const CoreParams &kp, const DirAr
 // and pm are 32-bit words in either, and so is everything in between.  The
 // next pass's samples wait in the container's own vector (two registers per
 // array for Io16), so Io32 is the loop it was.
-template <int LJ, int NLIVE, typename IO>
+//
+// DECIM (deduced from a std::true_type behind the container's tag; the
+// decimating mixer, cordic_fm_mix_decim.hip and cordic_fm_mix_bank_decim.hip):
+// the tuned samples are not stored but summed in groups of 2^log2r and one
+// value per group is (store_decim, above); hi - lo and lo are multiples of
+// 2^log2r, aox / aoy are indexed by sample >> log2r.  Everything in front of
+// the stores is the same text, and without the tag the loop is the code it was.
+template <int LJ, int NLIVE, typename IO, bool DECIM = false>
 __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &da,
 		const RotRegs &rr, const uint32_t (&bk_base)[kDxMaxLevels],
 		const uint32_t *fcw, const uint32_t *pm, const typename IO::ielem *ax,
 		const typename IO::ielem *ay, typename IO::ielem *aox,
 		typename IO::ielem *aoy, const size_t lo, const size_t hi, uint32_t &carry,
-		unsigned &par, uint32_t *ex, const unsigned tid, const unsigned wave, IO)
+		unsigned &par, uint32_t *ex, const unsigned tid, const unsigned wave, IO,
+		std::integral_constant<bool, DECIM> = {},
+		[[maybe_unused]] const uint32_t log2r = 0)
 {
 	typedef typename IO::ivec ivec;
 	typedef typename IO::ielem ielem;
@@ -506,7 +626,9 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 			ty, pb, rx, ry);
 
 		const size_t i = t0 + (size_t)kVec * tid;
-		if (i + kVec <= hi) {
+		if constexpr (DECIM) {
+			store_decim(rx, ry, aox, aoy, i, hi, log2r, tid);
+		} else if (i + kVec <= hi) {
 			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aox + i), IO::narrow(rx));
 			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aoy + i), IO::narrow(ry));
 		} else if (i < hi) {
@@ -586,6 +708,13 @@ bool with_stages(int nlive, int ngroups, F &&f)
 }
 
 } // namespace fmx
+
+// Launch 2 of a decimating single call, for launch_fm_mix
+// (cordic_fm_mix_decim.hip); false: no instance.
+bool	launch_fm_mix_decim_scan(int ww, int nlive, int ngroups, size_t esize, unsigned grid,
+		size_t lds, void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
+		const fmx::FmxArgs &a, uint32_t log2r);
+
 } // namespace cordic_amd
 #endif // __HIPCC__
 #endif

@@ -101,16 +101,6 @@ namespace fmx {
 
 using namespace dev;
 
-struct FmxArgs {
-	const uint32_t *fcw, *pm;	// pm may be NULL
-	uint32_t *acc;			// may be NULL
-	const uint32_t *work;		// fm_reduce's: [0] start, [4 + b] partials
-	const void *x, *y;		// int32 or int16, by the kernel's container
-	void	*ox, *oy;
-	size_t	n, span;		// span: samples per block, whole passes
-	uint32_t xw;			// LDS byte offset of the 12 exchange words
-};
-
 template <int LJ, int NLIVE, typename IO>
 __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da,
 		FmxArgs a)
@@ -199,16 +189,16 @@ bool fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
-		size_t work_bytes)
+		size_t work_bytes, uint32_t log2r)
 {
 	return iq_call_ok(n, d_acc, nullptr, d_fcw, d_pm, d_xval, d_yval, d_oxval, d_oyval,
-		esize, d_work, work_bytes) ? CORDIC_OK : CORDIC_ERR_ARGS;
+		esize, d_work, work_bytes, log2r) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
 		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
-		void *d_oyval, size_t esize, void *d_work, void *stream)
+		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -237,6 +227,9 @@ int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 		span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
+	if (log2r)	// the decimating scan (cordic_fm_mix_decim.hip): n is whole groups
+		return tnco::finish(launch_fm_mix_decim_scan(cfg.ww, cfg.nlive, dx.n, esize, grid,
+			lds, stream, kp, da, a, log2r));
 	const bool done = with_unit(unit_of(cfg.ww, esize), [&](auto lj, auto io) {
 		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
 			hipLaunchKernelGGL((fm_mix_xydir<decltype(lj)::value, decltype(nl)::value,

@@ -46,8 +46,27 @@ static_assert(sizeof(MixSpan) == 88, "the descriptor is read as scalar words");
 constexpr SpanRule kFmxbRule = {1024, 4096, 1u << 20};
 constexpr int	   kFmxbBlocksPerCu = 4;	// = kFmxBlocksPerCu
 
-// The jobs of a create, of either struct (JobView, cordic_span_bank.h)
-typedef JobView<cordic_fmmix_job, cordic_fmmix_job16> MixJobs;
+// The jobs of a create, of either struct (JobView, cordic_span_bank.h), and the
+// bank's k = log2r (0: cordic_mixbank_create; cordic_mixbank_create_decim: the
+// outputs hold n >> k sums of R = 2^k tuned samples), which every job of the
+// view carries to the checks and to span_place.
+struct MixJob : cordic_fmmix_job {
+	uint32_t log2r = 0;
+};
+struct MixJobs : JobView<cordic_fmmix_job, cordic_fmmix_job16> {
+	typedef JobView<cordic_fmmix_job, cordic_fmmix_job16> View;
+	uint32_t log2r = 0;
+	MixJobs(const cordic_fmmix_job *j, uint32_t k = 0) : View(j), log2r(k) {}
+	MixJobs(const cordic_fmmix_job16 *j, uint32_t k = 0) : View(j), log2r(k) {}
+	MixJobs(std::nullptr_t) : View(nullptr) {}
+	MixJob	operator[](size_t k) const
+	{
+		MixJob m;
+		static_cast<cordic_fmmix_job &>(m) = View::operator[](k);
+		m.log2r = log2r;
+		return m;
+	}
+};
 #define F(f) CORDIC_SAME_FIELD(cordic_fmmix_job, cordic_fmmix_job16, f)
 static_assert(sizeof(cordic_fmmix_job) == 72 && F(d_fcw) && F(d_pm) && F(d_xval)
 	&& F(d_yval) && F(d_oxval) && F(d_oyval) && F(d_acc) && F(n) && F(phase0)
@@ -57,38 +76,48 @@ static_assert(sizeof(cordic_fmmix_job) == 72 && F(d_fcw) && F(d_pm) && F(d_xval)
 // The argument checks of cordic_mixbank_create / _create16 that need no device
 // (bank_jobs_valid, cordic_span_bank.h): d_fcw, the four sample arrays
 // required, d_pm and d_acc optional; the outputs are d_oxval, d_oyval and the
-// word at d_acc.
+// word at d_acc.  A decimating bank (jobs.log2r = k > 0): k <= 8, every n a
+// multiple of 2^k, and the two outputs are n >> k elements long.
 inline bool fmxb_jobs_valid(size_t njobs, MixJobs jobs)
 {
+	if (jobs.log2r > 8)
+		return false;
+	for (size_t k = 0; k < njobs; k++)
+		if (jobs.n(k) & (((uint64_t)1 << jobs.log2r) - 1))
+			return false;
 	return bank_jobs_valid(njobs, jobs,
-		[](const cordic_fmmix_job &jb, uint64_t es, const void **word) {
+		[](const MixJob &jb, uint64_t es, const void **word) {
 			*word = jb.d_acc;
 			return std::array<JobArray, 6>{{{jb.d_fcw, 4, true, false},
 				{jb.d_xval, es, true, false}, {jb.d_yval, es, true, false},
-				{jb.d_pm, 4, false, false}, {jb.d_oxval, es, true, true},
-				{jb.d_oyval, es, true, true}}};
+				{jb.d_pm, 4, false, false}, {jb.d_oxval, es, true, true, jb.log2r},
+				{jb.d_oyval, es, true, true, jb.log2r}}};
 		});
 }
 
 // what span_cut (cordic_span_bank.h) leaves to the bank: the sample arrays,
-// `at` bytes in
-inline void span_place(MixSpan *d, const cordic_fmmix_job &jb, uint64_t at)
+// `at` = s0 * esize bytes in.  s0 is whole passes of 1024, a multiple of R = 2^k
+// <= 256, so the outputs of a decimating bank begin (s0 >> k) * esize = at >> k
+// bytes in.
+inline void span_place(MixSpan *d, const MixJob &jb, uint64_t at)
 {
 	d->x = (uintptr_t)jb.d_xval + at;
 	d->y = (uintptr_t)jb.d_yval + at;
-	d->ox = (uintptr_t)jb.d_oxval + at;
-	d->oy = (uintptr_t)jb.d_oyval + at;
+	d->ox = (uintptr_t)jb.d_oxval + (at >> jb.log2r);
+	d->oy = (uintptr_t)jb.d_oyval + (at >> jb.log2r);
 }
 
 // The two launches, for a plan of which fmx_is_fused (cordic_fm_mix.h) is true
 // -- fmx_is_fused16 where the spans were cut from 16-bit jobs (io16).
 // d_start / d_part: the bank's workspace (one word per non-empty job, one per
 // span).  cus: the device's, at create.  An empty table launches nothing.
+// log2r = k in 1 .. 8: the spans were cut for a decimating bank, and launch 2 is
+// fm_mixbank_decim_xydir (cordic_fm_mix_bank_decim.hip).
 // CORDIC_OK or CORDIC_ERR_DEVICE.
 struct DxInfo;		// (cordic_internal.h)
 int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
-		uint32_t *d_part, int cus, bool io16, void *stream);
+		uint32_t *d_part, int cus, bool io16, void *stream, uint32_t log2r = 0);
 
 // what the create of the plan-side banks (plan_bank_create, cordic_abi.cpp)
 // asks of a bank besides its view of the jobs
@@ -99,6 +128,16 @@ struct MixBankTraits {
 	static constexpr const char *max_spans = "CORDIC_FMXB_MAX_SPANS";
 	static constexpr int blocks_per_cu = kFmxbBlocksPerCu;
 };
+
+#ifdef __HIPCC__
+// Launch 2 of a decimating bank, for launch_fmx_bank
+// (cordic_fm_mix_bank_decim.hip); false: no instance.
+namespace dev { struct CoreParams; struct DirArgs; }
+bool	launch_fmx_bank_decim_walk(int ww, int nlive, int ngroups, bool io16, unsigned grid,
+		size_t lds, void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
+		const MixSpan *d_spans, uint32_t nspans, const uint32_t *d_start,
+		const uint32_t *d_part, uint32_t xw, uint32_t log2r);
+#endif
 
 } // namespace cordic_amd
 #endif

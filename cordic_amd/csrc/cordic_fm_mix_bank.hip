@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 
 int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
-		uint32_t *d_part, int cus, bool io16, void *stream)
+		uint32_t *d_part, int cus, bool io16, void *stream, uint32_t log2r)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -156,6 +156,9 @@ int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 	const unsigned grid = g.walk;
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
+	if (log2r)	// a decimating bank's walk (cordic_fm_mix_bank_decim.hip)
+		return tnco::finish(launch_fmx_bank_decim_walk(cfg.ww, cfg.nlive, dx.n, io16, grid,
+			lds, stream, kp, da, d_spans, nspans, d_start, d_part, xw, log2r));
 	const bool done = with_unit(unit_of(cfg.ww, io16 ? 2 : 4), [&](auto lj, auto io) {
 		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
 			hipLaunchKernelGGL((fm_mixbank_xydir<decltype(lj)::value,

@@ -58,11 +58,12 @@ inline bool outputs_overlap(const Range (&out)[NOUT], const Range (&in)[NIN],
 // d_last may be NULL), n <= SIZE_MAX >> 4, the words on the grid of 4, the
 // sample arrays on that of esize, d_work on that of 16, and no output range --
 // the two arrays, the words at d_acc and d_last, the `work_bytes` of d_work --
-// over another output or any input, by the true byte ranges.
+// over another output or any input, by the true byte ranges.  out_shift: the
+// two output arrays hold n >> out_shift elements (the decimating mixer).
 inline bool iq_call_ok(size_t n, const void *d_acc, const void *d_last,
 		const void *d_fcw, const void *d_pm, const void *d_x, const void *d_y,
 		const void *d_o0, const void *d_o1, size_t esize, const void *d_work,
-		size_t work_bytes)
+		size_t work_bytes, unsigned out_shift = 0)
 {
 	if (!d_fcw || !d_x || !d_y || !d_o0 || !d_o1 || !d_work || n > (~(size_t)0 >> 4))
 		return false;
@@ -75,7 +76,8 @@ inline bool iq_call_ok(size_t n, const void *d_acc, const void *d_last,
 	if ((words & 3u) || (samples & (esize - 1))
 			|| (reinterpret_cast<uintptr_t>(d_work) & 15u))
 		return false;
-	const Range out[5] = {range_of(d_o0, n * esize), range_of(d_o1, n * esize),
+	const size_t nout = n >> out_shift;
+	const Range out[5] = {range_of(d_o0, nout * esize), range_of(d_o1, nout * esize),
 		range_of(d_acc, 4), range_of(d_last, 4), range_of(d_work, work_bytes)};
 	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
 		range_of(d_x, n * esize), range_of(d_y, n * esize)};

@@ -69,11 +69,13 @@ template <typename J32, typename J16> struct JobView {
 
 // One array of a job: its address, the bytes a sample takes in it (4 for
 // tuning and phase words, esize for a sample array), whether it has to be
-// there and whether the bank writes it.
+// there and whether the bank writes it.  shift: the array holds n >> shift
+// elements, not n (the outputs of a decimating mixer bank).
 struct JobArray {
 	const void *p;
 	uint64_t bytes;
 	bool	required, is_output;
+	uint32_t shift = 0;
 };
 
 // The argument checks of a bank's create that need no device.  list(jb, es,
@@ -85,7 +87,8 @@ struct JobArray {
 // SIZE_MAX >> 4; no output range (the words among them, so two jobs -- or one
 // job twice -- naming the same word) overlaps another output range or any
 // input range of the bank (BankRanges, cordic_bank_host.h), by the true byte
-// ranges, n * bytes.  A job of no samples is not looked at.
+// ranges, n * bytes ((n >> shift) * bytes for an array that says so).  A job of
+// no samples is not looked at.
 template <typename Jobs, typename List>
 inline bool bank_jobs_valid(size_t njobs, Jobs jobs, List list)
 {
@@ -103,7 +106,7 @@ inline bool bank_jobs_valid(size_t njobs, Jobs jobs, List list)
 			if ((a.required && !a.p) || ((uintptr_t)a.p & (a.bytes - 1)))
 				return false;
 		for (const JobArray &a : arrays)
-			if (a.p && !r.add((uintptr_t)a.p, jb.n * a.bytes, a.is_output))
+			if (a.p && !r.add((uintptr_t)a.p, (jb.n >> a.shift) * a.bytes, a.is_output))
 				return false;
 		for (const void *w : word)
 			if (w && !r.add((uintptr_t)w, 4, true))

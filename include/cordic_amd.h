@@ -1274,6 +1274,89 @@ int	cordic_plan_fm_mix16(const cordic_plan *plan, size_t n,
 		const int16_t *d_xval, const int16_t *d_yval,
 		int16_t *d_oxval, int16_t *d_oyval, void *d_work, void *stream);
 
+/* Decimating FM mixer: integrate-and-dump by R = 2^log2r inside the kernel.
+ *
+ * A digital down-converter: cordic_plan_fm_mix tunes the channel to baseband,
+ * R consecutive tuned samples are summed and one value is kept, so that
+ * everything behind the mixer -- a channel filter, cordic_fm_demod, a
+ * demodulation bank -- runs at 1/R of the rate and the full-rate I/Q is never
+ * stored.  With k = log2r, R = 2^k and
+ *   (tx_i, ty_i) = exactly what cordic_plan_fm_mix(plan, n, d_fcw, d_pm,
+ *                  phase0, d_acc, d_xval, d_yval, ...) writes for sample i
+ * (sign-extended OW-bit values; the same start, p_i and *d_acc before and
+ * after, inputs taken modulo IW and PW), for j in [0, n / R)
+ *   d_oxval[j] = floor((tx_(jR) + tx_(jR+1) + .. + tx_(jR+R-1)) / R)
+ *   d_oyval[j] likewise.
+ * The sum is exact (OW + k bits: 40 for OW 32 and k = 8) and floor is toward
+ * minus infinity, an arithmetic shift right by k; the result is an OW-bit
+ * value.  There is no tolerance: the outputs are a function of the mixer's.
+ * k lies in 0 .. 8.  k = 0 IS cordic_plan_fm_mix: the same bits, the same
+ * launches, the same workspace.  n must be a multiple of R and no partial sum
+ * is carried between calls, so a job cut into consecutive calls at multiples
+ * of R that share a d_acc -- phase0 in the first, 0 in the others -- gives the
+ * bits of one call, and a captured call replayed continues.  Constant tuning
+ * words give the decimated bits of cordic_plan_mix.
+ *
+ * The outputs hold n >> k elements.  The overlap rule of cordic_plan_fm_mix
+ * (no output -- d_oxval, d_oyval, d_acc, d_work -- over an input or another
+ * output, found on the host with nothing written), "nothing outside the output
+ * is written" and the alignment rule (every array on its element's grid,
+ * d_work on the 16-byte grid) apply to those true byte ranges, (n >> k) * 4.
+ *
+ * Status codes: those of cordic_plan_fm_mix in their order -- CORDIC_ERR_ARGS
+ * for a NULL plan, CORDIC_ERR_MODE -- then CORDIC_ERR_ARGS for k > 8 and for n
+ * not a multiple of R (nothing written), then n == 0: CORDIC_OK with nothing
+ * touched, then the pointer, alignment and overlap checks of
+ * cordic_plan_fm_mix.
+ *
+ * Two paths, identical bits, under the launch contract of cordic_plan_fm_mix:
+ *   fused     exactly the plans for which cordic_plan_fm_mix_info answers 1:
+ *             no new query is needed.  Exactly two launches: the mixer's
+ *             reduction of d_fcw, unchanged, then the decimating scan -- the
+ *             mixer's kernel with the sum behind the rotator, in the lane (k =
+ *             1: two outputs per lane, k = 2: one) and across 2^(k-2)
+ *             neighbouring lanes of one wave for k > 2, so that no block waits
+ *             for another and the data crosses no barrier.  Nothing is
+ *             allocated; legal inside a stream capture; any arrays on their
+ *             element's grid; 16 + 8 / R bytes per sample (20 + 8 / R with
+ *             d_pm).
+ *   fallback  every other plan: cordic_plan_fm_mix writes two full-rate
+ *             arrays inside d_work and one small elementwise launch sums them.
+ * cordic_plan_fm_mix_decim_workspace is a pure host function: 0 where the call
+ * would fail (a NULL plan, the wrong mode, k > 8, n not a multiple of R) and
+ * for n == 0, a multiple of 16, non-decreasing in n over the multiples of R;
+ * for a fused plan, and for k = 0, equal to cordic_plan_fm_mix_workspace;
+ * otherwise that plus two arrays of n elements, each part on the 16-byte grid:
+ * at most 12 n + 65536 + 48.
+ *
+ * cordic_plan_fm_mix_decim16: the same on int16 I/Q arrays, under
+ * cordic_plan_fm_mix16's container rule (IW <= 16 and OW <= 16, any PW;
+ * CORDIC_ERR_CONTAINER behind CORDIC_ERR_ARGS for a NULL plan and
+ * CORDIC_ERR_MODE, in front of the checks of k and n).  (tx_i, ty_i) are what
+ * cordic_plan_fm_mix16 writes; sample arrays on the 2-byte grid, output ranges
+ * (n >> k) * 2 bytes.  Fused for the plans for which cordic_plan_fm_mix_info
+ * answers 1 and WW < 35 (cordic_plan_fm_mix16's fused rule): 12 + 4 / R bytes
+ * per sample.  The fallback is cordic_plan_fm_mix16 -- whichever path it takes
+ * -- into two arrays of n shorts inside d_work and the elementwise launch.
+ * cordic_plan_fm_mix_decim16_workspace: as above; for a fused plan, and for k
+ * = 0, equal to cordic_plan_fm_mix16_workspace, otherwise that plus two arrays
+ * of n shorts, at most 24 n + 65536 + 128.
+ */
+size_t	cordic_plan_fm_mix_decim_workspace(const cordic_plan *plan, size_t n,
+		uint32_t log2r);
+int	cordic_plan_fm_mix_decim(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval,
+		int32_t *d_oxval, int32_t *d_oyval, void *d_work, void *stream);
+size_t	cordic_plan_fm_mix_decim16_workspace(const cordic_plan *plan, size_t n,
+		uint32_t log2r);
+int	cordic_plan_fm_mix_decim16(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval,
+		int16_t *d_oxval, int16_t *d_oyval, void *d_work, void *stream);
+
 /* FM mixer banks: many per-sample-tuned mixer jobs in two launches.
  *
  * What FM demodulation banks are to cordic_fm_demod, for cordic_plan_fm_mix:
@@ -1374,6 +1457,30 @@ typedef struct cordic_fmmix_job16 {
 } cordic_fmmix_job16;			/* 72 bytes                             */
 int	cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
 		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank);
+
+/* Decimating FM mixer banks: cordic_mixbank_create_decim and _create_decim16
+ * make the bank of cordic_plan_fm_mix_decim (_decim16) jobs -- a tuned,
+ * decimating LO per channel in front of a channeliser's discriminators.  They
+ * take the job structs above; ONE k = log2r serves the whole bank, and each
+ * job's d_oxval / d_oyval hold n >> k elements.  Each returns an ordinary
+ * cordic_mixbank: _run, _info and _destroy work on it unchanged, run gives per
+ * job the bits (outputs and *d_acc) of the decimating single call, two runs in
+ * a row continue every channel, and _info reports the spans of the
+ * non-decimating bank of the same jobs (spans are whole 1024-sample passes,
+ * hence multiples of R).  Every create rule is cordic_mixbank_create's
+ * (_create16's), word for word, with these differences: k > 8 and a job whose
+ * n is not a multiple of 2^k are CORDIC_ERR_ARGS, behind the plan's status
+ * codes; the overlap check runs over the decimated output ranges, (n >> k)
+ * elements.  Fused where the bank of cordic_mixbank_create is -- exactly two
+ * launches, the second the decimating scan walking the spans -- and otherwise
+ * one by one through the decimating single call, with a workspace sized at
+ * create for the longest job.  k = 0 is cordic_mixbank_create (_create16).
+ * cordic_mixbank_create and _create16 themselves are unchanged.
+ */
+int	cordic_mixbank_create_decim(const cordic_plan *plan, uint32_t log2r,
+		size_t njobs, const cordic_fmmix_job *jobs, cordic_mixbank **bank);
+int	cordic_mixbank_create_decim16(const cordic_plan *plan, uint32_t log2r,
+		size_t njobs, const cordic_fmmix_job16 *jobs, cordic_mixbank **bank);
 
 /* Tuned FM receiver: the FM mixer and FM demodulation in one kernel.
  *

@@ -376,10 +376,33 @@ ABI = {
                                       C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_rx_decim_workspace": (C.c_size_t, [C.c_void_p, _cfgp,
+                                                       C.c_size_t, C.c_uint32]),
+    "cordic_plan_fm_rx_decim16_workspace": (C.c_size_t, [C.c_void_p, _cfgp,
+                                                         C.c_size_t,
+                                                         C.c_uint32]),
+    "cordic_plan_fm_rx_decim": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                          C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "cordic_plan_fm_rx_decim16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                            C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "cordic_rxbank_create": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
                                        C.c_void_p, C.POINTER(C.c_void_p)]),
     "cordic_rxbank_create16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
                                          C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cordic_rxbank_create_decim": (C.c_int, [C.c_void_p, _cfgp, C.c_uint32,
+                                             C.c_size_t, C.c_void_p,
+                                             C.POINTER(C.c_void_p)]),
+    "cordic_rxbank_create_decim16": (C.c_int, [C.c_void_p, _cfgp, C.c_uint32,
+                                               C.c_size_t, C.c_void_p,
+                                               C.POINTER(C.c_void_p)]),
     "cordic_rxbank_destroy": (None, [C.c_void_p]),
     "cordic_rxbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32),
@@ -817,6 +840,59 @@ class Plan:
         self._fm_rx("cordic_plan_fm_rx16", self.fm_rx16_workspace, conv, fcw,
                     x, y, mag, freq, work, pm, n, phase0, acc, dphase0, last,
                     stream)
+
+    def fm_rx_decim_workspace(self, conv, n, log2r):
+        """cordic_plan_fm_rx_decim_workspace: bytes of device scratch an
+        fm_rx_decim call of n samples at R = 2**log2r into the converter
+        `conv` needs (16-byte aligned); 0 where the call would fail"""
+        return int(lib().cordic_plan_fm_rx_decim_workspace(
+            self._h, conv.ref if conv is not None else None, n, log2r))
+
+    def fm_rx_decim16_workspace(self, conv, n, log2r):
+        """cordic_plan_fm_rx_decim16_workspace: the same for fm_rx_decim16"""
+        return int(lib().cordic_plan_fm_rx_decim16_workspace(
+            self._h, conv.ref if conv is not None else None, n, log2r))
+
+    def _fm_rx_decim(self, name, conv, log2r, fcw, x, y, mag, freq, work, pm,
+                     n, phase0, acc, dphase0, last, stream):
+        n = x.numel() if n is None else n
+        if work is None and n:
+            raise TypeError("work: a device buffer of %s_workspace(conv, n, "
+                            "log2r) bytes" % name)
+        need = getattr(self, name + "_workspace")(conv, n, log2r)
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and need and work.numel() * work.element_size() < need:
+            raise ValueError("work: %d bytes, %s_workspace(conv, %d, %d) = %d"
+                             % (work.numel() * work.element_size(), name, n,
+                                log2r, need))
+        cname = "cordic_plan_" + name
+        _check(getattr(lib(), cname)(
+            self._h, conv.ref if conv is not None else None, n, log2r,
+            _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc), _ptr(x),
+            _ptr(y), dphase0 & 0xffffffff, _ptr(last), _ptr(mag), _ptr(freq),
+            _ptr(work), _stream(stream)), cname)
+
+    def fm_rx_decim(self, conv, log2r, fcw, x, y, mag, freq, work=None,
+                    pm=None, n=None, phase0=0, acc=None, dphase0=0, last=None,
+                    stream=None):
+        """cordic_plan_fm_rx_decim: fm_mix_decim by R = 2**log2r and fm_demod
+        (on the r2p / sr2p core `conv`) in one call, neither the tuned nor the
+        decimated I/Q stored: mag and freq hold n >> log2r elements, what
+        fm_demod gives on fm_mix_decim's outputs.  n a multiple of R, log2r in
+        0 .. 8 (0: fm_rx itself).  work: device scratch of
+        fm_rx_decim_workspace(conv, n, log2r) bytes, the caller's."""
+        self._fm_rx_decim("fm_rx_decim", conv, log2r, fcw, x, y, mag, freq,
+                          work, pm, n, phase0, acc, dphase0, last, stream)
+
+    def fm_rx_decim16(self, conv, log2r, fcw, x, y, mag, freq, work=None,
+                      pm=None, n=None, phase0=0, acc=None, dphase0=0,
+                      last=None, stream=None):
+        """cordic_plan_fm_rx_decim16: fm_rx_decim on int16 x, y, mag, freq
+        (both cores within the 16-bit containers); fcw, pm, acc and last stay
+        32-bit words."""
+        _same16("cordic_plan_fm_rx_decim16", x, y, mag, freq)
+        self._fm_rx_decim("fm_rx_decim16", conv, log2r, fcw, x, y, mag, freq,
+                          work, pm, n, phase0, acc, dphase0, last, stream)
 
     @property
     def queue_info(self):
@@ -2252,12 +2328,16 @@ class RxBank(_SpanBank):
     x, y, mag, freq, n, phase0, acc, dphase0, last) or dicts with those keys;
     fcw, x, y, mag, freq are int32 tensors or device addresses, pm one more or
     None, acc and last one-word device tensors or None; n None: fcw.numel().
-    The plan must stay open as long as the bank; conv is copied."""
+    The plan must stay open as long as the bank; conv is copied.
+    log2r = k > 0 (cordic_rxbank_create_decim): a bank of fm_rx_decim jobs --
+    one k for the whole bank, every n a multiple of 2**k, mag and freq of
+    n >> k elements."""
 
     _prefix = "cordic_rxbank"
     _create = "cordic_rxbank_create"
+    _create_decim = "cordic_rxbank_create_decim"
 
-    def __init__(self, plan, conv, jobs):
+    def __init__(self, plan, conv, jobs, log2r=None):
         jobs = [tuple(jb.get(k) for k in _FMRX_KEYS) if isinstance(jb, dict)
                 else tuple(jb) for jb in jobs]
         self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
@@ -2276,9 +2356,15 @@ class RxBank(_SpanBank):
             arr[k].phase0 = (phase0 or 0) & 0xffffffff
             arr[k].dphase0 = (dphase0 or 0) & 0xffffffff
         h = C.c_void_p()
-        _check(getattr(lib(), self._create)(
-            getattr(plan, "_h", plan), conv.ref if conv is not None else None,
-            len(jobs), arr, C.byref(h)), self._create)
+        cref = conv.ref if conv is not None else None
+        if log2r is None:
+            _check(getattr(lib(), self._create)(
+                getattr(plan, "_h", plan), cref, len(jobs), arr, C.byref(h)),
+                self._create)
+        else:
+            _check(getattr(lib(), self._create_decim)(
+                getattr(plan, "_h", plan), cref, log2r, len(jobs), arr,
+                C.byref(h)), self._create_decim)
         self._h = h
 
 
@@ -2289,13 +2375,14 @@ class RxBank16(RxBank):
     are RxBank's."""
 
     _create = "cordic_rxbank_create16"
+    _create_decim = "cordic_rxbank_create_decim16"
 
-    def __init__(self, plan, conv, jobs):
+    def __init__(self, plan, conv, jobs, log2r=None):
         for jb in jobs:
             jb = tuple(jb.get(k) for k in _FMRX_KEYS) if isinstance(jb, dict) \
                 else tuple(jb)
             _same16(self._create, *jb[2:6])
-        RxBank.__init__(self, plan, conv, jobs)
+        RxBank.__init__(self, plan, conv, jobs, log2r)
 
 
 class _CHostStats(C.Structure):

@@ -18,6 +18,7 @@
 #include "cordic_fm_mix.h"
 #include "cordic_fm_mix_bank.h"
 #include "cordic_fm_rx.h"
+#include "cordic_fm_rx_decim.h"
 #include "cordic_fm_rx_bank.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
@@ -378,7 +379,8 @@ struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 // the check of the plan (and converter), `fused` the whole bank's path,
 // `work_bytes` a job's workspace one by one, `finish` what a fused bank still
 // needs behind its span table.  TR (MixBankTraits, RxBankTraits, next to the
-// views): the job check, the span rule, the knobs' names, the blocks per CU.
+// views): the job check, the span rule (of the view: a decimating receiver
+// bank's halo follows its k), the knobs' names, the blocks per CU.
 // The checks come in this order, each bank's documented order of status codes.
 template <typename TR, typename Bank, typename Jobs, typename Ok, typename Fused,
 	typename Work, typename Finish>
@@ -412,10 +414,11 @@ static int plan_bank_create(const cordic_plan *plan, size_t njobs, Jobs jobs, Ba
 	b->io16 = io16;
 	int rc = CORDIC_OK;
 	if (b->fused) {
+		const SpanRule rule = TR::rule_of(jobs);
 		uint64_t passes = 0;
 		for (size_t k = 0; k < njobs; k++)
-			passes += span_units_of(TR::rule, jobs.n(k));
-		rc = span_table_build(&b->spans, TR::passes, TR::max_spans, TR::rule, passes,
+			passes += span_units_of(rule, jobs.n(k));
+		rc = span_table_build(&b->spans, TR::passes, TR::max_spans, rule, passes,
 			b->cus, TR::blocks_per_cu, njobs, jobs, &b->passes);
 	}
 	if (!rc)
@@ -645,29 +648,166 @@ int cordic_plan_fm_rx16(const cordic_plan *plan, const cordic_config *conv, size
 		d_last, d_omag, d_ofreq, d_work, stream, true);
 }
 
+// ---- the decimating receiver: the integrate-and-dump by 2^log2r between that
+// mixer and the discriminator (cordic_fm_rx_decim.h), on either container.
+// Fused where the receiver is.  CORDIC_FMRXD_FALLBACK=1 in the environment
+// (read at every single call and workspace query, as CORDIC_FMXD_FALLBACK is:
+// set it before both) sends a fused pair's single call through the fallback.
+static bool fm_rx_decim_fused(const cordic_plan *plan, const cordic_config *conv,
+		bool io16)
+{
+	const char *e = std::getenv("CORDIC_FMRXD_FALLBACK");
+	if (e && e[0] == '1')
+		return false;
+	return fm_rx_fused(plan, conv, io16);
+}
+
+// the decimating mixer call's own workspace, as its _workspace query answers
+static size_t fm_rx_decim_mix_bytes(const cordic_plan *plan, size_t n, uint32_t log2r,
+		bool io16)
+{
+	return fm_mix_decim_work_bytes(plan, io16, fm_mix_decim_fused(plan, io16), n, log2r);
+}
+
+// a pair that the call accepts; 0 where the call would fail
+static size_t fm_rx_decim_work_bytes(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, uint32_t log2r, bool io16)
+{
+	if (!fmxd_shape_ok(n, log2r))
+		return 0;
+	if (!log2r)
+		return fm_rx_work_bytes(plan, conv, n, io16);
+	return fmrxd_work_bytes(fm_rx_decim_fused(plan, conv, io16),
+		fm_rx_decim_mix_bytes(plan, n, log2r, io16), n, log2r, io16 ? 2 : 4);
+}
+
+static int fm_rx_decim(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const void *d_xval, const void *d_yval, uint32_t dphase0,
+		uint32_t *d_last, void *d_omag, void *d_ofreq, void *d_work, void *stream,
+		bool io16)
+{
+	if (int rc = fm_rx_ok(plan, conv, io16))
+		return rc;
+	if (!fmxd_shape_ok(n, log2r))
+		return CORDIC_ERR_ARGS;
+	if (log2r == 0 || n == 0)	// the receiver itself: its bits, its launches
+		return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
+			d_last, d_omag, d_ofreq, d_work, stream, io16);
+	const size_t es = io16 ? 2 : 4;
+	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_last, d_omag,
+			d_ofreq, es, d_work, fm_rx_decim_work_bytes(plan, conv, n, log2r, io16),
+			log2r))
+		return rc;
+	if (fm_rx_decim_fused(plan, conv, io16))
+		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
+			phase0, d_acc, d_xval, d_yval, dphase0, d_last, d_omag, d_ofreq, es,
+			d_work, stream, log2r);
+	// the fallback: the two calls of the definition -- [the decimating mixer's
+	// workspace | T_x | T_y | the discriminator's workspace]
+	unsigned char *w = static_cast<unsigned char *>(d_work);
+	const size_t m = n >> log2r;
+	const size_t at = fm_rx_decim_mix_bytes(plan, n, log2r, io16);
+	const size_t each = fmrx_array_bytes(m, es);
+	void *tx = w + at, *ty = w + at + each, *dw = w + at + 2 * each;
+	if (io16) {
+		if (int rc = cordic_plan_fm_mix_decim16(plan, n, log2r, d_fcw, d_pm, phase0, d_acc,
+				static_cast<const int16_t *>(d_xval),
+				static_cast<const int16_t *>(d_yval), static_cast<int16_t *>(tx),
+				static_cast<int16_t *>(ty), d_work, stream))
+			return rc;
+		return cordic_fm_demod16(conv, m, static_cast<const int16_t *>(tx),
+			static_cast<const int16_t *>(ty), dphase0, d_last,
+			static_cast<int16_t *>(d_omag), static_cast<int16_t *>(d_ofreq), dw, stream);
+	}
+	if (int rc = cordic_plan_fm_mix_decim(plan, n, log2r, d_fcw, d_pm, phase0, d_acc,
+			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
+			static_cast<int32_t *>(tx), static_cast<int32_t *>(ty), d_work, stream))
+		return rc;
+	return cordic_fm_demod(conv, m, static_cast<const int32_t *>(tx),
+		static_cast<const int32_t *>(ty), dphase0, d_last,
+		static_cast<int32_t *>(d_omag), static_cast<int32_t *>(d_ofreq), dw, stream);
+}
+
+size_t cordic_plan_fm_rx_decim_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r)
+{
+	return fm_rx_ok(plan, conv, false) == CORDIC_OK
+		? fm_rx_decim_work_bytes(plan, conv, n, log2r, false) : 0;
+}
+
+size_t cordic_plan_fm_rx_decim16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r)
+{
+	return fm_rx_ok(plan, conv, true) == CORDIC_OK
+		? fm_rx_decim_work_bytes(plan, conv, n, log2r, true) : 0;
+}
+
+int cordic_plan_fm_rx_decim(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last, int32_t *d_omag, int32_t *d_ofreq,
+		void *d_work, void *stream)
+{
+	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+		dphase0, d_last, d_omag, d_ofreq, d_work, stream, false);
+}
+
+int cordic_plan_fm_rx_decim16(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_xval, const int16_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq,
+		void *d_work, void *stream)
+{
+	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
+		dphase0, d_last, d_omag, d_ofreq, d_work, stream, true);
+}
+
 // ---- receiver banks: many of those jobs in two launches (cordic_fm_rx_bank.h)
 struct cordic_rxbank : BankHandle<cordic_fmrx_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
 	cordic_config conv;			// a copy
 	bool	io16 = false;			// the jobs' sample arrays hold int16
 	uint32_t passes = 0;
+	uint32_t log2r = 0;			// > 0: a decimating bank
 	SpanTable<RxSpan> spans;		// fused
 	uint32_t *d_conv = nullptr;		// fused: conv's kernel parameters
 };
 
-// both creates: `jobs` is either job struct (RxJobs, cordic_fm_rx_bank.h); a
-// fused bank uploads the converter's kernel parameters behind its span table
+// all four creates: `jobs` is either job struct with the bank's k (RxJobs,
+// cordic_fm_rx_bank.h); a fused bank uploads the converter's kernel parameters
+// behind its span table.  A bank that runs one by one keeps the fallback's
+// workspace at its largest, whatever the A/B knobs say at run.
 static int rxbank_create(const cordic_plan *plan, const cordic_config *conv,
 		size_t njobs, RxJobs jobs, cordic_rxbank **bank)
 {
 	return plan_bank_create<RxBankTraits>(plan, njobs, jobs, bank,
 		[&](bool io16) { return fm_rx_ok(plan, conv, io16); },
 		[&](bool io16) { return fm_rx_fused(plan, conv, io16); },
-		[&](bool io16, size_t n) { return fm_rx_work_bytes(plan, conv, n, io16); },
-		cordic_rxbank_destroy, [&](cordic_rxbank *b) {
+		[&](bool io16, size_t n) {
+			if (!jobs.log2r)
+				return fm_rx_work_bytes(plan, conv, n, io16);
+			return fmrxd_work_bytes(false,
+				fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r), n,
+				jobs.log2r, io16 ? 2 : 4);
+		}, cordic_rxbank_destroy, [&](cordic_rxbank *b) {
 			b->conv = *conv;
+			b->log2r = jobs.log2r;
 			return b->fused ? fmrxb_upload_conv(b->conv, &b->d_conv) : CORDIC_OK;
 		});
+}
+
+int cordic_rxbank_create_decim(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job *jobs, cordic_rxbank **bank)
+{
+	return rxbank_create(plan, conv, njobs, RxJobs(jobs, log2r), bank);
+}
+
+int cordic_rxbank_create_decim16(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job16 *jobs,
+		cordic_rxbank **bank)
+{
+	return rxbank_create(plan, conv, njobs, RxJobs(jobs, log2r), bank);
 }
 
 int cordic_rxbank_create(const cordic_plan *plan, const cordic_config *conv,
@@ -713,11 +853,12 @@ int cordic_rxbank_run(const cordic_rxbank *bank, void *stream)
 		const SpanTable<RxSpan> &t = bank->spans;
 		return launch_fmrx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_conv,
 			t.d_spans, t.nspans, t.start(), t.part(), t.more(), bank->cus, bank->io16,
-			stream);
+			stream, bank->log2r);
 	}, [&](const cordic_fmrx_job &jb) {
-		return fm_rx(plan, &bank->conv, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
-			jb.d_acc, jb.d_xval, jb.d_yval, jb.dphase0, jb.d_last, jb.d_omag,
-			jb.d_ofreq, bank->d_work, stream, bank->io16);
+		// (log2r 0: the receiver's own call, cordic_plan_fm_rx or _rx16)
+		return fm_rx_decim(plan, &bank->conv, (size_t)jb.n, bank->log2r, jb.d_fcw,
+			jb.d_pm, jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.dphase0, jb.d_last,
+			jb.d_omag, jb.d_ofreq, bank->d_work, stream, bank->io16);
 	});
 }
 

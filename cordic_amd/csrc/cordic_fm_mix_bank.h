@@ -123,7 +123,7 @@ int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 // asks of a bank besides its view of the jobs
 struct MixBankTraits {
 	static bool jobs_valid(size_t njobs, MixJobs jobs) { return fmxb_jobs_valid(njobs, jobs); }
-	static constexpr const SpanRule &rule = kFmxbRule;
+	static SpanRule rule_of(const MixJobs &) { return kFmxbRule; }
 	static constexpr const char *passes = "CORDIC_FMXB_PASSES";
 	static constexpr const char *max_spans = "CORDIC_FMXB_MAX_SPANS";
 	static constexpr int blocks_per_cu = kFmxbBlocksPerCu;

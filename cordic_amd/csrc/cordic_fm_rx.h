@@ -69,21 +69,24 @@ bool	fmrx_conv_is_fused(const cordic_config &conv);
 // Alignment -- the four sample arrays on the grid of `esize`, the words on that
 // of 4, d_work on that of 16 -- and no output range (the words at d_acc and
 // d_last and the `work_bytes` of d_work included) over anything else, by the
-// true byte ranges; nothing is launched.  n > 0.
+// true byte ranges; nothing is launched.  n > 0.  log2r: the two outputs hold
+// n >> log2r elements (the decimating receiver).
 int	fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes);
+		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r = 0);
 
 // The fused path: two launches on `stream` (fm_rx_reduce, then fm_rx_xydir),
 // nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
 // The caller has checked fmx_is_fused / fmx_is_fused16, fmrx_conv_is_fused and
 // fmrx_check_call.
+// log2r = k in 1 .. 8: launch 2 is fm_rx_decim_xydir (cordic_fm_rx_decim.hip),
+// which writes n >> k samples; n is a multiple of 2^k.
 int	launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream);
+		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r = 0);
 
 } // namespace cordic_amd
 

@@ -81,6 +81,7 @@
 #include "cordic_table_nco.h"
 #include "cordic_hostargs.h"
 #include "cordic_fm_rx.h"
+#include "cordic_fm_rx_decim.h"
 
 #ifndef CORDIC_FMRX_UNIT
 #define CORDIC_FMRX_UNIT 30	// 30: <30, Io32> and the host side; 29; 16
@@ -221,17 +222,17 @@ bool fmrx_conv_is_fused(const cordic_config &conv)
 int fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes)
+		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r)
 {
 	return iq_call_ok(n, d_acc, d_last, d_fcw, d_pm, d_xval, d_yval, d_omag, d_ofreq,
-		esize, d_work, work_bytes) ? CORDIC_OK : CORDIC_ERR_ARGS;
+		esize, d_work, work_bytes, log2r) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream)
+		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r)
 {
 	using namespace fmrx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -243,17 +244,20 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 		(void)hipGetLastError();
 		return CORDIC_ERR_DEVICE;
 	}
+	// (log2r > 0: the decimating receiver's LDS, halo and knob)
 	uint32_t xw = 0;
-	const size_t lds = lds_bytes(dx, &xw);
+	const size_t lds = log2r ? fmrxd::lds_bytes(dx, &xw) : lds_bytes(dx, &xw);
 	size_t cap = (size_t)cus * blocks_per_cu(lds);
 	if (cap > kFmrxMaxBlocks)
 		cap = kFmrxMaxBlocks;
-	cap = env_block_cap("CORDIC_FMRX_MAX_BLOCKS", cap);
-	const CallSpan cs = call_span(n, cap, kFmrxPass, kFmrxHalo);
+	cap = env_block_cap(log2r ? "CORDIC_FMRXD_MAX_BLOCKS" : "CORDIC_FMRX_MAX_BLOCKS", cap);
+	const CallSpan cs = call_span(n, cap, kFmrxPass, log2r ? fmrxd_halo(log2r) : kFmrxHalo);
 	const size_t span = cs.span;
 	const unsigned grid = (unsigned)cs.grid;
 	// the instance first: nothing is enqueued for a core without one
 	static RxLaunch *const units[3] = {launch_rx_lj30, launch_rx_lj29, launch_rx_io16};
+	static fmrxd::RxdLaunch *const dunits[3] = {fmrxd::launch_rxd_lj30,
+		fmrxd::launch_rxd_lj29, fmrxd::launch_rxd_io16};
 	const fmx::Unit u = fmx::unit_of(cfg.ww, esize);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
@@ -269,7 +273,8 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 		n, span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = units[u](cfg.nlive, grid, lds, st, kp, da, a);
+	const bool done = log2r ? dunits[u](cfg.nlive, grid, lds, st, kp, da, a, log2r)
+		: units[u](cfg.nlive, grid, lds, st, kp, da, a);
 	return tnco::finish(done);
 }
 #endif

@@ -54,8 +54,35 @@ static_assert(sizeof(RxSpan) == 104, "the descriptor is read as scalar words");
 constexpr SpanRule kFmrxbRule = {1024, 4096, 1u << 20, 4, 1};
 constexpr int	   kFmrxbBlocksPerCu = 3;	// by its registers (cordic_fm_rx_bank.hip)
 
-// The jobs of a create, of either struct (JobView, cordic_span_bank.h)
-typedef JobView<cordic_fmrx_job, cordic_fmrx_job16> RxJobs;
+// A decimating bank (cordic_rxbank_create_decim, k = log2r in 1 .. 8): the halo
+// is the R = 2^k input samples of the decimated sample in front, max(4, R) --
+// a multiple of R, so every span begins and ends on a multiple of R.  k = 0:
+// kFmrxbRule.
+constexpr SpanRule fmrxb_rule(uint32_t log2r)
+{
+	return SpanRule{1024, 4096, 1u << 20, log2r > 2 ? 1u << log2r : 4u, 1};
+}
+
+// The jobs of a create, of either struct (JobView, cordic_span_bank.h), and the
+// bank's k = log2r (0: cordic_rxbank_create), which every job of the view
+// carries to the checks and to span_place (as MixJobs, cordic_fm_mix_bank.h).
+struct RxJob : cordic_fmrx_job {
+	uint32_t log2r = 0;
+};
+struct RxJobs : JobView<cordic_fmrx_job, cordic_fmrx_job16> {
+	typedef JobView<cordic_fmrx_job, cordic_fmrx_job16> View;
+	uint32_t log2r = 0;
+	RxJobs(const cordic_fmrx_job *j, uint32_t k = 0) : View(j), log2r(k) {}
+	RxJobs(const cordic_fmrx_job16 *j, uint32_t k = 0) : View(j), log2r(k) {}
+	RxJobs(std::nullptr_t) : View(nullptr) {}
+	RxJob	operator[](size_t k) const
+	{
+		RxJob m;
+		static_cast<cordic_fmrx_job &>(m) = View::operator[](k);
+		m.log2r = log2r;
+		return m;
+	}
+};
 #define F(f) CORDIC_SAME_FIELD(cordic_fmrx_job, cordic_fmrx_job16, f)
 static_assert(sizeof(cordic_fmrx_job) == 88 && F(d_fcw) && F(d_pm) && F(d_xval)
 	&& F(d_yval) && F(d_omag) && F(d_ofreq) && F(d_acc) && F(d_last) && F(n)
@@ -66,28 +93,36 @@ static_assert(sizeof(cordic_fmrx_job) == 88 && F(d_fcw) && F(d_pm) && F(d_xval)
 // The argument checks of cordic_rxbank_create / _create16 that need no device
 // (bank_jobs_valid, cordic_span_bank.h): d_fcw and the four sample arrays
 // required, d_pm, d_acc and d_last optional; the outputs are d_omag, d_ofreq
-// and the words at d_acc and d_last.
+// and the words at d_acc and d_last.  A decimating bank (jobs.log2r = k > 0): k
+// <= 8, every n a multiple of 2^k, and the two outputs are n >> k elements long.
 inline bool fmrxb_jobs_valid(size_t njobs, RxJobs jobs)
 {
+	if (jobs.log2r > 8)
+		return false;
+	for (size_t k = 0; k < njobs; k++)
+		if (jobs.n(k) & (((uint64_t)1 << jobs.log2r) - 1))
+			return false;
 	return bank_jobs_valid(njobs, jobs,
-		[](const cordic_fmrx_job &jb, uint64_t es, const void **word) {
+		[](const RxJob &jb, uint64_t es, const void **word) {
 			word[0] = jb.d_acc;
 			word[1] = jb.d_last;
 			return std::array<JobArray, 6>{{{jb.d_fcw, 4, true, false},
 				{jb.d_xval, es, true, false}, {jb.d_yval, es, true, false},
-				{jb.d_pm, 4, false, false}, {jb.d_omag, es, true, true},
-				{jb.d_ofreq, es, true, true}}};
+				{jb.d_pm, 4, false, false}, {jb.d_omag, es, true, true, jb.log2r},
+				{jb.d_ofreq, es, true, true, jb.log2r}}};
 		});
 }
 
 // what span_cut (cordic_span_bank.h) leaves to the bank: the sample arrays,
-// `at` bytes in, and the discriminator's word
-inline void span_place(RxSpan *d, const cordic_fmrx_job &jb, uint64_t at)
+// `at` = s0 * esize bytes in, and the discriminator's word.  s0 is a multiple
+// of R = 2^k (fmrxb_rule), so the outputs of a decimating bank begin (s0 >> k) *
+// esize = at >> k bytes in.
+inline void span_place(RxSpan *d, const RxJob &jb, uint64_t at)
 {
 	d->x = (uintptr_t)jb.d_xval + at;
 	d->y = (uintptr_t)jb.d_yval + at;
-	d->mag = (uintptr_t)jb.d_omag + at;
-	d->freq = (uintptr_t)jb.d_ofreq + at;
+	d->mag = (uintptr_t)jb.d_omag + (at >> jb.log2r);
+	d->freq = (uintptr_t)jb.d_ofreq + (at >> jb.log2r);
 	d->last = (uintptr_t)jb.d_last;
 	d->dphase0 = jb.dphase0;
 }
@@ -101,21 +136,38 @@ int	fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv);
 // fused (cordic_fm_rx.h) -- the 16-bit rule where the spans were cut from
 // 16-bit jobs (io16).  d_start / d_part / d_prev: the bank's workspace (one word
 // per non-empty job, one per span, one per non-empty job).  cus: the device's,
-// at create.  An empty table launches nothing.  CORDIC_OK or CORDIC_ERR_DEVICE.
+// at create.  An empty table launches nothing.  log2r = k in 1 .. 8: the spans
+// were cut for a decimating bank (fmrxb_rule(k)), and launch 2 is
+// fm_rxbank_decim_xydir (cordic_fm_rx_bank_decim.hip).  CORDIC_OK or
+// CORDIC_ERR_DEVICE.
 struct DxInfo;		// (cordic_internal.h)
 int	launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
 		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream);
+		void *stream, uint32_t log2r = 0);
 
-// (as MixBankTraits, cordic_fm_mix_bank.h)
+// (as MixBankTraits, cordic_fm_mix_bank.h; the rule depends on the bank's k)
 struct RxBankTraits {
 	static bool jobs_valid(size_t njobs, RxJobs jobs) { return fmrxb_jobs_valid(njobs, jobs); }
-	static constexpr const SpanRule &rule = kFmrxbRule;
+	static SpanRule rule_of(const RxJobs &jobs) { return fmrxb_rule(jobs.log2r); }
 	static constexpr const char *passes = "CORDIC_FMRXB_PASSES";
 	static constexpr const char *max_spans = "CORDIC_FMRXB_MAX_SPANS";
 	static constexpr int blocks_per_cu = kFmrxbBlocksPerCu;
 };
+
+#ifdef __HIPCC__
+// Launch 2 of a decimating bank, for launch_fmrx_bank
+// (cordic_fm_rx_bank_decim.hip, compiled once per <LJ, container>); false: no
+// instance.
+namespace dev { struct CoreParams; struct DirArgs; }
+namespace fmrxd {
+typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, void *stream,
+		const dev::CoreParams &kp, const dev::DirArgs &da, const RxSpan *spans,
+		uint32_t nspans, const uint32_t *start, const uint32_t *part,
+		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw, uint32_t log2r);
+BankLaunch launch_rxbank_decim_lj30, launch_rxbank_decim_lj29, launch_rxbank_decim_io16;
+}
+#endif
 
 } // namespace cordic_amd
 #endif

@@ -54,6 +54,7 @@
 #include "cordic_hostargs.h"
 #include "cordic_devmem.h"
 #include "cordic_fm_rx.h"
+#include "cordic_fm_rx_decim.h"
 #include "cordic_fm_rx_bank.h"
 #include "cordic_span_reduce.h"
 
@@ -169,15 +170,16 @@ int fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv)
 int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
 		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream)
+		void *stream, uint32_t log2r)
 {
 	using namespace fmrx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
 	if (nspans == 0)
 		return CORDIC_OK;
 	hipStream_t st = static_cast<hipStream_t>(stream);
+	// (log2r > 0: the decimating receiver's LDS, with the ring)
 	uint32_t xw = 0;
-	const size_t lds = lds_bytes(dx, &xw);
+	const size_t lds = log2r ? fmrxd::lds_bytes(dx, &xw) : lds_bytes(dx, &xw);
 	size_t per_cu = blocks_per_cu(lds);
 	if (per_cu > (size_t)kFmrxbBlocksPerCu)
 		per_cu = kFmrxbBlocksPerCu;
@@ -186,6 +188,8 @@ int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 	// the instance first: nothing is enqueued for a core without one
 	static BankLaunch *const units[3] = {launch_rxbank_lj30, launch_rxbank_lj29,
 		launch_rxbank_io16};
+	static fmrxd::BankLaunch *const dunits[3] = {fmrxd::launch_rxbank_decim_lj30,
+		fmrxd::launch_rxbank_decim_lj29, fmrxd::launch_rxbank_decim_io16};
 	const fmx::Unit u = fmx::unit_of(cfg.ww, io16 ? 2 : 4);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
@@ -193,6 +197,9 @@ int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 		d_spans, nspans, d_start, d_part);
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
+	if (log2r)
+		return tnco::finish(dunits[u](cfg.nlive, g.walk, lds, stream, kp, da, d_spans,
+			nspans, d_start, d_part, d_prev, d_conv, xw, log2r));
 	return tnco::finish(units[u](cfg.nlive, g.walk, lds, st, kp, da, d_spans, nspans,
 		d_start, d_part, d_prev, d_conv, xw));
 }

@@ -1579,6 +1579,69 @@ int	cordic_plan_fm_rx16(const cordic_plan *plan, const cordic_config *conv,
 		uint32_t dphase0, uint32_t *d_last,
 		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream);
 
+/* Decimating FM receiver: tune, sum by R = 2^k and discriminate in one kernel.
+ *
+ * With k = log2r in 0 .. 8 and R = 2^k, cordic_plan_fm_rx_decim gives, bit for
+ * bit, the outputs and both words of
+ *   cordic_plan_fm_mix_decim(plan, n, k, d_fcw, d_pm, phase0, d_acc, d_xval,
+ *                            d_yval, T_x, T_y, ..)
+ *   cordic_fm_demod(conv, n >> k, T_x, T_y, dphase0, d_last, d_omag, d_ofreq, ..)
+ * run in sequence, without T_x and T_y: d_omag and d_ofreq hold n >> k elements;
+ * afterwards *d_acc = start + all n tuning words and *d_last = the converter's
+ * phase of the last decimated sample; prev = (dphase0 + *d_last) mod 2^PW(conv).
+ * The converter takes the decimated OW-bit values modulo its IW, as in
+ * cordic_plan_fm_rx.  n must be a multiple of R: no partial sum is carried
+ * between calls.  A job cut at multiples of R into consecutive calls that share
+ * d_acc and d_last gives the bits of one call; a captured call replayed
+ * continues.  k = 0 IS cordic_plan_fm_rx: the same bits, launches and workspace.
+ * cordic_plan_fm_rx_decim16: the same on int16 I/Q, magnitude and frequency,
+ * under cordic_plan_fm_rx16's container rule.
+ *
+ * Status codes, in this order: those of cordic_plan_fm_rx (_rx16) through the
+ * container check; CORDIC_ERR_ARGS for k > 8 or n % R != 0, nothing written;
+ * n == 0: CORDIC_OK, nothing touched; then CORDIC_ERR_ARGS for a NULL d_fcw,
+ * d_xval, d_yval, d_omag, d_ofreq or d_work, a pointer off its grid, or an
+ * overlap, judged with output ranges of n >> k elements.
+ *
+ * Two paths, identical bits:
+ *   fused     exactly where cordic_plan_fm_rx_info (_rx16_info) answers 1.  TWO
+ *             launches on `stream`: cordic_plan_fm_rx's reduction, then the
+ *             scan with the rotator, the sums, and the converter run on 1024
+ *             decimated samples at a time from a ring in LDS -- its cost per
+ *             input sample is 1/R of the receiver's and its stores are whole
+ *             vectors.  Legal inside a stream capture, as cordic_plan_fm_rx.
+ *   fallback  every other pair: the two calls above through d_work.
+ *             CORDIC_FMRXD_FALLBACK=1 in the environment (read at every call
+ *             and workspace query; an A/B knob) forces it.
+ * CORDIC_FMRXD_MAX_BLOCKS=<n> caps the fused grid; the bits do not depend on it.
+ *
+ * d_work: at least cordic_plan_fm_rx_decim_workspace(plan, conv, n, log2r)
+ * bytes (_decim16_workspace for the *16 form).  Pure host functions: 0 where
+ * the call would fail and for n == 0, a multiple of 16, non-decreasing in n
+ * over the multiples of R.  Fused, or k = 0: cordic_plan_fm_rx_workspace
+ * (_rx16_workspace).  Otherwise [the decimating mixer call's workspace | T_x |
+ * T_y of n >> k elements | cordic_fm_demod_workspace(n >> k)], each part on
+ * the 16-byte grid: at most cordic_plan_fm_mix_decim_workspace(plan, n, k) +
+ * 9 (n >> k) + 96 bytes (_decim16: cordic_plan_fm_mix_decim16_workspace(plan,
+ * n, k) + 5 (n >> k) + 96).
+ */
+size_t	cordic_plan_fm_rx_decim_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r);
+size_t	cordic_plan_fm_rx_decim16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r);
+int	cordic_plan_fm_rx_decim(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc,
+		const int32_t *d_xval, const int32_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last,
+		int32_t *d_omag, int32_t *d_ofreq, void *d_work, void *stream);
+int	cordic_plan_fm_rx_decim16(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc,
+		const int16_t *d_xval, const int16_t *d_yval,
+		uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream);
+
 /* Receiver banks: many tuned-receiver jobs in two launches.
  *
  * What FM mixer banks are to cordic_plan_fm_mix, for cordic_plan_fm_rx: the
@@ -1668,6 +1731,28 @@ int	cordic_rxbank_run(const cordic_rxbank *bank, void *stream);
 int	cordic_rxbank_info(const cordic_rxbank *bank, uint64_t *samples,
 		uint32_t *spans, int32_t *fused, int32_t *tile);
 void	cordic_rxbank_destroy(cordic_rxbank *bank);
+
+/* Decimating receiver banks: cordic_rxbank_create_decim(plan, conv, k, ..)
+ * makes the bank of cordic_plan_fm_rx_decim (_decim16) jobs at R = 2^k -- tune,
+ * sum by R and discriminate a whole channeliser in two launches a round.  The
+ * jobs are the structs above; a job's d_omag and d_ofreq hold n >> k elements.
+ * The result is an ordinary cordic_rxbank: _run, _info and _destroy serve it
+ * unchanged.  k = 0 is cordic_rxbank_create.  Every rule of cordic_rxbank_create
+ * holds, in its order; behind the checks of the plan and the converter,
+ * CORDIC_ERR_ARGS for k > 8 or a job with n % R != 0; the overlap and length
+ * checks take the outputs' true byte ranges, (n >> k) elements.  Fused exactly
+ * where cordic_rxbank_create is: every job is cut into spans of P passes of
+ * 1024 input samples LESS max(4, R), the input samples of the decimated sample
+ * in front, which are tuned and summed again and not stored; launch 2 is the
+ * decimating receiver's kernel walking the spans.  Everything else loops the
+ * single call.  Banks ignore CORDIC_FMRXD_FALLBACK.
+ */
+int	cordic_rxbank_create_decim(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job *jobs,
+		cordic_rxbank **bank);
+int	cordic_rxbank_create_decim16(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job16 *jobs,
+		cordic_rxbank **bank);
 
 /* ------------------------------------------- clocked view (streaming shim)
  *

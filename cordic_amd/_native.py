@@ -403,6 +403,31 @@ ABI = {
     "cordic_rxbank_create_decim16": (C.c_int, [C.c_void_p, _cfgp, C.c_uint32,
                                                C.c_size_t, C.c_void_p,
                                                C.POINTER(C.c_void_p)]),
+    "cordic_plan_fm_rx_c16_workspace": (C.c_size_t, [C.c_void_p, _cfgp,
+                                                     C.c_size_t]),
+    "cordic_plan_fm_rx_c16_info": (C.c_int, [C.c_void_p, _cfgp,
+                                             C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
+    "cordic_plan_fm_rx_c16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                        C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "cordic_plan_fm_rx_decim_c16_workspace": (C.c_size_t, [C.c_void_p, _cfgp,
+                                                           C.c_size_t,
+                                                           C.c_uint32]),
+    "cordic_plan_fm_rx_decim_c16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                              C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p,
+                                              C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "cordic_rxbank_create_c16": (C.c_int, [C.c_void_p, _cfgp, C.c_size_t,
+                                           C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cordic_rxbank_create_decim_c16": (C.c_int, [C.c_void_p, _cfgp, C.c_uint32,
+                                                 C.c_size_t, C.c_void_p,
+                                                 C.POINTER(C.c_void_p)]),
     "cordic_rxbank_destroy": (None, [C.c_void_p]),
     "cordic_rxbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32),
@@ -893,6 +918,66 @@ class Plan:
         _same16("cordic_plan_fm_rx_decim16", x, y, mag, freq)
         self._fm_rx_decim("fm_rx_decim16", conv, log2r, fcw, x, y, mag, freq,
                           work, pm, n, phase0, acc, dphase0, last, stream)
+
+    def fm_rx_c16_workspace(self, conv, n):
+        """cordic_plan_fm_rx_c16_workspace: bytes of device scratch an
+        fm_rx_c16 call of n complex samples needs"""
+        return int(lib().cordic_plan_fm_rx_c16_workspace(
+            self._h, conv.ref if conv is not None else None, n))
+
+    def fm_rx_c16_info(self, conv):
+        """cordic_plan_fm_rx_c16_info: (fused, tile), fm_rx16_info's answer"""
+        return self._fm_rx_info("cordic_plan_fm_rx_c16_info", conv)
+
+    def fm_rx_decim_c16_workspace(self, conv, n, log2r):
+        """cordic_plan_fm_rx_decim_c16_workspace: the same for
+        fm_rx_decim_c16 at R = 2**log2r; 0 where the call would fail"""
+        return int(lib().cordic_plan_fm_rx_decim_c16_workspace(
+            self._h, conv.ref if conv is not None else None, n, log2r))
+
+    def _fm_rx_c16(self, cname, need, args, conv, fcw, iq, mag, freq, work,
+                   pm, n, phase0, acc, dphase0, last, stream):
+        _same16(cname, iq, mag, freq)
+        n = iq.numel() // 2 if n is None else n
+        if hasattr(iq, "numel") and iq.numel() < 2 * n:
+            raise ValueError("%s: iq holds %d shorts, 2 n = %d"
+                             % (cname, iq.numel(), 2 * n))
+        if work is None and n:
+            raise TypeError("%s: work, a device buffer of the _workspace "
+                            "query's bytes" % cname)
+        if hasattr(work, "numel") and hasattr(work, "element_size") \
+                and need(n) and work.numel() * work.element_size() < need(n):
+            raise ValueError("%s: work has %d bytes, %d needed"
+                             % (cname, work.numel() * work.element_size(),
+                                need(n)))
+        _check(getattr(lib(), cname)(
+            self._h, conv.ref if conv is not None else None, n, *args,
+            _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc), _ptr(iq),
+            dphase0 & 0xffffffff, _ptr(last), _ptr(mag), _ptr(freq),
+            _ptr(work), _stream(stream)), cname)
+
+    def fm_rx_c16(self, conv, fcw, iq, mag, freq, work=None, pm=None, n=None,
+                  phase0=0, acc=None, dphase0=0, last=None, stream=None):
+        """cordic_plan_fm_rx_c16: fm_rx16 on INTERLEAVED int16 I/Q -- iq is
+        one int16 tensor of 2 n elements, I0 Q0 I1 Q1 .., as a capture
+        delivers it; mag and freq are int16 tensors of n elements.  The bits
+        of fm_rx16 on iq[0::2], iq[1::2].  n None: iq.numel() // 2.  work:
+        fm_rx_c16_workspace(conv, n) bytes."""
+        self._fm_rx_c16("cordic_plan_fm_rx_c16",
+                        lambda k: self.fm_rx_c16_workspace(conv, k), (), conv,
+                        fcw, iq, mag, freq, work, pm, n, phase0, acc, dphase0,
+                        last, stream)
+
+    def fm_rx_decim_c16(self, conv, log2r, fcw, iq, mag, freq, work=None,
+                        pm=None, n=None, phase0=0, acc=None, dphase0=0,
+                        last=None, stream=None):
+        """cordic_plan_fm_rx_decim_c16: fm_rx_decim16 on interleaved int16
+        I/Q (iq: 2 n shorts); mag and freq hold n >> log2r shorts.  work:
+        fm_rx_decim_c16_workspace(conv, n, log2r) bytes."""
+        self._fm_rx_c16("cordic_plan_fm_rx_decim_c16",
+                        lambda k: self.fm_rx_decim_c16_workspace(conv, k, log2r),
+                        (log2r,), conv, fcw, iq, mag, freq, work, pm, n,
+                        phase0, acc, dphase0, last, stream)
 
     @property
     def queue_info(self):
@@ -2383,6 +2468,64 @@ class RxBank16(RxBank):
                 else tuple(jb)
             _same16(self._create, *jb[2:6])
         RxBank.__init__(self, plan, conv, jobs, log2r)
+
+
+class _CFmRxJobC16(C.Structure):
+    """cordic_fmrx_job_c16"""
+    _fields_ = [("d_fcw", C.c_void_p), ("d_pm", C.c_void_p),
+                ("d_iq", C.c_void_p),
+                ("d_omag", C.c_void_p), ("d_ofreq", C.c_void_p),
+                ("d_acc", C.c_void_p), ("d_last", C.c_void_p),
+                ("n", C.c_uint64), ("phase0", C.c_uint32),
+                ("dphase0", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+_FMRX_C16_KEYS = ("fcw", "pm", "iq", "mag", "freq", "n", "phase0", "acc",
+                  "dphase0", "last")
+
+
+class RxBankC16(_SpanBank):
+    """cordic_rxbank_create_c16: an RxBank of fm_rx_c16 jobs on INTERLEAVED
+    int16 I/Q.  jobs: tuples (fcw, pm, iq, mag, freq, n, phase0, acc, dphase0,
+    last) or dicts with those keys; iq is an int16 tensor (or device address)
+    of 2 n shorts, I0 Q0 I1 Q1 .., mag and freq int16 tensors; fcw, pm, acc and
+    last stay 32-bit; n None: fcw.numel().  log2r = k > 0
+    (cordic_rxbank_create_decim_c16): a bank of fm_rx_decim_c16 jobs.  info,
+    run and close are RxBank's: the handle is an ordinary cordic_rxbank."""
+
+    _prefix = "cordic_rxbank"
+    _create = "cordic_rxbank_create_c16"
+    _create_decim = "cordic_rxbank_create_decim_c16"
+
+    def __init__(self, plan, conv, jobs, log2r=None):
+        jobs = [tuple(jb.get(k) for k in _FMRX_C16_KEYS) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
+        arr = (_CFmRxJobC16 * max(1, len(jobs)))()
+        for k, (fcw, pm, iq, mag, freq, n, phase0, acc, dphase0, last) \
+                in enumerate(jobs):
+            _same16(self._create, iq, mag, freq)
+            arr[k].d_fcw = _ptr(fcw)
+            arr[k].d_pm = _ptr(pm)
+            arr[k].d_iq = _ptr(iq)
+            arr[k].d_omag = _ptr(mag)
+            arr[k].d_ofreq = _ptr(freq)
+            arr[k].d_acc = _ptr(acc)
+            arr[k].d_last = _ptr(last)
+            arr[k].n = fcw.numel() if n is None else n
+            arr[k].phase0 = (phase0 or 0) & 0xffffffff
+            arr[k].dphase0 = (dphase0 or 0) & 0xffffffff
+        h = C.c_void_p()
+        cref = conv.ref if conv is not None else None
+        if log2r is None:
+            _check(getattr(lib(), self._create)(
+                getattr(plan, "_h", plan), cref, len(jobs), arr, C.byref(h)),
+                self._create)
+        else:
+            _check(getattr(lib(), self._create_decim)(
+                getattr(plan, "_h", plan), cref, log2r, len(jobs), arr,
+                C.byref(h)), self._create_decim)
+        self._h = h
 
 
 class _CHostStats(C.Structure):

@@ -763,18 +763,115 @@ int cordic_plan_fm_rx_decim16(const cordic_plan *plan, const cordic_config *conv
 		dphase0, d_last, d_omag, d_ofreq, d_work, stream, true);
 }
 
+// ---- the receivers on INTERLEAVED int16 I/Q (the *_c16 forms): the *16 twins
+// with d_iq in the place of d_xval / d_yval.  Fused where the twin is, with the
+// twin's launches and workspace (the <30, IoC16> instances of launch 2);
+// otherwise one split launch into two arrays behind the twin's workspace, then
+// the twin itself.
+static size_t fm_rx_c16_work_bytes(const cordic_plan *plan, const cordic_config *conv,
+		size_t n)
+{
+	return fmrx_c16_work_bytes(fm_rx_fused(plan, conv, true),
+		fm_rx_work_bytes(plan, conv, n, true), n);
+}
+
+static size_t fm_rx_decim_c16_work_bytes(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r)
+{
+	if (!fmxd_shape_ok(n, log2r))
+		return 0;
+	if (!log2r)
+		return fm_rx_c16_work_bytes(plan, conv, n);
+	return fmrx_c16_work_bytes(fm_rx_decim_fused(plan, conv, true),
+		fm_rx_decim_work_bytes(plan, conv, n, log2r, true), n);
+}
+
+// both single calls (log2r 0: the plain form, which CORDIC_FMRXD_FALLBACK does
+// not reach)
+static int fm_rx_decim_c16(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
+{
+	if (int rc = fm_rx_ok(plan, conv, true))
+		return rc;
+	if (!fmxd_shape_ok(n, log2r))
+		return CORDIC_ERR_ARGS;
+	if (n == 0)
+		return CORDIC_OK;
+	const bool fused = log2r ? fm_rx_decim_fused(plan, conv, true)
+		: fm_rx_fused(plan, conv, true);
+	const size_t twin = log2r ? fm_rx_decim_work_bytes(plan, conv, n, log2r, true)
+		: fm_rx_work_bytes(plan, conv, n, true);
+	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_iq, nullptr, d_last, d_omag,
+			d_ofreq, 2, d_work, fmrx_c16_work_bytes(fused, twin, n), log2r, true))
+		return rc;
+	if (fused)
+		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
+			phase0, d_acc, d_iq, nullptr, dphase0, d_last, d_omag, d_ofreq, 2, d_work,
+			stream, log2r, true);
+	// the fallback: [the twin's workspace | x | y], then the twin from them
+	unsigned char *w = static_cast<unsigned char *>(d_work);
+	const size_t at = (twin + 15) & ~(size_t)15, each = fmrx_array_bytes(n, 2);
+	int16_t *x = reinterpret_cast<int16_t *>(w + at);
+	int16_t *y = reinterpret_cast<int16_t *>(w + at + each);
+	if (int rc = launch_fmrx_split_c16(n, d_iq, x, y, stream))
+		return rc;
+	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, x, y, dphase0,
+		d_last, d_omag, d_ofreq, d_work, stream, true);
+}
+
+size_t cordic_plan_fm_rx_c16_workspace(const cordic_plan *plan, const cordic_config *conv,
+		size_t n)
+{
+	return fm_rx_ok(plan, conv, true) == CORDIC_OK
+		? fm_rx_c16_work_bytes(plan, conv, n) : 0;
+}
+
+int cordic_plan_fm_rx_c16_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile)
+{
+	return fm_rx_info(plan, conv, fused, tile, true);
+}
+
+int cordic_plan_fm_rx_c16(const cordic_plan *plan, const cordic_config *conv, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
+{
+	return fm_rx_decim_c16(plan, conv, n, 0, d_fcw, d_pm, phase0, d_acc, d_iq, dphase0,
+		d_last, d_omag, d_ofreq, d_work, stream);
+}
+
+size_t cordic_plan_fm_rx_decim_c16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r)
+{
+	return fm_rx_ok(plan, conv, true) == CORDIC_OK
+		? fm_rx_decim_c16_work_bytes(plan, conv, n, log2r) : 0;
+}
+
+int cordic_plan_fm_rx_decim_c16(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0,
+		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
+{
+	return fm_rx_decim_c16(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_iq,
+		dphase0, d_last, d_omag, d_ofreq, d_work, stream);
+}
+
 // ---- receiver banks: many of those jobs in two launches (cordic_fm_rx_bank.h)
 struct cordic_rxbank : BankHandle<cordic_fmrx_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
 	cordic_config conv;			// a copy
 	bool	io16 = false;			// the jobs' sample arrays hold int16
+	bool	iq = false;			// ... and d_xval is interleaved I/Q (_c16)
 	uint32_t passes = 0;
 	uint32_t log2r = 0;			// > 0: a decimating bank
 	SpanTable<RxSpan> spans;		// fused
 	uint32_t *d_conv = nullptr;		// fused: conv's kernel parameters
 };
 
-// all four creates: `jobs` is either job struct with the bank's k (RxJobs,
+// all six creates: `jobs` is either job struct with the bank's k (RxJobs,
 // cordic_fm_rx_bank.h); a fused bank uploads the converter's kernel parameters
 // behind its span table.  A bank that runs one by one keeps the fallback's
 // workspace at its largest, whatever the A/B knobs say at run.
@@ -785,14 +882,16 @@ static int rxbank_create(const cordic_plan *plan, const cordic_config *conv,
 		[&](bool io16) { return fm_rx_ok(plan, conv, io16); },
 		[&](bool io16) { return fm_rx_fused(plan, conv, io16); },
 		[&](bool io16, size_t n) {
-			if (!jobs.log2r)
-				return fm_rx_work_bytes(plan, conv, n, io16);
-			return fmrxd_work_bytes(false,
-				fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r), n,
-				jobs.log2r, io16 ? 2 : 4);
+			const size_t twin = !jobs.log2r ? fm_rx_work_bytes(plan, conv, n, io16)
+				: fmrxd_work_bytes(false,
+					fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r), n,
+					jobs.log2r, io16 ? 2 : 4);
+			// (interleaved jobs: the split arrays behind it)
+			return jobs.iq ? fmrx_c16_work_bytes(false, twin, n) : twin;
 		}, cordic_rxbank_destroy, [&](cordic_rxbank *b) {
 			b->conv = *conv;
 			b->log2r = jobs.log2r;
+			b->iq = jobs.iq;
 			return b->fused ? fmrxb_upload_conv(b->conv, &b->d_conv) : CORDIC_OK;
 		});
 }
@@ -820,6 +919,39 @@ int cordic_rxbank_create16(const cordic_plan *plan, const cordic_config *conv,
 		size_t njobs, const cordic_fmrx_job16 *jobs, cordic_rxbank **bank)
 {
 	return rxbank_create(plan, conv, njobs, jobs, bank);
+}
+
+// the interleaved creates: the jobs as 16-bit ones whose d_xval is d_iq
+// (fmrxb_from_c16); the checks keep rxbank_create's order
+static int rxbank_create_c16(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
+		cordic_rxbank **bank)
+{
+	if (!bank || (njobs && !jobs))
+		return CORDIC_ERR_ARGS;
+	if (njobs >= ((size_t)1 << 28)) {	// (refused before that many are copied)
+		const int rc = fm_rx_ok(plan, conv, true);
+		return rc ? rc : CORDIC_ERR_ARGS;
+	}
+	std::vector<cordic_fmrx_job16> split(njobs + 1);
+	for (size_t k = 0; k < njobs; k++)
+		split[k] = fmrxb_from_c16(jobs[k]);
+	// (NULL jobs with njobs == 0: NULL on, as _create16 would see it)
+	const cordic_fmrx_job16 *j16 = jobs ? split.data() : nullptr;
+	return rxbank_create(plan, conv, njobs, RxJobs(j16, log2r, true), bank);
+}
+
+int cordic_rxbank_create_c16(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job_c16 *jobs, cordic_rxbank **bank)
+{
+	return rxbank_create_c16(plan, conv, 0, njobs, jobs, bank);
+}
+
+int cordic_rxbank_create_decim_c16(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
+		cordic_rxbank **bank)
+{
+	return rxbank_create_c16(plan, conv, log2r, njobs, jobs, bank);
 }
 
 void cordic_rxbank_destroy(cordic_rxbank *bank)
@@ -853,8 +985,13 @@ int cordic_rxbank_run(const cordic_rxbank *bank, void *stream)
 		const SpanTable<RxSpan> &t = bank->spans;
 		return launch_fmrx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_conv,
 			t.d_spans, t.nspans, t.start(), t.part(), t.more(), bank->cus, bank->io16,
-			stream, bank->log2r);
+			stream, bank->log2r, bank->iq);
 	}, [&](const cordic_fmrx_job &jb) {
+		if (bank->iq)	// (d_xval carries the job's d_iq: fmrxb_from_c16)
+			return fm_rx_decim_c16(plan, &bank->conv, (size_t)jb.n, bank->log2r, jb.d_fcw,
+				jb.d_pm, jb.phase0, jb.d_acc, reinterpret_cast<const int16_t *>(jb.d_xval),
+				jb.dphase0, jb.d_last, reinterpret_cast<int16_t *>(jb.d_omag),
+				reinterpret_cast<int16_t *>(jb.d_ofreq), bank->d_work, stream);
 		// (log2r 0: the receiver's own call, cordic_plan_fm_rx or _rx16)
 		return fm_rx_decim(plan, &bank->conv, (size_t)jb.n, bank->log2r, jb.d_fcw,
 			jb.d_pm, jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.dphase0, jb.d_last,

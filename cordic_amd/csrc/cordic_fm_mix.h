@@ -492,6 +492,48 @@ __device__ __forceinline__ RotRegs rot_regs(const CoreParams &kp, const DirArgs 
 	return r;
 }
 
+// ---- IoC16: the container of INTERLEAVED int16 I/Q on the input side (the
+// *_c16 receivers, include/cordic_amd.h): complex sample i is the dword at iq +
+// 2 i, I in its low half and Q in its high half.  The outputs are Io16's (two
+// separate int16 arrays), so everything the kernels ask a container for on the
+// store side is inherited.  A lane's 4 complex samples are ONE 16-byte load at
+// any 4-byte-aligned address (the element alignment of `cvec`, as u32x4g's);
+// they wait for their pass as the 4 dwords they are and are separated in
+// registers: v_bfe_i32 for I, v_ashrrev_i32 for Q, the two instructions per
+// sample that the widening of two packed shorts costs Io16.  The loops take the
+// new path behind is_iq<IO> (if constexpr) and an overload of widen_iq; for
+// Io32 / Io16 they are the code they were.  The receiver kernels use it; if the
+// mixer family wants the format, fmx::pass_loop takes the same policy.
+struct IoC16 : Io16 {
+	typedef u32x4 cvec __attribute__((aligned(4)));
+};
+template <typename IO> struct is_iq : std::false_type {};
+template <> struct is_iq<IoC16> : std::true_type {};
+// 4 input samples of one array as they wait in registers (IoC16: of both)
+template <typename IO> struct raw_in {
+	typedef decltype(IO::narrow(i32x4{})) type;
+};
+template <> struct raw_in<IoC16> {
+	typedef u32x4 type;
+};
+// a lane's (x, y) from what it loaded
+template <typename IO, typename RAW>
+__device__ __forceinline__ void widen_iq(IO, const RAW &nx, const RAW &ny, i32x4 &tx,
+		i32x4 &ty)
+{
+	tx = IO::widen(nx);
+	ty = IO::widen(ny);
+}
+__device__ __forceinline__ void widen_iq(IoC16, const u32x4 &q, const u32x4 &, i32x4 &tx,
+		i32x4 &ty)
+{
+#pragma unroll
+	for (int v = 0; v < kVec; v++) {
+		tx[v] = (int32_t)(q[v] << 16) >> 16;
+		ty[v] = (int32_t)q[v] >> 16;
+	}
+}
+
 // ---- the block's prologue, of all four launch-2 kernels (fm_mix_xydir,
 // fm_mixbank_xydir, fm_rx_xydir, fm_rxbank_xydir): one piece for each side of
 // the barrier, which is the caller's -- a single call puts its front_sum
@@ -665,11 +707,18 @@ inline size_t blocks_per_cu(size_t lds)
 // <LJ, container> of a core of working width ww on samples of esize bytes: the
 // one home of "WW 35 is LJ 29" and "no Io16 at WW 35" (fmx_is_fused16).  The
 // receiver's units, compiled once per value, index their entry points by it.
-enum Unit { kUnitNone = -1, kUnitLj30 = 0, kUnitLj29 = 1, kUnitIo16 = 2 };
+// kUnitC16: the receivers' <30, IoC16> units, for interleaved 16-bit input --
+// where Io16 serves, and nowhere else.
+enum Unit { kUnitNone = -1, kUnitLj30 = 0, kUnitLj29 = 1, kUnitIo16 = 2, kUnitC16 = 3 };
 inline Unit unit_of(int ww, size_t esize)
 {
 	return esize == 2 ? (ww < 35 ? kUnitIo16 : kUnitNone)
 		: ww == 35 ? kUnitLj29 : kUnitLj30;
+}
+inline Unit unit_of(int ww, size_t esize, bool iq)
+{
+	const Unit u = unit_of(ww, esize);
+	return !iq ? u : u == kUnitIo16 ? kUnitC16 : kUnitNone;
 }
 
 // Calls f(integral_constant<int, LJ>, IO) for the unit; false: none, or f's

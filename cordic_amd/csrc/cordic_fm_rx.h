@@ -70,11 +70,14 @@ bool	fmrx_conv_is_fused(const cordic_config &conv);
 // of 4, d_work on that of 16 -- and no output range (the words at d_acc and
 // d_last and the `work_bytes` of d_work included) over anything else, by the
 // true byte ranges; nothing is launched.  n > 0.  log2r: the two outputs hold
-// n >> log2r elements (the decimating receiver).
+// n >> log2r elements (the decimating receiver).  iq: d_xval is the one
+// interleaved input array (the *_c16 forms: esize 2, on the 4-byte grid, 4 n
+// bytes) and d_yval is not looked at.
 int	fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r = 0);
+		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r = 0,
+		bool iq = false);
 
 // The fused path: two launches on `stream` (fm_rx_reduce, then fm_rx_xydir),
 // nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
@@ -82,11 +85,25 @@ int	fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 // fmrx_check_call.
 // log2r = k in 1 .. 8: launch 2 is fm_rx_decim_xydir (cordic_fm_rx_decim.hip),
 // which writes n >> k samples; n is a multiple of 2^k.
+// iq (esize 2): d_xval holds interleaved int16 I/Q, 2 n shorts, and d_yval is
+// not read -- the <30, IoC16> instances of launch 2 (fmx::IoC16).
 int	launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r = 0);
+		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r = 0,
+		bool iq = false);
+
+// The *_c16 forms' fallback: [the *16 twin's workspace | x | y of n shorts],
+// each part on the 16-byte grid; one launch of fm_rx_split_c16 fills x and y
+// from d_iq (n > 0 complex samples on the 4-byte grid), then the twin runs.
+constexpr size_t fmrx_c16_work_bytes(bool fused, size_t twin_bytes, size_t n)
+{
+	return !n || fused ? twin_bytes
+		: ((twin_bytes + 15) & ~(size_t)15) + 2 * fmrx_array_bytes(n, 2);
+}
+int	launch_fmrx_split_c16(size_t n, const int16_t *d_iq, int16_t *d_x, int16_t *d_y,
+		void *stream);
 
 } // namespace cordic_amd
 
@@ -146,7 +163,8 @@ __device__ __forceinline__ const CoreParams &conv_params(const uint32_t *ckmem, 
 // pass, and are dead again behind it.
 // d_last: where the lane with sample n - 1 writes its phase; NULL in every
 // span but a job's last, and where the job has none.  pm may be NULL
-// (wave-uniform).  Nothing at or behind n is read or written, and in front of
+// (wave-uniform).  IO = fmx::IoC16: ax is the span's interleaved I/Q (complex
+// sample i at ax + 2 i, one 16-byte load per lane), ay is not read.  Nothing at or behind n is read or written, and in front of
 // sample 0 only the halo vector is read.
 template <int LJ, int NLIVE, typename IO>
 __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &da,
@@ -160,7 +178,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 {
 	typedef typename IO::ivec ivec;
 	typedef typename IO::ielem ielem;
-	typedef decltype(IO::narrow(i32x4{})) raw4;	// 4 samples as they lie in memory
+	// 4 samples as they lie in memory (IoC16: 4 complex ones, in x; ay unused)
+	typedef typename fmx::raw_in<IO>::type raw4;
 	const ptrdiff_t sn = (ptrdiff_t)n;
 	const unsigned lane = tid & 63u;
 	// this lane's 4 samples of the pass at t0
@@ -174,8 +193,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 			f = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(fcw + i));
 			if (pm)	// (wave-uniform)
 				m = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(pm + i));
-			x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
-			y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			if constexpr (fmx::is_iq<IO>::value) {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const typename IO::cvec *>(ax + 2 * i));
+			} else {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
+				y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			}
 		} else if (i >= 0 && i < sn) {	// the last, partial vector: one lane
 #pragma unroll
 			for (int v = 0; v < kVec; v++) {
@@ -183,8 +206,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 					f[v] = fcw[i + v];
 					if (pm)
 						m[v] = pm[i + v];
-					x[v] = ax[i + v];
-					y[v] = ay[i + v];
+					if constexpr (fmx::is_iq<IO>::value) {
+						x[v] = reinterpret_cast<const uint32_t *>(ax)[i + v];
+					} else {
+						x[v] = ax[i + v];
+						y[v] = ay[i + v];
+					}
 				}
 			}
 		}
@@ -197,7 +224,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 		const bool halo = t0 == 0 && tid == 0;
 		u32x4 f = nf;
 		const u32x4 m = nm;
-		const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
+		i32x4 tx, ty;
+		fmx::widen_iq(IO{}, nx, ny, tx, ty);
 		if (t0 + kFmrxPass < n + kFmrxHalo)
 			load_pass(t0 + kFmrxPass, nf, nm, nx, ny);
 
@@ -278,20 +306,22 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 }
 
 // ---- the single call's kernel arguments and the launchers of its instances,
-// one unit per <LJ, container> (cordic_fm_rx.hip compiled three times:
-// itself, cordic_fm_rx_lj29.hip, cordic_fm_rx_io16.hip); false: no instance
+// one unit per <LJ, container> (cordic_fm_rx.hip compiled four times: itself,
+// cordic_fm_rx_lj29.hip, cordic_fm_rx_io16.hip, cordic_fm_rx_c16.hip); false: no
+// instance
 struct RxArgs {
 	const uint32_t *fcw, *pm;	// pm may be NULL
 	uint32_t *acc, *last;		// either may be NULL
 	const uint32_t *work;		// [0] start, [1] prev, [4 + b] partials, conv
 	const void *x, *y;		// int32 or int16, by the kernel's container
+					// (IoC16: x interleaved, y not read)
 	void	*mag, *freq;
 	size_t	n, span;		// span: samples per block, whole passes less the halo
 	uint32_t xw;			// LDS byte offset of the exchange words
 };
 typedef bool RxLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxArgs &a);
-RxLaunch launch_rx_lj30, launch_rx_lj29, launch_rx_io16;	// by fmx::Unit
+RxLaunch launch_rx_lj30, launch_rx_lj29, launch_rx_io16, launch_rx_c16;	// by fmx::Unit
 
 // ---- host side of both units
 // the tables and the exchange words behind them

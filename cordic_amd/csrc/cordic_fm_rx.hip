@@ -46,11 +46,14 @@
 // A/B knob like CORDIC_FMX_MAX_BLOCKS) caps the grid at n blocks.  The bits do
 // not depend on it.
 //
-// The unit is compiled three times, one <LJ, container> each, so that the
-// three build beside each other: as itself (<30, Io32>, launch 1 and the host
-// side), as cordic_fm_rx_lj29.hip (<29, Io32>) and as cordic_fm_rx_io16.hip
-// (<30, Io16>).  Each defines ONE entry point, FMRX_LAUNCH, around
-// fmx::with_stages; launch_fm_rx indexes the three by fmx::unit_of.
+// The unit is compiled four times, one <LJ, container> each, so that the
+// four build beside each other: as itself (<30, Io32>, launch 1 and the host
+// side), as cordic_fm_rx_lj29.hip (<29, Io32>), as cordic_fm_rx_io16.hip
+// (<30, Io16>) and as cordic_fm_rx_c16.hip (<30, fmx::IoC16>: interleaved int16
+// I/Q in d_xval, cordic_plan_fm_rx_c16; its registers are listed there).  Each
+// defines ONE entry point, FMRX_LAUNCH, around fmx::with_stages; launch_fm_rx
+// indexes the four by fmx::unit_of.  The host side also holds fm_rx_split_c16,
+// the split kernel of the *_c16 forms' fallback.
 //
 // Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
 // .private_segment_fixed_size is 0 for every instance: nothing spills to
@@ -84,7 +87,7 @@
 #include "cordic_fm_rx_decim.h"
 
 #ifndef CORDIC_FMRX_UNIT
-#define CORDIC_FMRX_UNIT 30	// 30: <30, Io32> and the host side; 29; 16
+#define CORDIC_FMRX_UNIT 30	// 30: <30, Io32> and the host side; 29; 16; 0xc16
 #endif
 
 namespace cordic_amd {
@@ -118,11 +121,13 @@ __global__ __launch_bounds__(kBlock) void fm_rx_xydir(CoreParams kp, DirArgs da,
 	const size_t lo = (size_t)blockIdx.x * a.span;	// < n by the grid
 	const size_t cnt = (a.n - lo < a.span) ? a.n - lo : a.span;
 	const bool tail = blockIdx.x == gridDim.x - 1;
+	// shorts per input sample: IoC16 has both halves in a.x (a.y is not read)
+	constexpr size_t kIn = fmx::is_iq<IO>::value ? 2 : 1;
 	// the phase of sample lo, without its pm
 	uint32_t carry = a.work[0] + ex[8] + ex[9] + ex[10] + ex[11];
 	unsigned par = 0;
 	pass_loop<LJ, NLIVE>(kp, da, rr, bk_base, ckmem, ln, a.fcw + lo,
-		a.pm ? a.pm + lo : nullptr, static_cast<const ielem *>(a.x) + lo,
+		a.pm ? a.pm + lo : nullptr, static_cast<const ielem *>(a.x) + kIn * lo,
 		static_cast<const ielem *>(a.y) + lo, static_cast<ielem *>(a.mag) + lo,
 		static_cast<ielem *>(a.freq) + lo, cnt, blockIdx.x == 0, a.work[1],
 		tail ? a.last : nullptr, carry, par, ex, tid, wave, IO{});
@@ -139,6 +144,10 @@ typedef Io32 UnitIo;
 #define FMRX_LAUNCH launch_rx_io16
 constexpr int kUnitLj = 30;
 typedef Io16 UnitIo;
+#elif CORDIC_FMRX_UNIT == 0xc16
+#define FMRX_LAUNCH launch_rx_c16
+constexpr int kUnitLj = 30;
+typedef fmx::IoC16 UnitIo;
 #else
 #define FMRX_LAUNCH launch_rx_lj30
 constexpr int kUnitLj = 30;
@@ -222,17 +231,59 @@ bool fmrx_conv_is_fused(const cordic_config &conv)
 int fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r)
+		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r, bool iq)
 {
 	return iq_call_ok(n, d_acc, d_last, d_fcw, d_pm, d_xval, d_yval, d_omag, d_ofreq,
-		esize, d_work, work_bytes, log2r) ? CORDIC_OK : CORDIC_ERR_ARGS;
+		esize, d_work, work_bytes, log2r, iq) ? CORDIC_OK : CORDIC_ERR_ARGS;
+}
+
+// The *_c16 forms' fallback: thread t splits complex samples 4 t .. 4 t + 3, one
+// 16-byte load at any 4-byte alignment and two 8-byte stores (x and y lie on the
+// 16-byte grid inside the workspace); the last, partial vector goes element by
+// element.  Nothing at or behind complex sample n is read or written.
+namespace fmrx {
+__global__ __launch_bounds__(256) void fm_rx_split_c16(const int16_t *__restrict__ iq,
+		int16_t *__restrict__ x, int16_t *__restrict__ y, size_t n)
+{
+	const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+	if (i + 4 <= n) {
+		const u32x4 q = CORDIC_LOAD_IN(reinterpret_cast<const fmx::IoC16::cvec *>(iq + 2 * i));
+		u16x4 a, b;
+#pragma unroll
+		for (int v = 0; v < 4; v++) {
+			a[v] = (uint16_t)q[v];
+			b[v] = (uint16_t)(q[v] >> 16);
+		}
+		*reinterpret_cast<u16x4 *>(x + i) = a;
+		*reinterpret_cast<u16x4 *>(y + i) = b;
+	} else {
+		for (size_t j = i; j < n; j++) {
+			x[j] = iq[2 * j];
+			y[j] = iq[2 * j + 1];
+		}
+	}
+}
+} // namespace fmrx
+
+int launch_fmrx_split_c16(size_t n, const int16_t *d_iq, int16_t *d_x, int16_t *d_y,
+		void *stream)
+{
+	(void)hipGetLastError();	// (a stale error is not this call's)
+	if (n == 0)
+		return CORDIC_OK;
+	const size_t blocks = (n + 1023) / 1024;
+	if (blocks > 0x7fffffffu)
+		return CORDIC_ERR_ARGS;
+	hipLaunchKernelGGL(fmrx::fm_rx_split_c16, dim3((unsigned)blocks), dim3(256), 0,
+		static_cast<hipStream_t>(stream), d_iq, d_x, d_y, n);
+	return tnco::finish(true);
 }
 
 int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r)
+		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r, bool iq)
 {
 	using namespace fmrx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -255,10 +306,11 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 	const size_t span = cs.span;
 	const unsigned grid = (unsigned)cs.grid;
 	// the instance first: nothing is enqueued for a core without one
-	static RxLaunch *const units[3] = {launch_rx_lj30, launch_rx_lj29, launch_rx_io16};
-	static fmrxd::RxdLaunch *const dunits[3] = {fmrxd::launch_rxd_lj30,
-		fmrxd::launch_rxd_lj29, fmrxd::launch_rxd_io16};
-	const fmx::Unit u = fmx::unit_of(cfg.ww, esize);
+	static RxLaunch *const units[4] = {launch_rx_lj30, launch_rx_lj29, launch_rx_io16,
+		launch_rx_c16};
+	static fmrxd::RxdLaunch *const dunits[4] = {fmrxd::launch_rxd_lj30,
+		fmrxd::launch_rxd_lj29, fmrxd::launch_rxd_io16, fmrxd::launch_rxd_c16};
+	const fmx::Unit u = fmx::unit_of(cfg.ww, esize, iq);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	uint32_t *work = static_cast<uint32_t *>(d_work);

@@ -66,23 +66,49 @@ constexpr SpanRule fmrxb_rule(uint32_t log2r)
 // The jobs of a create, of either struct (JobView, cordic_span_bank.h), and the
 // bank's k = log2r (0: cordic_rxbank_create), which every job of the view
 // carries to the checks and to span_place (as MixJobs, cordic_fm_mix_bank.h).
+// iq: the jobs of a cordic_rxbank_create_c16 (fmrxb_from_c16 below) -- 16-bit
+// jobs whose d_xval is the job's d_iq, interleaved int16 I/Q of 2 n shorts on
+// the 4-byte grid, and whose d_yval is NULL and not looked at.
 struct RxJob : cordic_fmrx_job {
 	uint32_t log2r = 0;
+	bool	iq = false;
 };
 struct RxJobs : JobView<cordic_fmrx_job, cordic_fmrx_job16> {
 	typedef JobView<cordic_fmrx_job, cordic_fmrx_job16> View;
 	uint32_t log2r = 0;
+	bool	iq = false;
 	RxJobs(const cordic_fmrx_job *j, uint32_t k = 0) : View(j), log2r(k) {}
-	RxJobs(const cordic_fmrx_job16 *j, uint32_t k = 0) : View(j), log2r(k) {}
+	RxJobs(const cordic_fmrx_job16 *j, uint32_t k = 0, bool interleaved = false)
+		: View(j), log2r(k), iq(interleaved) {}
 	RxJobs(std::nullptr_t) : View(nullptr) {}
 	RxJob	operator[](size_t k) const
 	{
 		RxJob m;
 		static_cast<cordic_fmrx_job &>(m) = View::operator[](k);
 		m.log2r = log2r;
+		m.iq = iq;
 		return m;
 	}
 };
+
+// a cordic_fmrx_job_c16 as the 16-bit job the bank's host layer works on
+inline cordic_fmrx_job16 fmrxb_from_c16(const cordic_fmrx_job_c16 &c)
+{
+	cordic_fmrx_job16 j{};
+	j.d_fcw = c.d_fcw;
+	j.d_pm = c.d_pm;
+	j.d_xval = c.d_iq;
+	j.d_omag = c.d_omag;
+	j.d_ofreq = c.d_ofreq;
+	j.d_acc = c.d_acc;
+	j.d_last = c.d_last;
+	j.n = c.n;
+	j.phase0 = c.phase0;
+	j.dphase0 = c.dphase0;
+	j.reserved = c.reserved;
+	return j;
+}
+static_assert(sizeof(cordic_fmrx_job_c16) == 80, "as include/cordic_amd.h documents it");
 #define F(f) CORDIC_SAME_FIELD(cordic_fmrx_job, cordic_fmrx_job16, f)
 static_assert(sizeof(cordic_fmrx_job) == 88 && F(d_fcw) && F(d_pm) && F(d_xval)
 	&& F(d_yval) && F(d_omag) && F(d_ofreq) && F(d_acc) && F(d_last) && F(n)
@@ -92,7 +118,8 @@ static_assert(sizeof(cordic_fmrx_job) == 88 && F(d_fcw) && F(d_pm) && F(d_xval)
 
 // The argument checks of cordic_rxbank_create / _create16 that need no device
 // (bank_jobs_valid, cordic_span_bank.h): d_fcw and the four sample arrays
-// required, d_pm, d_acc and d_last optional; the outputs are d_omag, d_ofreq
+// required (of an interleaved job: d_iq, on the 4-byte grid, 4 n bytes), d_pm,
+// d_acc and d_last optional; the outputs are d_omag, d_ofreq
 // and the words at d_acc and d_last.  A decimating bank (jobs.log2r = k > 0): k
 // <= 8, every n a multiple of 2^k, and the two outputs are n >> k elements long.
 inline bool fmrxb_jobs_valid(size_t njobs, RxJobs jobs)
@@ -106,6 +133,13 @@ inline bool fmrxb_jobs_valid(size_t njobs, RxJobs jobs)
 		[](const RxJob &jb, uint64_t es, const void **word) {
 			word[0] = jb.d_acc;
 			word[1] = jb.d_last;
+			// (interleaved: one input array of 2 * es bytes per sample)
+			if (jb.iq)
+				return std::array<JobArray, 6>{{{jb.d_fcw, 4, true, false},
+					{jb.d_xval, 2 * es, true, false}, {nullptr, es, false, false},
+					{jb.d_pm, 4, false, false},
+					{jb.d_omag, es, true, true, jb.log2r},
+					{jb.d_ofreq, es, true, true, jb.log2r}}};
 			return std::array<JobArray, 6>{{{jb.d_fcw, 4, true, false},
 				{jb.d_xval, es, true, false}, {jb.d_yval, es, true, false},
 				{jb.d_pm, 4, false, false}, {jb.d_omag, es, true, true, jb.log2r},
@@ -117,10 +151,11 @@ inline bool fmrxb_jobs_valid(size_t njobs, RxJobs jobs)
 // `at` = s0 * esize bytes in, and the discriminator's word.  s0 is a multiple
 // of R = 2^k (fmrxb_rule), so the outputs of a decimating bank begin (s0 >> k) *
 // esize = at >> k bytes in.
+// An interleaved job's x carries d_iq, 2 * at bytes in, and its y is unused.
 inline void span_place(RxSpan *d, const RxJob &jb, uint64_t at)
 {
-	d->x = (uintptr_t)jb.d_xval + at;
-	d->y = (uintptr_t)jb.d_yval + at;
+	d->x = (uintptr_t)jb.d_xval + (jb.iq ? 2 * at : at);
+	d->y = jb.iq ? 0 : (uintptr_t)jb.d_yval + at;
 	d->mag = (uintptr_t)jb.d_omag + (at >> jb.log2r);
 	d->freq = (uintptr_t)jb.d_ofreq + (at >> jb.log2r);
 	d->last = (uintptr_t)jb.d_last;
@@ -139,12 +174,13 @@ int	fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv);
 // at create.  An empty table launches nothing.  log2r = k in 1 .. 8: the spans
 // were cut for a decimating bank (fmrxb_rule(k)), and launch 2 is
 // fm_rxbank_decim_xydir (cordic_fm_rx_bank_decim.hip).  CORDIC_OK or
-// CORDIC_ERR_DEVICE.
+// iq: the spans were cut from interleaved jobs (RxJobs::iq, below; io16 too):
+// the <30, IoC16> instances.  CORDIC_OK or CORDIC_ERR_DEVICE.
 struct DxInfo;		// (cordic_internal.h)
 int	launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
 		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream, uint32_t log2r = 0);
+		void *stream, uint32_t log2r = 0, bool iq = false);
 
 // (as MixBankTraits, cordic_fm_mix_bank.h; the rule depends on the bank's k)
 struct RxBankTraits {
@@ -165,7 +201,8 @@ typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, void *stream,
 		const dev::CoreParams &kp, const dev::DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
 		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw, uint32_t log2r);
-BankLaunch launch_rxbank_decim_lj30, launch_rxbank_decim_lj29, launch_rxbank_decim_io16;
+BankLaunch launch_rxbank_decim_lj30, launch_rxbank_decim_lj29, launch_rxbank_decim_io16,
+	launch_rxbank_decim_c16;
 }
 #endif
 

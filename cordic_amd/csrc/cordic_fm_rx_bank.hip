@@ -37,10 +37,12 @@
 // Knobs: CORDIC_FMRXB_PASSES and CORDIC_FMRXB_MAX_SPANS at create,
 // CORDIC_FMRXB_MAX_BLOCKS at every run.  The bits depend on none.
 //
-// The unit is compiled three times, one <LJ, container> each: as itself (<30,
-// Io32>, launch 1 and the host side), as cordic_fm_rx_bank_lj29.hip and as
-// cordic_fm_rx_bank_io16.hip.  Each defines ONE entry point, FMRXB_LAUNCH,
-// around fmx::with_stages; launch_fmrx_bank indexes the three by fmx::unit_of.
+// The unit is compiled four times, one <LJ, container> each: as itself (<30,
+// Io32>, launch 1 and the host side), as cordic_fm_rx_bank_lj29.hip, as
+// cordic_fm_rx_bank_io16.hip and as cordic_fm_rx_bank_c16.hip (interleaved
+// int16 I/Q: a span's x carries d_iq, its y is unused).  Each defines ONE entry
+// point, FMRXB_LAUNCH, around fmx::with_stages; launch_fmrx_bank indexes the
+// four by fmx::unit_of.
 //
 // Registers: the table in DESIGN.md section 4.8 and profiles/r20/fm_rx.txt.
 #include <hip/hip_runtime.h>
@@ -59,7 +61,7 @@
 #include "cordic_span_reduce.h"
 
 #ifndef CORDIC_FMRXB_UNIT
-#define CORDIC_FMRXB_UNIT 30	// 30: <30, Io32>, launch 1 and the host side; 29; 16
+#define CORDIC_FMRXB_UNIT 30	// 30: <30, Io32>, launch 1 and the host side; 29; 16; 0xc16
 #endif
 
 namespace cordic_amd {
@@ -84,7 +86,8 @@ typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
 		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw);
-BankLaunch launch_rxbank_lj30, launch_rxbank_lj29, launch_rxbank_io16;	// by fmx::Unit
+BankLaunch launch_rxbank_lj30, launch_rxbank_lj29, launch_rxbank_io16,
+	launch_rxbank_c16;	// by fmx::Unit
 
 // launch 2 (see the head of this file)
 template <int LJ, int NLIVE, typename IO>
@@ -140,6 +143,10 @@ typedef Io32 UnitIo;
 #define FMRXB_LAUNCH launch_rxbank_io16
 constexpr int kUnitLj = 30;
 typedef Io16 UnitIo;
+#elif CORDIC_FMRXB_UNIT == 0xc16
+#define FMRXB_LAUNCH launch_rxbank_c16
+constexpr int kUnitLj = 30;
+typedef fmx::IoC16 UnitIo;
 #else
 #define FMRXB_LAUNCH launch_rxbank_lj30
 constexpr int kUnitLj = 30;
@@ -170,7 +177,7 @@ int fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv)
 int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
 		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream, uint32_t log2r)
+		void *stream, uint32_t log2r, bool iq)
 {
 	using namespace fmrx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -186,11 +193,12 @@ int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 	// launch 1 has 8 waves a SIMD: 8 blocks of 4 waves a CU
 	const SpanGrids g = span_grids(nspans, cus, 8, "CORDIC_FMRXB_MAX_BLOCKS", per_cu);
 	// the instance first: nothing is enqueued for a core without one
-	static BankLaunch *const units[3] = {launch_rxbank_lj30, launch_rxbank_lj29,
-		launch_rxbank_io16};
-	static fmrxd::BankLaunch *const dunits[3] = {fmrxd::launch_rxbank_decim_lj30,
-		fmrxd::launch_rxbank_decim_lj29, fmrxd::launch_rxbank_decim_io16};
-	const fmx::Unit u = fmx::unit_of(cfg.ww, io16 ? 2 : 4);
+	static BankLaunch *const units[4] = {launch_rxbank_lj30, launch_rxbank_lj29,
+		launch_rxbank_io16, launch_rxbank_c16};
+	static fmrxd::BankLaunch *const dunits[4] = {fmrxd::launch_rxbank_decim_lj30,
+		fmrxd::launch_rxbank_decim_lj29, fmrxd::launch_rxbank_decim_io16,
+		fmrxd::launch_rxbank_decim_c16};
+	const fmx::Unit u = fmx::unit_of(cfg.ww, io16 ? 2 : 4, iq);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	hipLaunchKernelGGL((span_reduce<RxSpan, 256>), dim3(g.reduce), dim3(256), 0, st,

@@ -21,9 +21,9 @@
 // barrier.  The shares of a span's prologue (ex[8 .. 12)) are written only
 // behind those.
 //
-// The unit is compiled three times, as cordic_fm_rx_bank.hip is: as itself
-// (<30, Io32>), as cordic_fm_rx_bank_decim_lj29.hip and as
-// cordic_fm_rx_bank_decim_io16.hip.  Registers: profiles/r23/fm_rx_decim.txt.
+// The unit is compiled four times, as cordic_fm_rx_bank.hip is: as itself
+// (<30, Io32>), as cordic_fm_rx_bank_decim_lj29.hip, as
+// cordic_fm_rx_bank_decim_io16.hip and as cordic_fm_rx_bank_decim_c16.hip.  Registers: profiles/r23/fm_rx_decim.txt.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -36,7 +36,7 @@
 #include "cordic_fm_rx_bank.h"
 
 #ifndef CORDIC_FMRXBD_UNIT
-#define CORDIC_FMRXBD_UNIT 30	// 30: <30, Io32>; 29; 16
+#define CORDIC_FMRXBD_UNIT 30	// 30: <30, Io32>; 29; 16; 0xc16
 #endif
 
 namespace cordic_amd {
@@ -99,6 +99,10 @@ typedef Io32 UnitIo;
 #define FMRXBD_LAUNCH launch_rxbank_decim_io16
 constexpr int kUnitLj = 30;
 typedef Io16 UnitIo;
+#elif CORDIC_FMRXBD_UNIT == 0xc16
+#define FMRXBD_LAUNCH launch_rxbank_decim_c16
+constexpr int kUnitLj = 30;
+typedef fmx::IoC16 UnitIo;
 #else
 #define FMRXBD_LAUNCH launch_rxbank_decim_lj30
 constexpr int kUnitLj = 30;

@@ -120,7 +120,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 {
 	typedef typename IO::ivec ivec;
 	typedef typename IO::ielem ielem;
-	typedef decltype(IO::narrow(i32x4{})) raw4;	// 4 samples as they lie in memory
+	// 4 samples as they lie in memory (IoC16: 4 complex ones, in x; ay unused)
+	typedef typename fmx::raw_in<IO>::type raw4;
 	const ptrdiff_t sn = (ptrdiff_t)n;
 	const ptrdiff_t halo_n = k > 2 ? (ptrdiff_t)1 << k : 4;
 	const ptrdiff_t sm = sn >> k;			// decimated samples of the span
@@ -138,8 +139,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 			f = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(fcw + i));
 			if (pm)	// (wave-uniform)
 				m = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(pm + i));
-			x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
-			y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			if constexpr (fmx::is_iq<IO>::value) {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const typename IO::cvec *>(ax + 2 * i));
+			} else {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
+				y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			}
 		} else if (i >= 0 && i < sn) {	// k = 1: the last, partial vector
 #pragma unroll
 			for (int v = 0; v < kVec; v++) {
@@ -147,8 +152,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 					f[v] = fcw[i + v];
 					if (pm)
 						m[v] = pm[i + v];
-					x[v] = ax[i + v];
-					y[v] = ay[i + v];
+					if constexpr (fmx::is_iq<IO>::value) {
+						x[v] = reinterpret_cast<const uint32_t *>(ax)[i + v];
+					} else {
+						x[v] = ax[i + v];
+						y[v] = ay[i + v];
+					}
 				}
 			}
 		}
@@ -160,7 +169,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 	load_pass(0, nf, nm, nx, ny);
 	for (size_t t0 = 0; t0 < n + (size_t)halo_n; t0 += kFmrxPass) {
 		const u32x4 f = nf, m = nm;
-		const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
+		i32x4 tx, ty;
+		fmx::widen_iq(IO{}, nx, ny, tx, ty);
 		const bool last_pass = t0 + kFmrxPass >= n + (size_t)halo_n;
 		if (!last_pass)
 			load_pass(t0 + kFmrxPass, nf, nm, nx, ny);
@@ -303,7 +313,7 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 // (cordic_fm_rx_decim.hip compiled three times); false: no instance
 typedef bool RxdLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const fmrx::RxArgs &a, uint32_t log2r);
-RxdLaunch launch_rxd_lj30, launch_rxd_lj29, launch_rxd_io16;	// by fmx::Unit
+RxdLaunch launch_rxd_lj30, launch_rxd_lj29, launch_rxd_io16, launch_rxd_c16;	// by fmx::Unit
 
 // the tables, the exchange words and the ring behind them
 inline size_t lds_bytes(const DxInfo &dx, uint32_t *xw)

@@ -32,8 +32,9 @@
 // A/B knob); the bits do not depend on it.  CORDIC_FMRXD_FALLBACK=1
 // (cordic_abi.cpp) sends a fused pair's single call through the fallback.
 //
-// The unit is compiled three times, as cordic_fm_rx.hip is: as itself (<30,
-// Io32>), as cordic_fm_rx_decim_lj29.hip and as cordic_fm_rx_decim_io16.hip.
+// The unit is compiled four times, as cordic_fm_rx.hip is: as itself (<30,
+// Io32>), as cordic_fm_rx_decim_lj29.hip, as cordic_fm_rx_decim_io16.hip and as
+// cordic_fm_rx_decim_c16.hip (interleaved int16 I/Q in, fmx::IoC16).
 // Registers and LDS per instance: profiles/r23/fm_rx_decim.txt.
 #include <hip/hip_runtime.h>
 
@@ -47,7 +48,7 @@
 #include "cordic_fm_rx_decim.h"
 
 #ifndef CORDIC_FMRXD_UNIT
-#define CORDIC_FMRXD_UNIT 30	// 30: <30, Io32>; 29; 16
+#define CORDIC_FMRXD_UNIT 30	// 30: <30, Io32>; 29; 16; 0xc16
 #endif
 
 namespace cordic_amd {
@@ -81,11 +82,13 @@ __global__ __launch_bounds__(kBlock) void fm_rx_decim_xydir(CoreParams kp, DirAr
 	const size_t cnt = (a.n - lo < a.span) ? a.n - lo : a.span;
 	const size_t olo = lo >> log2r;
 	const bool tail = blockIdx.x == gridDim.x - 1;
+	// shorts per input sample: IoC16 has both halves in a.x (a.y is not read)
+	constexpr size_t kIn = fmx::is_iq<IO>::value ? 2 : 1;
 	// the phase of sample lo, without its pm
 	uint32_t carry = a.work[0] + ex[8] + ex[9] + ex[10] + ex[11];
 	unsigned par = 0, fpar = 0;
 	pass_loop<LJ, NLIVE>(kp, da, rr, bk_base, ckmem, ln, a.fcw + lo,
-		a.pm ? a.pm + lo : nullptr, static_cast<const ielem *>(a.x) + lo,
+		a.pm ? a.pm + lo : nullptr, static_cast<const ielem *>(a.x) + kIn * lo,
 		static_cast<const ielem *>(a.y) + lo, static_cast<ielem *>(a.mag) + olo,
 		static_cast<ielem *>(a.freq) + olo, cnt, log2r, blockIdx.x == 0, a.work[1],
 		tail ? a.last : nullptr, carry, par, fpar, ex,
@@ -103,6 +106,10 @@ typedef Io32 UnitIo;
 #define FMRXD_LAUNCH launch_rxd_io16
 constexpr int kUnitLj = 30;
 typedef Io16 UnitIo;
+#elif CORDIC_FMRXD_UNIT == 0xc16
+#define FMRXD_LAUNCH launch_rxd_c16
+constexpr int kUnitLj = 30;
+typedef fmx::IoC16 UnitIo;
 #else
 #define FMRXD_LAUNCH launch_rxd_lj30
 constexpr int kUnitLj = 30;

@@ -1754,6 +1754,95 @@ int	cordic_rxbank_create_decim16(const cordic_plan *plan, const cordic_config *c
 		uint32_t log2r, size_t njobs, const cordic_fmrx_job16 *jobs,
 		cordic_rxbank **bank);
 
+/* Tuned FM receiver on INTERLEAVED int16 I/Q: single, decimating, banks.
+ *
+ * What an ADC, a network capture or a file delivers is complex int16 in ONE
+ * array, I0 Q0 I1 Q1 ..  The *_c16 forms take it as it comes: d_iq holds n
+ * complex samples as 2 n shorts, x_i = d_iq[2 i], y_i = d_iq[2 i + 1], and every
+ * output sample and the words *d_acc and *d_last are, bit for bit, those of the
+ * split-array call on d_xval[i] = d_iq[2 i], d_yval[i] = d_iq[2 i + 1]:
+ *   cordic_plan_fm_rx_c16          cordic_plan_fm_rx16
+ *   cordic_plan_fm_rx_decim_c16    cordic_plan_fm_rx_decim16
+ *   cordic_rxbank_create_c16       cordic_rxbank_create16
+ *   cordic_rxbank_create_decim_c16 cordic_rxbank_create_decim16
+ * without the caller's splitting pass (one launch and 8 bytes per sample).
+ * d_omag and d_ofreq stay separate int16 arrays of n >> k elements.  Everything
+ * the twins document carries over: phase0 and dphase0 are added by every call;
+ * a job cut into consecutive calls that share d_acc and d_last gives the bits
+ * of one call (the decimating forms: cut at multiples of R); a captured call
+ * replayed continues; n == 0 is CORDIC_OK with nothing touched; k = 0 is the
+ * plain form; the decimating forms need n % R == 0.
+ *
+ * Status codes: those of the *16 twin, in its order, the container rule
+ * included.  The argument checks differ in one place: d_iq replaces the pair
+ * d_xval / d_yval.  d_iq must be non-NULL and sit on the 4-byte grid, one
+ * complex sample -- ANY 4-byte alignment is served, not only 16; its byte range
+ * is 4 n, and no output (d_omag, d_ofreq, the words at d_acc and d_last,
+ * d_work) may overlap it.  d_omag and d_ofreq stay on the 2-byte grid.
+ *
+ * Two paths, identical bits:
+ *   fused     exactly where cordic_plan_fm_rx16_info answers 1;
+ *             cordic_plan_fm_rx_c16_info reports the same *fused and *tile =
+ *             1024.  The twin's two launches with the twin's grid, spans, halo
+ *             and workspace; in the second a lane gets its four samples by ONE
+ *             16-byte load at d_iq + 2 i and separates the halves in registers.
+ *             12 bytes per sample (16 with d_pm), as the twin.  Nothing at or
+ *             behind complex sample n is read.
+ *   fallback  every other pair: one small kernel splits d_iq into two int16
+ *             arrays inside d_work, then the *16 twin runs from them -- its
+ *             launches, nothing allocated.  CORDIC_FMRXD_FALLBACK=1 forces it
+ *             for cordic_plan_fm_rx_decim_c16, as for its twin.
+ *
+ * d_work: at least cordic_plan_fm_rx_c16_workspace(plan, conv, n) bytes
+ * (cordic_plan_fm_rx_decim_c16_workspace(plan, conv, n, log2r)).  Pure host
+ * functions: 0 where the call would fail and for n == 0, a multiple of 16,
+ * non-decreasing in n.  Fused: the twin's workspace.  Otherwise [the twin's
+ * workspace | x | y of n shorts], each part on the 16-byte grid: at most
+ * cordic_plan_fm_rx16_workspace(plan, conv, n) + 4 n + 32 bytes
+ * (cordic_plan_fm_rx_decim16_workspace(plan, conv, n, log2r) + 4 n + 32).
+ *
+ * Banks: cordic_rxbank_create_c16 / _create_decim_c16 take jobs of
+ * cordic_fmrx_job_c16 and follow every rule of cordic_rxbank_create16 /
+ * _create_decim16 in its order, with d_iq in the place of d_xval / d_yval: on
+ * the 4-byte grid, 4 n bytes in the sorted overlap check.  The result is an
+ * ordinary cordic_rxbank: _run, _info and _destroy serve it unchanged, and
+ * cordic_rxbank_info tells fused from one by one (run then loops the single
+ * *_c16 call over the jobs with a workspace allocated at create for the
+ * longest job).
+ * Measured: profiles/r24/fm_rx_c16.txt.
+ */
+size_t	cordic_plan_fm_rx_c16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n);
+int	cordic_plan_fm_rx_c16_info(const cordic_plan *plan, const cordic_config *conv,
+		int32_t *fused, int32_t *tile);
+int	cordic_plan_fm_rx_c16(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc, const int16_t *d_iq,
+		uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream);
+size_t	cordic_plan_fm_rx_decim_c16_workspace(const cordic_plan *plan,
+		const cordic_config *conv, size_t n, uint32_t log2r);
+int	cordic_plan_fm_rx_decim_c16(const cordic_plan *plan, const cordic_config *conv,
+		size_t n, uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm,
+		uint32_t phase0, uint32_t *d_acc, const int16_t *d_iq,
+		uint32_t dphase0, uint32_t *d_last,
+		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream);
+typedef struct cordic_fmrx_job_c16 {
+	const uint32_t *d_fcw;		/* n words                              */
+	const uint32_t *d_pm;		/* n words, or NULL                     */
+	const int16_t *d_iq;		/* 2 n shorts: I0 Q0 I1 Q1 ..           */
+	int16_t	*d_omag, *d_ofreq;	/* n >> k shorts each                   */
+	uint32_t *d_acc, *d_last;	/* optional device words (NULL: none)   */
+	uint64_t n;			/* complex samples; 0 allowed           */
+	uint32_t phase0, dphase0;
+	uint64_t reserved;		/* 0                                    */
+} cordic_fmrx_job_c16;			/* 80 bytes                             */
+int	cordic_rxbank_create_c16(const cordic_plan *plan, const cordic_config *conv,
+		size_t njobs, const cordic_fmrx_job_c16 *jobs, cordic_rxbank **bank);
+int	cordic_rxbank_create_decim_c16(const cordic_plan *plan, const cordic_config *conv,
+		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
+		cordic_rxbank **bank);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with

@@ -717,13 +717,7 @@ class Plan:
         at the sum behind sample n-1.  work: device scratch of
         fm_mix_workspace(n) bytes (16-byte aligned), the caller's."""
         n = x.numel() if n is None else n
-        if work is None and n:
-            raise TypeError("work: a device buffer of fm_mix_workspace(n) bytes")
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and work.numel() * work.element_size() < self.fm_mix_workspace(n):
-            raise ValueError("work: %d bytes, fm_mix_workspace(%d) = %d"
-                             % (work.numel() * work.element_size(), n,
-                                self.fm_mix_workspace(n)))
+        _need_work(work, n, self.fm_mix_workspace, n)
         _check(lib().cordic_plan_fm_mix(
             self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
             _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
@@ -742,13 +736,7 @@ class Plan:
         caller's."""
         n = x.numel() if n is None else n
         _same16("cordic_plan_fm_mix16", x, y, ox, oy)
-        if work is None and n:
-            raise TypeError("work: a device buffer of fm_mix16_workspace(n) bytes")
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and work.numel() * work.element_size() < self.fm_mix16_workspace(n):
-            raise ValueError("work: %d bytes, fm_mix16_workspace(%d) = %d"
-                             % (work.numel() * work.element_size(), n,
-                                self.fm_mix16_workspace(n)))
+        _need_work(work, n, self.fm_mix16_workspace, n)
         _check(lib().cordic_plan_fm_mix16(
             self._h, n, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc),
             _ptr(x), _ptr(y), _ptr(ox), _ptr(oy), _ptr(work), _stream(stream)),
@@ -767,15 +755,7 @@ class Plan:
     def _fm_mix_decim(self, name, log2r, fcw, x, y, ox, oy, work, pm, n, phase0,
                       acc, stream):
         n = x.numel() if n is None else n
-        if work is None and n:
-            raise TypeError("work: a device buffer of %s_workspace(n, log2r) "
-                            "bytes" % name)
-        need = getattr(self, name + "_workspace")(n, log2r)
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and need and work.numel() * work.element_size() < need:
-            raise ValueError("work: %d bytes, %s_workspace(%d, %d) = %d"
-                             % (work.numel() * work.element_size(), name, n,
-                                log2r, need))
+        _need_work(work, n, getattr(self, name + "_workspace"), n, log2r)
         cname = "cordic_plan_" + name
         _check(getattr(lib(), cname)(
             self._h, n, log2r, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff,
@@ -831,14 +811,7 @@ class Plan:
     def _fm_rx(self, name, wsize, conv, fcw, x, y, mag, freq, work, pm, n,
                phase0, acc, dphase0, last, stream):
         n = x.numel() if n is None else n
-        if work is None and n:
-            raise TypeError("work: a device buffer of %s(conv, n) bytes"
-                            % wsize.__name__)
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and work.numel() * work.element_size() < wsize(conv, n):
-            raise ValueError("work: %d bytes, %s(conv, %d) = %d"
-                             % (work.numel() * work.element_size(),
-                                wsize.__name__, n, wsize(conv, n)))
+        _need_work(work, n, wsize, conv, n)
         _check(getattr(lib(), name)(
             self._h, conv.ref if conv is not None else None, n, _ptr(fcw),
             _ptr(pm), phase0 & 0xffffffff, _ptr(acc), _ptr(x), _ptr(y),
@@ -881,15 +854,7 @@ class Plan:
     def _fm_rx_decim(self, name, conv, log2r, fcw, x, y, mag, freq, work, pm,
                      n, phase0, acc, dphase0, last, stream):
         n = x.numel() if n is None else n
-        if work is None and n:
-            raise TypeError("work: a device buffer of %s_workspace(conv, n, "
-                            "log2r) bytes" % name)
-        need = getattr(self, name + "_workspace")(conv, n, log2r)
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and need and work.numel() * work.element_size() < need:
-            raise ValueError("work: %d bytes, %s_workspace(conv, %d, %d) = %d"
-                             % (work.numel() * work.element_size(), name, n,
-                                log2r, need))
+        _need_work(work, n, getattr(self, name + "_workspace"), conv, n, log2r)
         cname = "cordic_plan_" + name
         _check(getattr(lib(), cname)(
             self._h, conv.ref if conv is not None else None, n, log2r,
@@ -935,21 +900,14 @@ class Plan:
         return int(lib().cordic_plan_fm_rx_decim_c16_workspace(
             self._h, conv.ref if conv is not None else None, n, log2r))
 
-    def _fm_rx_c16(self, cname, need, args, conv, fcw, iq, mag, freq, work,
+    def _fm_rx_c16(self, cname, wsize, args, conv, fcw, iq, mag, freq, work,
                    pm, n, phase0, acc, dphase0, last, stream):
         _same16(cname, iq, mag, freq)
         n = iq.numel() // 2 if n is None else n
         if hasattr(iq, "numel") and iq.numel() < 2 * n:
             raise ValueError("%s: iq holds %d shorts, 2 n = %d"
                              % (cname, iq.numel(), 2 * n))
-        if work is None and n:
-            raise TypeError("%s: work, a device buffer of the _workspace "
-                            "query's bytes" % cname)
-        if hasattr(work, "numel") and hasattr(work, "element_size") \
-                and need(n) and work.numel() * work.element_size() < need(n):
-            raise ValueError("%s: work has %d bytes, %d needed"
-                             % (cname, work.numel() * work.element_size(),
-                                need(n)))
+        _need_work(work, n, wsize, conv, n, *args)
         _check(getattr(lib(), cname)(
             self._h, conv.ref if conv is not None else None, n, *args,
             _ptr(fcw), _ptr(pm), phase0 & 0xffffffff, _ptr(acc), _ptr(iq),
@@ -963,10 +921,9 @@ class Plan:
         delivers it; mag and freq are int16 tensors of n elements.  The bits
         of fm_rx16 on iq[0::2], iq[1::2].  n None: iq.numel() // 2.  work:
         fm_rx_c16_workspace(conv, n) bytes."""
-        self._fm_rx_c16("cordic_plan_fm_rx_c16",
-                        lambda k: self.fm_rx_c16_workspace(conv, k), (), conv,
-                        fcw, iq, mag, freq, work, pm, n, phase0, acc, dphase0,
-                        last, stream)
+        self._fm_rx_c16("cordic_plan_fm_rx_c16", self.fm_rx_c16_workspace, (),
+                        conv, fcw, iq, mag, freq, work, pm, n, phase0, acc,
+                        dphase0, last, stream)
 
     def fm_rx_decim_c16(self, conv, log2r, fcw, iq, mag, freq, work=None,
                         pm=None, n=None, phase0=0, acc=None, dphase0=0,
@@ -975,9 +932,9 @@ class Plan:
         I/Q (iq: 2 n shorts); mag and freq hold n >> log2r shorts.  work:
         fm_rx_decim_c16_workspace(conv, n, log2r) bytes."""
         self._fm_rx_c16("cordic_plan_fm_rx_decim_c16",
-                        lambda k: self.fm_rx_decim_c16_workspace(conv, k, log2r),
-                        (log2r,), conv, fcw, iq, mag, freq, work, pm, n,
-                        phase0, acc, dphase0, last, stream)
+                        self.fm_rx_decim_c16_workspace, (log2r,), conv, fcw, iq,
+                        mag, freq, work, pm, n, phase0, acc, dphase0, last,
+                        stream)
 
     @property
     def queue_info(self):
@@ -2093,6 +2050,21 @@ def _is16(t):
     return hasattr(t, "element_size") and t.element_size() == 2
 
 
+def _need_work(work, n, query, *args):
+    """The caller's scratch of an FM plan call of n samples: TypeError where
+    there is none and n > 0, ValueError where a tensor holds fewer bytes than
+    query(*args) answers -- the call's _workspace query, named in both."""
+    def asked():
+        return "%s(%s)" % (query.__name__, ", ".join(
+            str(a) if isinstance(a, int) else "conv" for a in args))
+    if work is None and n:
+        raise TypeError("work: a device buffer of %s bytes" % asked())
+    if hasattr(work, "numel") and hasattr(work, "element_size"):
+        have, need = work.numel() * work.element_size(), query(*args)
+        if have < need:
+            raise ValueError("work: %d bytes, %s = %d" % (have, asked(), need))
+
+
 def _same16(what, *tensors):
     # (None and raw addresses go through: the library answers for them)
     if any(hasattr(t, "element_size") and t.element_size() != 2 for t in tensors):
@@ -2302,6 +2274,10 @@ class _CFmMixJob(C.Structure):
 
 
 _FMMIX_KEYS = ("fcw", "pm", "x", "y", "ox", "oy", "n", "phase0", "acc")
+# a job key that is a tensor or a device address, and its field in the C struct
+_JOB_FIELDS = {"fcw": "d_fcw", "pm": "d_pm", "x": "d_xval", "y": "d_yval",
+               "ox": "d_oxval", "oy": "d_oyval", "iq": "d_iq", "mag": "d_omag",
+               "freq": "d_ofreq", "acc": "d_acc", "last": "d_last"}
 
 
 class _SpanBank:
@@ -2309,6 +2285,34 @@ class _SpanBank:
     handle self._h, through the C functions <_prefix>_info, _run and _destroy."""
 
     _prefix = None
+    _keys = _job = _create = _create_decim = None
+
+    def _open(self, plan, conv, jobs, log2r):
+        """Packs `jobs` -- tuples in the order of self._keys, or dicts with
+        those keys -- into an array of self._job (_JOB_FIELDS; n None:
+        fcw.numel()) and creates the handle: <_create>(plan, *conv, njobs,
+        jobs, &h), or <_create_decim> with log2r in front of njobs."""
+        jobs = [tuple(jb.get(k) for k in self._keys) if isinstance(jb, dict)
+                else tuple(jb) for jb in jobs]
+        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
+        arr = (self._job * max(1, len(jobs)))()
+        for k, jb in enumerate(jobs):
+            if len(jb) != len(self._keys):
+                raise ValueError("a job is (%s)" % ", ".join(self._keys))
+            for key, v in zip(self._keys, jb):
+                if key == "n":
+                    arr[k].n = jb[0].numel() if v is None else v
+                elif key in _JOB_FIELDS:
+                    setattr(arr[k], _JOB_FIELDS[key], _ptr(v))
+                else:           # phase0, dphase0
+                    setattr(arr[k], key, (v or 0) & 0xffffffff)
+        h = C.c_void_p()
+        name = self._create if log2r is None else self._create_decim
+        _check(getattr(lib(), name)(
+            getattr(plan, "_h", plan), *conv,
+            *(() if log2r is None else (log2r,)), len(jobs), arr, C.byref(h)),
+            name)
+        self._h = h
 
     def info(self):
         a, b = C.c_uint64(), C.c_uint32()
@@ -2348,32 +2352,10 @@ class MixBank(_SpanBank):
     _prefix = "cordic_mixbank"
     _create = "cordic_mixbank_create"
     _create_decim = "cordic_mixbank_create_decim"
+    _keys, _job = _FMMIX_KEYS, _CFmMixJob
 
     def __init__(self, plan, jobs, log2r=None):
-        jobs = [tuple(jb.get(k) for k in _FMMIX_KEYS) if isinstance(jb, dict)
-                else tuple(jb) for jb in jobs]
-        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
-        arr = (_CFmMixJob * max(1, len(jobs)))()
-        for k, (fcw, pm, x, y, ox, oy, n, phase0, acc) in enumerate(jobs):
-            arr[k].d_fcw = _ptr(fcw)
-            arr[k].d_pm = _ptr(pm)
-            arr[k].d_xval = _ptr(x)
-            arr[k].d_yval = _ptr(y)
-            arr[k].d_oxval = _ptr(ox)
-            arr[k].d_oyval = _ptr(oy)
-            arr[k].d_acc = _ptr(acc)
-            arr[k].n = fcw.numel() if n is None else n
-            arr[k].phase0 = (phase0 or 0) & 0xffffffff
-        h = C.c_void_p()
-        if log2r is None:
-            _check(getattr(lib(), self._create)(getattr(plan, "_h", plan),
-                                                len(jobs), arr, C.byref(h)),
-                   self._create)
-        else:
-            _check(getattr(lib(), self._create_decim)(
-                getattr(plan, "_h", plan), log2r, len(jobs), arr, C.byref(h)),
-                self._create_decim)
-        self._h = h
+        self._open(plan, (), jobs, log2r)
 
 
 class MixBank16(MixBank):
@@ -2421,36 +2403,10 @@ class RxBank(_SpanBank):
     _prefix = "cordic_rxbank"
     _create = "cordic_rxbank_create"
     _create_decim = "cordic_rxbank_create_decim"
+    _keys, _job = _FMRX_KEYS, _CFmRxJob
 
     def __init__(self, plan, conv, jobs, log2r=None):
-        jobs = [tuple(jb.get(k) for k in _FMRX_KEYS) if isinstance(jb, dict)
-                else tuple(jb) for jb in jobs]
-        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
-        arr = (_CFmRxJob * max(1, len(jobs)))()
-        for k, (fcw, pm, x, y, mag, freq, n, phase0, acc, dphase0, last) \
-                in enumerate(jobs):
-            arr[k].d_fcw = _ptr(fcw)
-            arr[k].d_pm = _ptr(pm)
-            arr[k].d_xval = _ptr(x)
-            arr[k].d_yval = _ptr(y)
-            arr[k].d_omag = _ptr(mag)
-            arr[k].d_ofreq = _ptr(freq)
-            arr[k].d_acc = _ptr(acc)
-            arr[k].d_last = _ptr(last)
-            arr[k].n = fcw.numel() if n is None else n
-            arr[k].phase0 = (phase0 or 0) & 0xffffffff
-            arr[k].dphase0 = (dphase0 or 0) & 0xffffffff
-        h = C.c_void_p()
-        cref = conv.ref if conv is not None else None
-        if log2r is None:
-            _check(getattr(lib(), self._create)(
-                getattr(plan, "_h", plan), cref, len(jobs), arr, C.byref(h)),
-                self._create)
-        else:
-            _check(getattr(lib(), self._create_decim)(
-                getattr(plan, "_h", plan), cref, log2r, len(jobs), arr,
-                C.byref(h)), self._create_decim)
-        self._h = h
+        self._open(plan, (conv.ref if conv is not None else None,), jobs, log2r)
 
 
 class RxBank16(RxBank):
@@ -2496,36 +2452,14 @@ class RxBankC16(_SpanBank):
     _prefix = "cordic_rxbank"
     _create = "cordic_rxbank_create_c16"
     _create_decim = "cordic_rxbank_create_decim_c16"
+    _keys, _job = _FMRX_C16_KEYS, _CFmRxJobC16
 
     def __init__(self, plan, conv, jobs, log2r=None):
-        jobs = [tuple(jb.get(k) for k in _FMRX_C16_KEYS) if isinstance(jb, dict)
-                else tuple(jb) for jb in jobs]
-        self._keep = (plan, jobs)   # the plan and the tensors behind the addresses
-        arr = (_CFmRxJobC16 * max(1, len(jobs)))()
-        for k, (fcw, pm, iq, mag, freq, n, phase0, acc, dphase0, last) \
-                in enumerate(jobs):
-            _same16(self._create, iq, mag, freq)
-            arr[k].d_fcw = _ptr(fcw)
-            arr[k].d_pm = _ptr(pm)
-            arr[k].d_iq = _ptr(iq)
-            arr[k].d_omag = _ptr(mag)
-            arr[k].d_ofreq = _ptr(freq)
-            arr[k].d_acc = _ptr(acc)
-            arr[k].d_last = _ptr(last)
-            arr[k].n = fcw.numel() if n is None else n
-            arr[k].phase0 = (phase0 or 0) & 0xffffffff
-            arr[k].dphase0 = (dphase0 or 0) & 0xffffffff
-        h = C.c_void_p()
-        cref = conv.ref if conv is not None else None
-        if log2r is None:
-            _check(getattr(lib(), self._create)(
-                getattr(plan, "_h", plan), cref, len(jobs), arr, C.byref(h)),
-                self._create)
-        else:
-            _check(getattr(lib(), self._create_decim)(
-                getattr(plan, "_h", plan), cref, log2r, len(jobs), arr,
-                C.byref(h)), self._create_decim)
-        self._h = h
+        for jb in jobs:
+            jb = tuple(jb.get(k) for k in _FMRX_C16_KEYS) if isinstance(jb, dict) \
+                else tuple(jb)
+            _same16(self._create, *jb[2:5])
+        self._open(plan, (conv.ref if conv is not None else None,), jobs, log2r)
 
 
 class _CHostStats(C.Structure):

@@ -1,7 +1,8 @@
 // cordic_abi.cpp -- the extern "C" surface declared in include/cordic_amd.h:
-// plans, job sets, FM mixer banks, the tuned FM receiver, the int16 calls, the config and stateless
-// wrappers.  (Table, quadratic and oscillator-bank handles:
-// cordic_abi_table.cpp; the clocked views: cordic_abi_clocked.cpp.)  Thin by
+// plans, job sets, the int16 calls, the config and stateless wrappers.  (The
+// plan-side FM layer -- mixer, receiver and their banks: cordic_abi_fm.cpp;
+// table, quadratic and oscillator-bank handles: cordic_abi_table.cpp; the
+// clocked views: cordic_abi_clocked.cpp.)  Thin by
 // design: argument checks, then the host layer (cordic_config.cpp) or the
 // device launchers (cordic_kernels.hip).
 #include <hip/hip_runtime_api.h>
@@ -12,14 +13,9 @@
 #include <new>
 #include <vector>
 
+#include "cordic_abi_plan.h"
 #include "cordic_amd.h"
-#include "cordic_bank_host.h"
 #include "cordic_devmem.h"
-#include "cordic_fm_mix.h"
-#include "cordic_fm_mix_bank.h"
-#include "cordic_fm_rx.h"
-#include "cordic_fm_rx_decim.h"
-#include "cordic_fm_rx_bank.h"
 #include "cordic_internal.h"
 #include "cordic_jobs_fused.h"
 #include "cordic_queue_ring.h"
@@ -33,24 +29,7 @@ constexpr size_t kSeedTableWords = 4 + 4096 * 4 + 4096 * 2
 constexpr size_t kDirTableWords = 4 + kDxMaxLevels * (6 + 2 * 4096 + 2 * 256);
 
 // ------------------------------------------------------------------- plans
-struct cordic_plan {
-	cordic_config cfg;
-	uint32_t *d_table = nullptr;	// device copy of the seed table
-	int m = 0, S = 0, nbuckets = 0, nleaves = 0;
-	DtInfo dt;			// direction tails behind the seeds (dt.n == 0: none)
-	uint32_t *d_dir = nullptr;	// direction tables for per-sample vectors
-	DxInfo dx;			// (dx.n == 0: none)
-	QueueRing queues;
-	// prologue images of the seeded kernels, per constant vector (round 5;
-	// cordic_internal.h: SeedImages -- internally locked, write-once slots)
-	SeedImages *images = nullptr;
-	// batch size from which the table-driven kernels serve (< 0: default)
-	std::atomic<long long> min_samples{-1};
-	// an int16 entry point has been called on this plan: cordic_plan_prepare
-	// then also builds the int16 container's image (its own slot)
-	mutable std::atomic<bool> io16_used{false};
-};
-
+// (the handle: cordic_abi_plan.h)
 int cordic_last_kernel(void) { return g_last_kernel; }
 
 int cordic_plan_create(const cordic_config *cfg, cordic_plan **plan)
@@ -138,866 +117,6 @@ int cordic_plan_mix(const cordic_plan *plan, size_t n, uint32_t phase0,
 	return launch_rotator(plan->cfg, Feed::PhaseArray_XYArray, j, stream);
 }
 
-// ---- the FM mixer: per-sample tuning words accumulated inside the rotator
-// (cordic_fm_mix.h)
-static int fm_mix_plan_ok(const cordic_plan *plan)
-{
-	if (!plan)
-		return CORDIC_ERR_ARGS;
-	if (plan->cfg.mode != CORDIC_P2R && plan->cfg.mode != CORDIC_SP2R)
-		return CORDIC_ERR_MODE;
-	return config_sane(plan->cfg) ? CORDIC_OK : CORDIC_ERR_ARGS;
-}
-
-static bool fm_mix_fused(const cordic_plan *plan)
-{
-	return fmx_is_fused(plan->cfg, plan->d_dir, plan->dx);
-}
-
-size_t cordic_plan_fm_mix_workspace(const cordic_plan *plan, size_t n)
-{
-	if (fm_mix_plan_ok(plan) != CORDIC_OK)
-		return 0;
-	return fmx_work_bytes(fm_mix_fused(plan), n);
-}
-
-int cordic_plan_fm_mix_info(const cordic_plan *plan, int32_t *fused, int32_t *tile)
-{
-	if (int rc = fm_mix_plan_ok(plan))
-		return rc;
-	const bool f = fm_mix_fused(plan);
-	if (fused)
-		*fused = f ? 1 : 0;
-	if (tile)
-		*tile = f ? (int32_t)kFmxPass : 0;
-	return CORDIC_OK;
-}
-
-int cordic_plan_fm_mix(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
-		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
-		const int32_t *d_xval, const int32_t *d_yval, int32_t *d_oxval,
-		int32_t *d_oyval, void *d_work, void *stream)
-{
-	if (int rc = fm_mix_plan_ok(plan))
-		return rc;
-	if (n == 0)
-		return CORDIC_OK;
-	const bool fused = fm_mix_fused(plan);
-	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval,
-			d_oyval, 4, d_work, fmx_work_bytes(fused, n)))
-		return rc;
-	if (fused)
-		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm,
-			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, 4, d_work, stream);
-	// the fallback: the phases into the workspace, behind the accumulator's own
-	// scratch, and the rotator on them
-	uint32_t *ph = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d_work)
-			+ kFmxPhaseAt);
-	if (int rc = cordic_phase_accumulate(n, d_fcw, d_pm, phase0, d_acc, ph, d_work,
-			stream))
-		return rc;
-	return cordic_plan_p2r(plan, n, d_xval, d_yval, ph, d_oxval, d_oyval, stream);
-}
-
-// ---- the same on int16 I/Q arrays.  16-bit containers: do the core's samples
-// (and phase words) fit?
-static int fits16(const cordic_config &c, bool phase_array)
-{
-	if (c.iw > 16 || c.ow > 16 || (phase_array && c.pw > 16))
-		return CORDIC_ERR_CONTAINER;
-	return CORDIC_OK;
-}
-
-// the plan, its mode, then the container (the tuning words stay 32-bit: any PW)
-static int fm_mix16_plan_ok(const cordic_plan *plan)
-{
-	if (int rc = fm_mix_plan_ok(plan))
-		return rc;
-	return fits16(plan->cfg, false);
-}
-
-static bool fm_mix16_fused(const cordic_plan *plan)
-{
-	return fmx_is_fused16(plan->cfg, plan->d_dir, plan->dx);
-}
-
-static size_t fm_mix16_work_bytes(const cordic_plan *plan, size_t n)
-{
-	return fmx16_work_bytes(fm_mix16_fused(plan), fm_mix_fused(plan), n);
-}
-
-size_t cordic_plan_fm_mix16_workspace(const cordic_plan *plan, size_t n)
-{
-	if (fm_mix16_plan_ok(plan) != CORDIC_OK)
-		return 0;
-	return fm_mix16_work_bytes(plan, n);
-}
-
-int cordic_plan_fm_mix16(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
-		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
-		const int16_t *d_xval, const int16_t *d_yval, int16_t *d_oxval,
-		int16_t *d_oyval, void *d_work, void *stream)
-{
-	if (int rc = fm_mix16_plan_ok(plan))
-		return rc;
-	if (n == 0)
-		return CORDIC_OK;
-	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval,
-			d_oyval, 2, d_work, fm_mix16_work_bytes(plan, n)))
-		return rc;
-	if (fm_mix16_fused(plan))
-		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm,
-			phase0, d_acc, d_xval, d_yval, d_oxval, d_oyval, 2, d_work, stream);
-	// the fallback: the 32-bit call on widened copies, all of it in d_work --
-	// [its workspace | x | y | ox | oy] -- and the low halves of what it wrote
-	unsigned char *w = static_cast<unsigned char *>(d_work);
-	const size_t at = fmx_work_bytes(fm_mix_fused(plan), n), each = fmx16_array_bytes(n);
-	int32_t *wx = reinterpret_cast<int32_t *>(w + at);
-	int32_t *wy = reinterpret_cast<int32_t *>(w + at + each);
-	int32_t *wox = reinterpret_cast<int32_t *>(w + at + 2 * each);
-	int32_t *woy = reinterpret_cast<int32_t *>(w + at + 3 * each);
-	if (int rc = launch_fmx_widen(n, d_xval, d_yval, wx, wy, stream))
-		return rc;
-	if (int rc = cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc, wx, wy, wox,
-			woy, d_work, stream))
-		return rc;
-	return launch_fmx_narrow(n, wox, woy, d_oxval, d_oyval, stream);
-}
-
-// ---- the decimating mixer: integrate-and-dump by 2^log2r behind the rotator
-// (cordic_fm_mix.h), on either container.  CORDIC_FMXD_FALLBACK=1 in the
-// environment (read at every single call and workspace query; a test and A/B
-// knob) sends a fused plan's single call through the fallback.  The workspace
-// grows with it and a call cannot see the size of the caller's buffer, so it
-// has to be set before the query as well as before the call, as
-// tools/bench_fm_mix_decim.py does.  Banks ignore it.
-static bool fm_mix_decim_fused(const cordic_plan *plan, bool io16)
-{
-	const char *e = std::getenv("CORDIC_FMXD_FALLBACK");
-	if (e && e[0] == '1')
-		return false;
-	return io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan);
-}
-
-// a plan that the call accepts; 0 where the call would fail
-static size_t fm_mix_decim_work_bytes(const cordic_plan *plan, bool io16, bool fused,
-		size_t n, uint32_t log2r)
-{
-	const size_t mix = io16 ? fm_mix16_work_bytes(plan, n)
-		: fmx_work_bytes(fm_mix_fused(plan), n);
-	if (!fmxd_shape_ok(n, log2r))
-		return 0;
-	return log2r ? fmxd_work_bytes(fused, mix, n, io16 ? 2 : 4) : mix;
-}
-
-static int fm_mix_decim(const cordic_plan *plan, bool io16, size_t n, uint32_t log2r,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
-		const void *d_xval, const void *d_yval, void *d_oxval, void *d_oyval,
-		void *d_work, void *stream, bool fused)
-{
-	if (!fmxd_shape_ok(n, log2r))
-		return CORDIC_ERR_ARGS;
-	if (log2r == 0 || n == 0) {	// the mixer itself: its bits, its launches
-		if (io16)
-			return cordic_plan_fm_mix16(plan, n, d_fcw, d_pm, phase0, d_acc,
-				static_cast<const int16_t *>(d_xval), static_cast<const int16_t *>(d_yval),
-				static_cast<int16_t *>(d_oxval), static_cast<int16_t *>(d_oyval), d_work,
-				stream);
-		return cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc,
-			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
-			static_cast<int32_t *>(d_oxval), static_cast<int32_t *>(d_oyval), d_work,
-			stream);
-	}
-	const size_t esize = io16 ? 2 : 4;
-	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_oxval, d_oyval,
-			esize, d_work, fm_mix_decim_work_bytes(plan, io16, fused, n, log2r), log2r))
-		return rc;
-	if (fused)
-		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm, phase0,
-			d_acc, d_xval, d_yval, d_oxval, d_oyval, esize, d_work, stream, log2r);
-	// the fallback: the mixer's call into two full-rate arrays behind its own
-	// workspace, then the sums
-	unsigned char *w = static_cast<unsigned char *>(d_work);
-	const size_t at = io16 ? fm_mix16_work_bytes(plan, n)
-		: fmx_work_bytes(fm_mix_fused(plan), n);
-	void *tx = w + at, *ty = w + at + fmxd_array_bytes(n, esize);
-	if (int rc = fm_mix_decim(plan, io16, n, 0, d_fcw, d_pm, phase0, d_acc, d_xval,
-			d_yval, tx, ty, d_work, stream, false))
-		return rc;
-	return launch_fmx_decimate(n, log2r, esize, tx, ty, d_oxval, d_oyval, stream);
-}
-
-size_t cordic_plan_fm_mix_decim_workspace(const cordic_plan *plan, size_t n, uint32_t log2r)
-{
-	if (fm_mix_plan_ok(plan) != CORDIC_OK)
-		return 0;
-	return fm_mix_decim_work_bytes(plan, false, fm_mix_decim_fused(plan, false), n, log2r);
-}
-
-size_t cordic_plan_fm_mix_decim16_workspace(const cordic_plan *plan, size_t n,
-		uint32_t log2r)
-{
-	if (fm_mix16_plan_ok(plan) != CORDIC_OK)
-		return 0;
-	return fm_mix_decim_work_bytes(plan, true, fm_mix_decim_fused(plan, true), n, log2r);
-}
-
-int cordic_plan_fm_mix_decim(const cordic_plan *plan, size_t n, uint32_t log2r,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
-		const int32_t *d_xval, const int32_t *d_yval, int32_t *d_oxval,
-		int32_t *d_oyval, void *d_work, void *stream)
-{
-	if (int rc = fm_mix_plan_ok(plan))
-		return rc;
-	return fm_mix_decim(plan, false, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
-		d_oxval, d_oyval, d_work, stream, fm_mix_decim_fused(plan, false));
-}
-
-int cordic_plan_fm_mix_decim16(const cordic_plan *plan, size_t n, uint32_t log2r,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
-		const int16_t *d_xval, const int16_t *d_yval, int16_t *d_oxval,
-		int16_t *d_oyval, void *d_work, void *stream)
-{
-	if (int rc = fm_mix16_plan_ok(plan))
-		return rc;
-	return fm_mix_decim(plan, true, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
-		d_oxval, d_oyval, d_work, stream, fm_mix_decim_fused(plan, true));
-}
-
-// ---- FM mixer banks: many of those jobs in two launches
-// (cordic_fm_mix_bank.h)
-struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
-	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
-	bool	io16 = false;			// the jobs' sample arrays hold int16
-	uint32_t passes = 0;
-	uint32_t log2r = 0;			// > 0: a decimating bank
-	SpanTable<MixSpan> spans;		// fused
-};
-
-// The create of the two plan-side banks (mixer, receiver), 32- and 16-bit:
-// `jobs` is the bank's view of either job struct (MixJobs, RxJobs), `core_ok`
-// the check of the plan (and converter), `fused` the whole bank's path,
-// `work_bytes` a job's workspace one by one, `finish` what a fused bank still
-// needs behind its span table.  TR (MixBankTraits, RxBankTraits, next to the
-// views): the job check, the span rule (of the view: a decimating receiver
-// bank's halo follows its k), the knobs' names, the blocks per CU.
-// The checks come in this order, each bank's documented order of status codes.
-template <typename TR, typename Bank, typename Jobs, typename Ok, typename Fused,
-	typename Work, typename Finish>
-static int plan_bank_create(const cordic_plan *plan, size_t njobs, Jobs jobs, Bank **bank,
-		Ok core_ok, Fused fused, Work work_bytes, void (*destroy)(Bank *),
-		Finish finish)
-{
-	const bool io16 = jobs.j16 != nullptr;	// (no jobs at all: the 32-bit rules)
-	if (!bank || (njobs && jobs.none()))
-		return CORDIC_ERR_ARGS;
-	if (int rc = core_ok(io16))
-		return rc;
-	if (njobs >= ((size_t)1 << 28) || !TR::jobs_valid(njobs, jobs))
-		return CORDIC_ERR_ARGS;
-	(void)hipGetLastError();	// (a stale error is not this call's)
-	// the handle keeps its jobs in the 32-bit struct, whatever the container
-	typedef typename decltype(Bank::jobs)::value_type Job;
-	std::vector<Job> wide;
-	const Job *flat = jobs.j32;
-	if (io16) {
-		wide.reserve(njobs);
-		for (size_t k = 0; k < njobs; k++)
-			wide.push_back(jobs[k]);
-		flat = wide.data();
-	}
-	Bank *b = nullptr;
-	if (int rc = bank_begin(njobs, flat, fused(io16),
-			[&](size_t n) { return work_bytes(io16, n); }, &b))
-		return rc;
-	b->plan = plan;
-	b->io16 = io16;
-	int rc = CORDIC_OK;
-	if (b->fused) {
-		const SpanRule rule = TR::rule_of(jobs);
-		uint64_t passes = 0;
-		for (size_t k = 0; k < njobs; k++)
-			passes += span_units_of(rule, jobs.n(k));
-		rc = span_table_build(&b->spans, TR::passes, TR::max_spans, rule, passes,
-			b->cus, TR::blocks_per_cu, njobs, jobs, &b->passes);
-	}
-	if (!rc)
-		rc = finish(b);
-	if (rc) {
-		destroy(b);
-		return rc;
-	}
-	*bank = b;
-	return CORDIC_OK;
-}
-
-// both creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h)
-static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
-		cordic_mixbank **bank)
-{
-	return plan_bank_create<MixBankTraits>(plan, njobs, jobs, bank,
-		[&](bool io16) { return io16 ? fm_mix16_plan_ok(plan) : fm_mix_plan_ok(plan); },
-		[&](bool io16) { return io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan); },
-		[&](bool io16, size_t n) {
-			return fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r);
-		}, cordic_mixbank_destroy, [&](cordic_mixbank *b) {
-			b->log2r = jobs.log2r;
-			return CORDIC_OK;
-		});
-}
-
-int cordic_mixbank_create(const cordic_plan *plan, size_t njobs,
-		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
-{
-	return mixbank_create(plan, njobs, jobs, bank);
-}
-
-int cordic_mixbank_create16(const cordic_plan *plan, size_t njobs,
-		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
-{
-	return mixbank_create(plan, njobs, jobs, bank);
-}
-
-int cordic_mixbank_create_decim(const cordic_plan *plan, uint32_t log2r, size_t njobs,
-		const cordic_fmmix_job *jobs, cordic_mixbank **bank)
-{
-	return mixbank_create(plan, njobs, MixJobs(jobs, log2r), bank);
-}
-
-int cordic_mixbank_create_decim16(const cordic_plan *plan, uint32_t log2r, size_t njobs,
-		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
-{
-	return mixbank_create(plan, njobs, MixJobs(jobs, log2r), bank);
-}
-
-void cordic_mixbank_destroy(cordic_mixbank *bank)
-{
-	if (!bank)
-		return;
-	bank->spans.free();
-	dev_free(bank->d_work);
-	delete bank;
-}
-
-int cordic_mixbank_info(const cordic_mixbank *bank, uint64_t *samples,
-		uint32_t *spans, int32_t *fused, int32_t *tile)
-{
-	if (!bank)
-		return CORDIC_ERR_ARGS;
-	if (samples) *samples = bank->samples;
-	if (spans) *spans = bank->spans.nspans;
-	if (fused) *fused = bank->fused ? 1 : 0;
-	if (tile) *tile = bank->fused ? (int32_t)(bank->passes * kFmxbRule.unit) : 0;
-	return CORDIC_OK;
-}
-
-int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
-{
-	if (!bank)
-		return CORDIC_ERR_ARGS;
-	(void)hipGetLastError();
-	const cordic_plan *plan = bank->plan;
-	return bank_run(*bank, [&] {
-		const SpanTable<MixSpan> &t = bank->spans;
-		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, t.d_spans, t.nspans,
-			t.start(), t.part(), bank->cus, bank->io16, stream, bank->log2r);
-	}, [&](const cordic_fmmix_job &jb) {
-		// (log2r 0: the mixer's own call, cordic_plan_fm_mix or _mix16)
-		return fm_mix_decim(plan, bank->io16, (size_t)jb.n, bank->log2r, jb.d_fcw,
-			jb.d_pm, jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval,
-			bank->d_work, stream, false);
-	});
-}
-
-// ---- the tuned FM receiver: that mixer and the FM discriminator in one kernel
-// (cordic_fm_rx.h).  The status codes are those of the two calls, the mixer's
-// first: the plan (ARGS, MODE), then the converter (ARGS, MODE, ARGS) and, for
-// the 16-bit form, the plan's container, then the converter's.
-static int fm_rx_ok(const cordic_plan *plan, const cordic_config *conv, bool io16)
-{
-	if (!plan || !conv)
-		return CORDIC_ERR_ARGS;
-	if (int rc = fm_mix_plan_ok(plan))
-		return rc;
-	if (int rc = fmd_check_core(conv))
-		return rc;
-	if (!io16)
-		return CORDIC_OK;
-	if (int rc = fits16(plan->cfg, false))
-		return rc;
-	return fits16(*conv, true);
-}
-
-static bool fm_rx_fused(const cordic_plan *plan, const cordic_config *conv, bool io16)
-{
-	return (io16 ? fm_mix16_fused(plan) : fm_mix_fused(plan))
-		&& fmrx_conv_is_fused(*conv);
-}
-
-static size_t fm_rx_mix_bytes(const cordic_plan *plan, size_t n, bool io16)
-{
-	return io16 ? fm_mix16_work_bytes(plan, n) : fmx_work_bytes(fm_mix_fused(plan), n);
-}
-
-static size_t fm_rx_work_bytes(const cordic_plan *plan, const cordic_config *conv,
-		size_t n, bool io16)
-{
-	return fmrx_work_bytes(fm_rx_fused(plan, conv, io16), fm_rx_mix_bytes(plan, n, io16),
-		n, io16 ? 2 : 4);
-}
-
-static int fm_rx_info(const cordic_plan *plan, const cordic_config *conv,
-		int32_t *fused, int32_t *tile, bool io16)
-{
-	if (int rc = fm_rx_ok(plan, conv, io16))
-		return rc;
-	const bool f = fm_rx_fused(plan, conv, io16);
-	if (fused)
-		*fused = f ? 1 : 0;
-	if (tile)
-		*tile = f ? (int32_t)kFmrxPass : 0;
-	return CORDIC_OK;
-}
-
-static int fm_rx(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const void *d_xval, const void *d_yval, uint32_t dphase0,
-		uint32_t *d_last, void *d_omag, void *d_ofreq, void *d_work, void *stream,
-		bool io16)
-{
-	if (int rc = fm_rx_ok(plan, conv, io16))
-		return rc;
-	if (n == 0)
-		return CORDIC_OK;
-	const size_t es = io16 ? 2 : 4;
-	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_last, d_omag,
-			d_ofreq, es, d_work, fm_rx_work_bytes(plan, conv, n, io16)))
-		return rc;
-	if (fm_rx_fused(plan, conv, io16))
-		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
-			phase0, d_acc, d_xval, d_yval, dphase0, d_last, d_omag, d_ofreq, es,
-			d_work, stream);
-	// the fallback: the mixer into two arrays inside d_work -- [its workspace |
-	// tuned x | tuned y | the discriminator's workspace] -- and the
-	// discriminator from them
-	unsigned char *w = static_cast<unsigned char *>(d_work);
-	const size_t at = fm_rx_mix_bytes(plan, n, io16), each = fmrx_array_bytes(n, es);
-	void *tx = w + at, *ty = w + at + each, *dw = w + at + 2 * each;
-	if (io16) {
-		if (int rc = cordic_plan_fm_mix16(plan, n, d_fcw, d_pm, phase0, d_acc,
-				static_cast<const int16_t *>(d_xval),
-				static_cast<const int16_t *>(d_yval), static_cast<int16_t *>(tx),
-				static_cast<int16_t *>(ty), d_work, stream))
-			return rc;
-		return cordic_fm_demod16(conv, n, static_cast<const int16_t *>(tx),
-			static_cast<const int16_t *>(ty), dphase0, d_last,
-			static_cast<int16_t *>(d_omag), static_cast<int16_t *>(d_ofreq), dw, stream);
-	}
-	if (int rc = cordic_plan_fm_mix(plan, n, d_fcw, d_pm, phase0, d_acc,
-			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
-			static_cast<int32_t *>(tx), static_cast<int32_t *>(ty), d_work, stream))
-		return rc;
-	return cordic_fm_demod(conv, n, static_cast<const int32_t *>(tx),
-		static_cast<const int32_t *>(ty), dphase0, d_last,
-		static_cast<int32_t *>(d_omag), static_cast<int32_t *>(d_ofreq), dw, stream);
-}
-
-size_t cordic_plan_fm_rx_workspace(const cordic_plan *plan, const cordic_config *conv,
-		size_t n)
-{
-	return fm_rx_ok(plan, conv, false) == CORDIC_OK
-		? fm_rx_work_bytes(plan, conv, n, false) : 0;
-}
-
-size_t cordic_plan_fm_rx16_workspace(const cordic_plan *plan, const cordic_config *conv,
-		size_t n)
-{
-	return fm_rx_ok(plan, conv, true) == CORDIC_OK
-		? fm_rx_work_bytes(plan, conv, n, true) : 0;
-}
-
-int cordic_plan_fm_rx_info(const cordic_plan *plan, const cordic_config *conv,
-		int32_t *fused, int32_t *tile)
-{
-	return fm_rx_info(plan, conv, fused, tile, false);
-}
-
-int cordic_plan_fm_rx16_info(const cordic_plan *plan, const cordic_config *conv,
-		int32_t *fused, int32_t *tile)
-{
-	return fm_rx_info(plan, conv, fused, tile, true);
-}
-
-int cordic_plan_fm_rx(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		uint32_t dphase0, uint32_t *d_last, int32_t *d_omag, int32_t *d_ofreq,
-		void *d_work, void *stream)
-{
-	return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
-		d_last, d_omag, d_ofreq, d_work, stream, false);
-}
-
-int cordic_plan_fm_rx16(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int16_t *d_xval, const int16_t *d_yval,
-		uint32_t dphase0, uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq,
-		void *d_work, void *stream)
-{
-	return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
-		d_last, d_omag, d_ofreq, d_work, stream, true);
-}
-
-// ---- the decimating receiver: the integrate-and-dump by 2^log2r between that
-// mixer and the discriminator (cordic_fm_rx_decim.h), on either container.
-// Fused where the receiver is.  CORDIC_FMRXD_FALLBACK=1 in the environment
-// (read at every single call and workspace query, as CORDIC_FMXD_FALLBACK is:
-// set it before both) sends a fused pair's single call through the fallback.
-static bool fm_rx_decim_fused(const cordic_plan *plan, const cordic_config *conv,
-		bool io16)
-{
-	const char *e = std::getenv("CORDIC_FMRXD_FALLBACK");
-	if (e && e[0] == '1')
-		return false;
-	return fm_rx_fused(plan, conv, io16);
-}
-
-// the decimating mixer call's own workspace, as its _workspace query answers
-static size_t fm_rx_decim_mix_bytes(const cordic_plan *plan, size_t n, uint32_t log2r,
-		bool io16)
-{
-	return fm_mix_decim_work_bytes(plan, io16, fm_mix_decim_fused(plan, io16), n, log2r);
-}
-
-// a pair that the call accepts; 0 where the call would fail
-static size_t fm_rx_decim_work_bytes(const cordic_plan *plan, const cordic_config *conv,
-		size_t n, uint32_t log2r, bool io16)
-{
-	if (!fmxd_shape_ok(n, log2r))
-		return 0;
-	if (!log2r)
-		return fm_rx_work_bytes(plan, conv, n, io16);
-	return fmrxd_work_bytes(fm_rx_decim_fused(plan, conv, io16),
-		fm_rx_decim_mix_bytes(plan, n, log2r, io16), n, log2r, io16 ? 2 : 4);
-}
-
-static int fm_rx_decim(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const void *d_xval, const void *d_yval, uint32_t dphase0,
-		uint32_t *d_last, void *d_omag, void *d_ofreq, void *d_work, void *stream,
-		bool io16)
-{
-	if (int rc = fm_rx_ok(plan, conv, io16))
-		return rc;
-	if (!fmxd_shape_ok(n, log2r))
-		return CORDIC_ERR_ARGS;
-	if (log2r == 0 || n == 0)	// the receiver itself: its bits, its launches
-		return fm_rx(plan, conv, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval, dphase0,
-			d_last, d_omag, d_ofreq, d_work, stream, io16);
-	const size_t es = io16 ? 2 : 4;
-	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_xval, d_yval, d_last, d_omag,
-			d_ofreq, es, d_work, fm_rx_decim_work_bytes(plan, conv, n, log2r, io16),
-			log2r))
-		return rc;
-	if (fm_rx_decim_fused(plan, conv, io16))
-		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
-			phase0, d_acc, d_xval, d_yval, dphase0, d_last, d_omag, d_ofreq, es,
-			d_work, stream, log2r);
-	// the fallback: the two calls of the definition -- [the decimating mixer's
-	// workspace | T_x | T_y | the discriminator's workspace]
-	unsigned char *w = static_cast<unsigned char *>(d_work);
-	const size_t m = n >> log2r;
-	const size_t at = fm_rx_decim_mix_bytes(plan, n, log2r, io16);
-	const size_t each = fmrx_array_bytes(m, es);
-	void *tx = w + at, *ty = w + at + each, *dw = w + at + 2 * each;
-	if (io16) {
-		if (int rc = cordic_plan_fm_mix_decim16(plan, n, log2r, d_fcw, d_pm, phase0, d_acc,
-				static_cast<const int16_t *>(d_xval),
-				static_cast<const int16_t *>(d_yval), static_cast<int16_t *>(tx),
-				static_cast<int16_t *>(ty), d_work, stream))
-			return rc;
-		return cordic_fm_demod16(conv, m, static_cast<const int16_t *>(tx),
-			static_cast<const int16_t *>(ty), dphase0, d_last,
-			static_cast<int16_t *>(d_omag), static_cast<int16_t *>(d_ofreq), dw, stream);
-	}
-	if (int rc = cordic_plan_fm_mix_decim(plan, n, log2r, d_fcw, d_pm, phase0, d_acc,
-			static_cast<const int32_t *>(d_xval), static_cast<const int32_t *>(d_yval),
-			static_cast<int32_t *>(tx), static_cast<int32_t *>(ty), d_work, stream))
-		return rc;
-	return cordic_fm_demod(conv, m, static_cast<const int32_t *>(tx),
-		static_cast<const int32_t *>(ty), dphase0, d_last,
-		static_cast<int32_t *>(d_omag), static_cast<int32_t *>(d_ofreq), dw, stream);
-}
-
-size_t cordic_plan_fm_rx_decim_workspace(const cordic_plan *plan,
-		const cordic_config *conv, size_t n, uint32_t log2r)
-{
-	return fm_rx_ok(plan, conv, false) == CORDIC_OK
-		? fm_rx_decim_work_bytes(plan, conv, n, log2r, false) : 0;
-}
-
-size_t cordic_plan_fm_rx_decim16_workspace(const cordic_plan *plan,
-		const cordic_config *conv, size_t n, uint32_t log2r)
-{
-	return fm_rx_ok(plan, conv, true) == CORDIC_OK
-		? fm_rx_decim_work_bytes(plan, conv, n, log2r, true) : 0;
-}
-
-int cordic_plan_fm_rx_decim(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int32_t *d_xval, const int32_t *d_yval,
-		uint32_t dphase0, uint32_t *d_last, int32_t *d_omag, int32_t *d_ofreq,
-		void *d_work, void *stream)
-{
-	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
-		dphase0, d_last, d_omag, d_ofreq, d_work, stream, false);
-}
-
-int cordic_plan_fm_rx_decim16(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int16_t *d_xval, const int16_t *d_yval,
-		uint32_t dphase0, uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq,
-		void *d_work, void *stream)
-{
-	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
-		dphase0, d_last, d_omag, d_ofreq, d_work, stream, true);
-}
-
-// ---- the receivers on INTERLEAVED int16 I/Q (the *_c16 forms): the *16 twins
-// with d_iq in the place of d_xval / d_yval.  Fused where the twin is, with the
-// twin's launches and workspace (the <30, IoC16> instances of launch 2);
-// otherwise one split launch into two arrays behind the twin's workspace, then
-// the twin itself.
-static size_t fm_rx_c16_work_bytes(const cordic_plan *plan, const cordic_config *conv,
-		size_t n)
-{
-	return fmrx_c16_work_bytes(fm_rx_fused(plan, conv, true),
-		fm_rx_work_bytes(plan, conv, n, true), n);
-}
-
-static size_t fm_rx_decim_c16_work_bytes(const cordic_plan *plan,
-		const cordic_config *conv, size_t n, uint32_t log2r)
-{
-	if (!fmxd_shape_ok(n, log2r))
-		return 0;
-	if (!log2r)
-		return fm_rx_c16_work_bytes(plan, conv, n);
-	return fmrx_c16_work_bytes(fm_rx_decim_fused(plan, conv, true),
-		fm_rx_decim_work_bytes(plan, conv, n, log2r, true), n);
-}
-
-// both single calls (log2r 0: the plain form, which CORDIC_FMRXD_FALLBACK does
-// not reach)
-static int fm_rx_decim_c16(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0, uint32_t *d_last,
-		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
-{
-	if (int rc = fm_rx_ok(plan, conv, true))
-		return rc;
-	if (!fmxd_shape_ok(n, log2r))
-		return CORDIC_ERR_ARGS;
-	if (n == 0)
-		return CORDIC_OK;
-	const bool fused = log2r ? fm_rx_decim_fused(plan, conv, true)
-		: fm_rx_fused(plan, conv, true);
-	const size_t twin = log2r ? fm_rx_decim_work_bytes(plan, conv, n, log2r, true)
-		: fm_rx_work_bytes(plan, conv, n, true);
-	if (int rc = fmrx_check_call(n, d_fcw, d_pm, d_acc, d_iq, nullptr, d_last, d_omag,
-			d_ofreq, 2, d_work, fmrx_c16_work_bytes(fused, twin, n), log2r, true))
-		return rc;
-	if (fused)
-		return launch_fm_rx(plan->cfg, plan->d_dir, plan->dx, *conv, n, d_fcw, d_pm,
-			phase0, d_acc, d_iq, nullptr, dphase0, d_last, d_omag, d_ofreq, 2, d_work,
-			stream, log2r, true);
-	// the fallback: [the twin's workspace | x | y], then the twin from them
-	unsigned char *w = static_cast<unsigned char *>(d_work);
-	const size_t at = (twin + 15) & ~(size_t)15, each = fmrx_array_bytes(n, 2);
-	int16_t *x = reinterpret_cast<int16_t *>(w + at);
-	int16_t *y = reinterpret_cast<int16_t *>(w + at + each);
-	if (int rc = launch_fmrx_split_c16(n, d_iq, x, y, stream))
-		return rc;
-	return fm_rx_decim(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, x, y, dphase0,
-		d_last, d_omag, d_ofreq, d_work, stream, true);
-}
-
-size_t cordic_plan_fm_rx_c16_workspace(const cordic_plan *plan, const cordic_config *conv,
-		size_t n)
-{
-	return fm_rx_ok(plan, conv, true) == CORDIC_OK
-		? fm_rx_c16_work_bytes(plan, conv, n) : 0;
-}
-
-int cordic_plan_fm_rx_c16_info(const cordic_plan *plan, const cordic_config *conv,
-		int32_t *fused, int32_t *tile)
-{
-	return fm_rx_info(plan, conv, fused, tile, true);
-}
-
-int cordic_plan_fm_rx_c16(const cordic_plan *plan, const cordic_config *conv, size_t n,
-		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
-		uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0, uint32_t *d_last,
-		int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
-{
-	return fm_rx_decim_c16(plan, conv, n, 0, d_fcw, d_pm, phase0, d_acc, d_iq, dphase0,
-		d_last, d_omag, d_ofreq, d_work, stream);
-}
-
-size_t cordic_plan_fm_rx_decim_c16_workspace(const cordic_plan *plan,
-		const cordic_config *conv, size_t n, uint32_t log2r)
-{
-	return fm_rx_ok(plan, conv, true) == CORDIC_OK
-		? fm_rx_decim_c16_work_bytes(plan, conv, n, log2r) : 0;
-}
-
-int cordic_plan_fm_rx_decim_c16(const cordic_plan *plan, const cordic_config *conv,
-		size_t n, uint32_t log2r, const uint32_t *d_fcw, const uint32_t *d_pm,
-		uint32_t phase0, uint32_t *d_acc, const int16_t *d_iq, uint32_t dphase0,
-		uint32_t *d_last, int16_t *d_omag, int16_t *d_ofreq, void *d_work, void *stream)
-{
-	return fm_rx_decim_c16(plan, conv, n, log2r, d_fcw, d_pm, phase0, d_acc, d_iq,
-		dphase0, d_last, d_omag, d_ofreq, d_work, stream);
-}
-
-// ---- receiver banks: many of those jobs in two launches (cordic_fm_rx_bank.h)
-struct cordic_rxbank : BankHandle<cordic_fmrx_job> {
-	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
-	cordic_config conv;			// a copy
-	bool	io16 = false;			// the jobs' sample arrays hold int16
-	bool	iq = false;			// ... and d_xval is interleaved I/Q (_c16)
-	uint32_t passes = 0;
-	uint32_t log2r = 0;			// > 0: a decimating bank
-	SpanTable<RxSpan> spans;		// fused
-	uint32_t *d_conv = nullptr;		// fused: conv's kernel parameters
-};
-
-// all six creates: `jobs` is either job struct with the bank's k (RxJobs,
-// cordic_fm_rx_bank.h); a fused bank uploads the converter's kernel parameters
-// behind its span table.  A bank that runs one by one keeps the fallback's
-// workspace at its largest, whatever the A/B knobs say at run.
-static int rxbank_create(const cordic_plan *plan, const cordic_config *conv,
-		size_t njobs, RxJobs jobs, cordic_rxbank **bank)
-{
-	return plan_bank_create<RxBankTraits>(plan, njobs, jobs, bank,
-		[&](bool io16) { return fm_rx_ok(plan, conv, io16); },
-		[&](bool io16) { return fm_rx_fused(plan, conv, io16); },
-		[&](bool io16, size_t n) {
-			const size_t twin = !jobs.log2r ? fm_rx_work_bytes(plan, conv, n, io16)
-				: fmrxd_work_bytes(false,
-					fm_mix_decim_work_bytes(plan, io16, false, n, jobs.log2r), n,
-					jobs.log2r, io16 ? 2 : 4);
-			// (interleaved jobs: the split arrays behind it)
-			return jobs.iq ? fmrx_c16_work_bytes(false, twin, n) : twin;
-		}, cordic_rxbank_destroy, [&](cordic_rxbank *b) {
-			b->conv = *conv;
-			b->log2r = jobs.log2r;
-			b->iq = jobs.iq;
-			return b->fused ? fmrxb_upload_conv(b->conv, &b->d_conv) : CORDIC_OK;
-		});
-}
-
-int cordic_rxbank_create_decim(const cordic_plan *plan, const cordic_config *conv,
-		uint32_t log2r, size_t njobs, const cordic_fmrx_job *jobs, cordic_rxbank **bank)
-{
-	return rxbank_create(plan, conv, njobs, RxJobs(jobs, log2r), bank);
-}
-
-int cordic_rxbank_create_decim16(const cordic_plan *plan, const cordic_config *conv,
-		uint32_t log2r, size_t njobs, const cordic_fmrx_job16 *jobs,
-		cordic_rxbank **bank)
-{
-	return rxbank_create(plan, conv, njobs, RxJobs(jobs, log2r), bank);
-}
-
-int cordic_rxbank_create(const cordic_plan *plan, const cordic_config *conv,
-		size_t njobs, const cordic_fmrx_job *jobs, cordic_rxbank **bank)
-{
-	return rxbank_create(plan, conv, njobs, jobs, bank);
-}
-
-int cordic_rxbank_create16(const cordic_plan *plan, const cordic_config *conv,
-		size_t njobs, const cordic_fmrx_job16 *jobs, cordic_rxbank **bank)
-{
-	return rxbank_create(plan, conv, njobs, jobs, bank);
-}
-
-// the interleaved creates: the jobs as 16-bit ones whose d_xval is d_iq
-// (fmrxb_from_c16); the checks keep rxbank_create's order
-static int rxbank_create_c16(const cordic_plan *plan, const cordic_config *conv,
-		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
-		cordic_rxbank **bank)
-{
-	if (!bank || (njobs && !jobs))
-		return CORDIC_ERR_ARGS;
-	if (njobs >= ((size_t)1 << 28)) {	// (refused before that many are copied)
-		const int rc = fm_rx_ok(plan, conv, true);
-		return rc ? rc : CORDIC_ERR_ARGS;
-	}
-	std::vector<cordic_fmrx_job16> split(njobs + 1);
-	for (size_t k = 0; k < njobs; k++)
-		split[k] = fmrxb_from_c16(jobs[k]);
-	// (NULL jobs with njobs == 0: NULL on, as _create16 would see it)
-	const cordic_fmrx_job16 *j16 = jobs ? split.data() : nullptr;
-	return rxbank_create(plan, conv, njobs, RxJobs(j16, log2r, true), bank);
-}
-
-int cordic_rxbank_create_c16(const cordic_plan *plan, const cordic_config *conv,
-		size_t njobs, const cordic_fmrx_job_c16 *jobs, cordic_rxbank **bank)
-{
-	return rxbank_create_c16(plan, conv, 0, njobs, jobs, bank);
-}
-
-int cordic_rxbank_create_decim_c16(const cordic_plan *plan, const cordic_config *conv,
-		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
-		cordic_rxbank **bank)
-{
-	return rxbank_create_c16(plan, conv, log2r, njobs, jobs, bank);
-}
-
-void cordic_rxbank_destroy(cordic_rxbank *bank)
-{
-	if (!bank)
-		return;
-	bank->spans.free();
-	dev_free(bank->d_work, bank->d_conv);
-	delete bank;
-}
-
-int cordic_rxbank_info(const cordic_rxbank *bank, uint64_t *samples, uint32_t *spans,
-		int32_t *fused, int32_t *tile)
-{
-	if (!bank)
-		return CORDIC_ERR_ARGS;
-	if (samples) *samples = bank->samples;
-	if (spans) *spans = bank->spans.nspans;
-	if (fused) *fused = bank->fused ? 1 : 0;
-	if (tile) *tile = bank->fused ? (int32_t)kFmrxPass : 0;
-	return CORDIC_OK;
-}
-
-int cordic_rxbank_run(const cordic_rxbank *bank, void *stream)
-{
-	if (!bank)
-		return CORDIC_ERR_ARGS;
-	(void)hipGetLastError();
-	const cordic_plan *plan = bank->plan;
-	return bank_run(*bank, [&] {
-		const SpanTable<RxSpan> &t = bank->spans;
-		return launch_fmrx_bank(plan->cfg, plan->d_dir, plan->dx, bank->d_conv,
-			t.d_spans, t.nspans, t.start(), t.part(), t.more(), bank->cus, bank->io16,
-			stream, bank->log2r, bank->iq);
-	}, [&](const cordic_fmrx_job &jb) {
-		if (bank->iq)	// (d_xval carries the job's d_iq: fmrxb_from_c16)
-			return fm_rx_decim_c16(plan, &bank->conv, (size_t)jb.n, bank->log2r, jb.d_fcw,
-				jb.d_pm, jb.phase0, jb.d_acc, reinterpret_cast<const int16_t *>(jb.d_xval),
-				jb.dphase0, jb.d_last, reinterpret_cast<int16_t *>(jb.d_omag),
-				reinterpret_cast<int16_t *>(jb.d_ofreq), bank->d_work, stream);
-		// (log2r 0: the receiver's own call, cordic_plan_fm_rx or _rx16)
-		return fm_rx_decim(plan, &bank->conv, (size_t)jb.n, bank->log2r, jb.d_fcw,
-			jb.d_pm, jb.phase0, jb.d_acc, jb.d_xval, jb.d_yval, jb.dphase0, jb.d_last,
-			jb.d_omag, jb.d_ofreq, bank->d_work, stream, bank->io16);
-	});
-}
 
 int cordic_plan_queue_info(const cordic_plan *plan, cordic_queue_info *info)
 {

@@ -112,7 +112,7 @@ static inline int cus_or_256()
 }
 
 // ---- What cordic_demodbank (cordic_fm_demod_bank.hip) and cordic_mixbank
-// (cordic_abi.cpp) share: a bank runs FUSED, from descriptor tables that its
+// (cordic_abi_fm.cpp) share: a bank runs FUSED, from descriptor tables that its
 // create cuts and uploads, or ONE BY ONE through the single call of its kind.
 template <typename Job> struct BankHandle {
 	bool	fused = false;
@@ -154,7 +154,7 @@ static int bank_begin(size_t njobs, const Job *jobs, bool fused,
 	return CORDIC_OK;
 }
 
-// ---- What cordic_mixbank (cordic_abi.cpp) and cordic_fmbank
+// ---- What cordic_mixbank (cordic_abi_fm.cpp) and cordic_fmbank
 // (cordic_abi_table.cpp) share, the prefix-sum banks (cordic_span_bank.h): the
 // span table on the device and the workspace of a run, [start words, one per
 // non-empty job | partial sums, one per span | SpanRule::words further latched

@@ -5,8 +5,8 @@
 // words, made in the kernel,
 //   p_i = start + fcw[0] + .. + fcw[i-1] + pm[i]      (mod 2^32)
 //   (ox_i, oy_i) = cordic_p2r(x_i, y_i, p_i).
-// The launcher and the host checks for cordic_abi.cpp, where the plan and with
-// it the three entry points live; the fallback (cordic_phase_accumulate into
+// The launcher and the host checks for cordic_abi_fm.cpp, where the entry
+// points live; the fallback (cordic_phase_accumulate into
 // the workspace, then cordic_plan_p2r) is put together there, and so is the
 // 16-bit fallback (widen, the 32-bit call, narrow).  The decimating mixer
 // (cordic_plan_fm_mix_decim, _decim16: R = 2^k tuned samples summed, one kept)
@@ -60,6 +60,21 @@ bool	fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 // more extra bits and takes the 16-bit fallback.
 bool	fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx);
 
+// A call's form, for the plan-side FM layer (cordic_abi_fm.cpp) and the
+// receiver's launchers: the sample arrays' container in bytes (4: int32, 2:
+// int16), whether the input is ONE array of interleaved I/Q (the *_c16 forms,
+// container 2), and k = log2r (0: not decimating).
+struct FmForm {
+	uint32_t container = 4;
+	bool	iq = false;
+	uint32_t log2r = 0;
+	constexpr size_t esize() const { return container; }
+	constexpr bool io16() const { return container == 2; }
+	// the same call at k = 0; on split arrays
+	constexpr FmForm plain() const { return FmForm{container, iq, 0}; }
+	constexpr FmForm split() const { return FmForm{container, false, log2r}; }
+};
+
 // The 16-bit fallback widens into d_work, runs the 32-bit call there and
 // narrows: [the 32-bit call's workspace | x | y | ox | oy], the four as int32,
 // every part on the 16-byte grid.  fused32: fmx_is_fused of the plan.
@@ -67,10 +82,20 @@ constexpr size_t fmx16_array_bytes(size_t n)
 {
 	return (n * 4 + 15) & ~(size_t)15;
 }
+struct Fmx16Layout {
+	size_t	x, y, ox, oy, end;	// byte offsets in d_work
+};
+// mix_bytes: the 32-bit call's own workspace
+constexpr Fmx16Layout fmx16_layout(size_t mix_bytes, size_t n)
+{
+	const size_t each = fmx16_array_bytes(n);
+	return Fmx16Layout{mix_bytes, mix_bytes + each, mix_bytes + 2 * each,
+		mix_bytes + 3 * each, mix_bytes + 4 * each};
+}
 constexpr size_t fmx16_work_bytes(bool fused16, bool fused32, size_t n)
 {
 	return !n ? 0 : fused16 ? kFmxWorkBytes
-		: fmx_work_bytes(fused32, n) + 4 * fmx16_array_bytes(n);
+		: fmx16_layout(fmx_work_bytes(fused32, n), n).end;
 }
 static_assert(kFmxWorkBytes % 16 == 0, "the widened arrays sit on the 16-byte grid");
 
@@ -103,10 +128,18 @@ constexpr size_t fmxd_array_bytes(size_t n, size_t esize)
 {
 	return (n * esize + 15) & ~(size_t)15;
 }
+struct FmxdLayout {
+	size_t	tx, ty, end;		// byte offsets in d_work
+};
 // mix_bytes: the mixer call's own workspace for n samples of that container
+constexpr FmxdLayout fmxd_layout(size_t mix_bytes, size_t n, size_t esize)
+{
+	const size_t each = fmxd_array_bytes(n, esize);
+	return FmxdLayout{mix_bytes, mix_bytes + each, mix_bytes + 2 * each};
+}
 constexpr size_t fmxd_work_bytes(bool fused, size_t mix_bytes, size_t n, size_t esize)
 {
-	return !n ? 0 : fused ? kFmxWorkBytes : mix_bytes + 2 * fmxd_array_bytes(n, esize);
+	return !n ? 0 : fused ? kFmxWorkBytes : fmxd_layout(mix_bytes, n, esize).end;
 }
 
 // log2r <= 8 and n a multiple of 2^log2r
@@ -706,16 +739,17 @@ inline size_t blocks_per_cu(size_t lds)
 // ---- which instance serves a plan, for all four launch-2 kernels
 // <LJ, container> of a core of working width ww on samples of esize bytes: the
 // one home of "WW 35 is LJ 29" and "no Io16 at WW 35" (fmx_is_fused16).  The
-// receiver's units, compiled once per value, index their entry points by it.
+// receiver's units, compiled once per value, index their entry points by it
+// (their list, in this order: cordic_fm_rx_unit.h).
 // kUnitC16: the receivers' <30, IoC16> units, for interleaved 16-bit input --
 // where Io16 serves, and nowhere else.
 enum Unit { kUnitNone = -1, kUnitLj30 = 0, kUnitLj29 = 1, kUnitIo16 = 2, kUnitC16 = 3 };
-inline Unit unit_of(int ww, size_t esize)
+constexpr Unit unit_of(int ww, size_t esize)
 {
 	return esize == 2 ? (ww < 35 ? kUnitIo16 : kUnitNone)
 		: ww == 35 ? kUnitLj29 : kUnitLj30;
 }
-inline Unit unit_of(int ww, size_t esize, bool iq)
+constexpr Unit unit_of(int ww, size_t esize, bool iq)
 {
 	const Unit u = unit_of(ww, esize);
 	return !iq ? u : u == kUnitIo16 ? kUnitC16 : kUnitNone;

@@ -6,7 +6,7 @@
 // job check; plain C++ that touches no device, so that a stand-alone program
 // can run it under a sanitizer -- and the launcher of the two kernels that walk
 // the descriptors (cordic_fm_mix_bank.hip).  Host-visible types only; the
-// handle and its four entry points live with the plan, in cordic_abi.cpp.
+// handle and its entry points live in cordic_abi_fm.cpp.
 //
 // No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
 // does not hash this unit.
@@ -119,7 +119,7 @@ int	launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
 		uint32_t *d_part, int cus, bool io16, void *stream, uint32_t log2r = 0);
 
-// what the create of the plan-side banks (plan_bank_create, cordic_abi.cpp)
+// what the create of the plan-side banks (plan_bank_create, cordic_abi_fm.cpp)
 // asks of a bank besides its view of the jobs
 struct MixBankTraits {
 	static bool jobs_valid(size_t njobs, MixJobs jobs) { return fmxb_jobs_valid(njobs, jobs); }

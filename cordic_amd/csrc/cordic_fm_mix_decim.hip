@@ -55,7 +55,7 @@
 // grids of both launchers assume, so no occupancy step is crossed.
 //
 // Knobs: CORDIC_FMX_MAX_BLOCKS caps the grid as for the mixer
-// (cordic_fm_mix.hip).  CORDIC_FMXD_FALLBACK=1 (cordic_abi.cpp; a test and A/B
+// (cordic_fm_mix.hip).  CORDIC_FMXD_FALLBACK=1 (cordic_abi_fm.cpp; a test and A/B
 // knob, read at every single call AND at every workspace query: set it before
 // both, the fallback's workspace is the larger one) sends a fused plan's SINGLE
 // call through the fallback; banks ignore

@@ -5,8 +5,8 @@
 //   (tx_i, ty_i) = what cordic_plan_fm_mix writes for (x_i, y_i, p_i)
 //   (mag_i, ph_i) = what cordic_r2p writes for (tx_i, ty_i) on conv
 //   freq_i       = sext_PW((ph_i - ph_(i-1)) mod 2^PW).
-// The launcher and the host checks for cordic_abi.cpp, where the plan and with
-// it the entry points live; the fallback (cordic_plan_fm_mix into two arrays
+// The launcher and the host checks for cordic_abi_fm.cpp, where the entry
+// points live; the fallback (cordic_plan_fm_mix into two arrays
 // inside the workspace, then cordic_fm_demod from them) is put together there.
 // Behind them, for hipcc only, the pass loop of the call's kernel
 // (cordic_fm_rx.hip), written over ONE span with its arrays at the span's first
@@ -53,10 +53,20 @@ constexpr size_t fmrx_array_bytes(size_t n, size_t esize)
 {
 	return (n * esize + 15) & ~(size_t)15;
 }
+struct FmrxLayout {
+	size_t	tx, ty, demod, end;	// byte offsets in d_work
+};
+// m: the elements of the tuned arrays and of the discriminator's call (the
+// decimating receiver: n >> k)
+constexpr FmrxLayout fmrx_layout(size_t mix_bytes, size_t m, size_t esize)
+{
+	const size_t each = fmrx_array_bytes(m, esize);
+	return FmrxLayout{mix_bytes, mix_bytes + each, mix_bytes + 2 * each,
+		mix_bytes + 2 * each + fmd_work_bytes(m)};
+}
 constexpr size_t fmrx_work_bytes(bool fused, size_t mix_bytes, size_t n, size_t esize)
 {
-	return !n ? 0 : fused ? kFmrxWorkBytes
-		: mix_bytes + 2 * fmrx_array_bytes(n, esize) + fmd_work_bytes(n);
+	return !n ? 0 : fused ? kFmrxWorkBytes : fmrx_layout(mix_bytes, n, esize).end;
 }
 static_assert(kFmrxWorkBytes % 16 == 0, "a multiple of 16");
 
@@ -66,41 +76,45 @@ static_assert(kFmrxWorkBytes % 16 == 0, "a multiple of 16");
 // (The mode and the container are the caller's to check.)
 bool	fmrx_conv_is_fused(const cordic_config &conv);
 
-// Alignment -- the four sample arrays on the grid of `esize`, the words on that
-// of 4, d_work on that of 16 -- and no output range (the words at d_acc and
-// d_last and the `work_bytes` of d_work included) over anything else, by the
-// true byte ranges; nothing is launched.  n > 0.  log2r: the two outputs hold
-// n >> log2r elements (the decimating receiver).  iq: d_xval is the one
-// interleaved input array (the *_c16 forms: esize 2, on the 4-byte grid, 4 n
-// bytes) and d_yval is not looked at.
-int	fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+// Alignment -- the four sample arrays on the grid of the form's container, the
+// words on that of 4, d_work on that of 16 -- and no output range (the words at
+// d_acc and d_last and the `work_bytes` of d_work included) over anything else,
+// by the true byte ranges; nothing is launched.  n > 0.  The two outputs hold
+// n >> form.log2r elements.  form.iq: d_xval is the one interleaved input array
+// (on the 4-byte grid, 4 n bytes) and d_yval is not looked at.
+int	fmrx_check_call(FmForm form, size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r = 0,
-		bool iq = false);
+		const void *d_work, size_t work_bytes);
 
 // The fused path: two launches on `stream` (fm_rx_reduce, then fm_rx_xydir),
-// nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
+// nothing else.  The sample arrays hold the form's container.
 // The caller has checked fmx_is_fused / fmx_is_fused16, fmrx_conv_is_fused and
 // fmrx_check_call.
-// log2r = k in 1 .. 8: launch 2 is fm_rx_decim_xydir (cordic_fm_rx_decim.hip),
-// which writes n >> k samples; n is a multiple of 2^k.
-// iq (esize 2): d_xval holds interleaved int16 I/Q, 2 n shorts, and d_yval is
-// not read -- the <30, IoC16> instances of launch 2 (fmx::IoC16).
+// form.log2r = k in 1 .. 8: launch 2 is fm_rx_decim_xydir
+// (cordic_fm_rx_decim.hip), which writes n >> k samples; n is a multiple of 2^k.
+// form.iq: d_xval holds interleaved int16 I/Q, 2 n shorts, and d_yval is not
+// read -- the <30, IoC16> instances of launch 2 (fmx::IoC16).
 int	launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
-		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
+		const cordic_config &conv, FmForm form, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r = 0,
-		bool iq = false);
+		void *d_ofreq, void *d_work, void *stream);
 
 // The *_c16 forms' fallback: [the *16 twin's workspace | x | y of n shorts],
 // each part on the 16-byte grid; one launch of fm_rx_split_c16 fills x and y
 // from d_iq (n > 0 complex samples on the 4-byte grid), then the twin runs.
+struct FmrxC16Layout {
+	size_t	x, y, end;		// byte offsets in d_work
+};
+constexpr FmrxC16Layout fmrx_c16_layout(size_t twin_bytes, size_t n)
+{
+	const size_t at = (twin_bytes + 15) & ~(size_t)15, each = fmrx_array_bytes(n, 2);
+	return FmrxC16Layout{at, at + each, at + 2 * each};
+}
 constexpr size_t fmrx_c16_work_bytes(bool fused, size_t twin_bytes, size_t n)
 {
-	return !n || fused ? twin_bytes
-		: ((twin_bytes + 15) & ~(size_t)15) + 2 * fmrx_array_bytes(n, 2);
+	return !n || fused ? twin_bytes : fmrx_c16_layout(twin_bytes, n).end;
 }
 int	launch_fmrx_split_c16(size_t n, const int16_t *d_iq, int16_t *d_x, int16_t *d_y,
 		void *stream);
@@ -305,10 +319,7 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 	}
 }
 
-// ---- the single call's kernel arguments and the launchers of its instances,
-// one unit per <LJ, container> (cordic_fm_rx.hip compiled four times: itself,
-// cordic_fm_rx_lj29.hip, cordic_fm_rx_io16.hip, cordic_fm_rx_c16.hip); false: no
-// instance
+// ---- the single call's kernel arguments (its launchers: cordic_fm_rx_unit.h)
 struct RxArgs {
 	const uint32_t *fcw, *pm;	// pm may be NULL
 	uint32_t *acc, *last;		// either may be NULL
@@ -319,10 +330,6 @@ struct RxArgs {
 	size_t	n, span;		// span: samples per block, whole passes less the halo
 	uint32_t xw;			// LDS byte offset of the exchange words
 };
-typedef bool RxLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a);
-RxLaunch launch_rx_lj30, launch_rx_lj29, launch_rx_io16, launch_rx_c16;	// by fmx::Unit
-
 // ---- host side of both units
 // the tables and the exchange words behind them
 inline size_t lds_bytes(const DxInfo &dx, uint32_t *xw)

@@ -46,14 +46,14 @@
 // A/B knob like CORDIC_FMX_MAX_BLOCKS) caps the grid at n blocks.  The bits do
 // not depend on it.
 //
-// The unit is compiled four times, one <LJ, container> each, so that the
-// four build beside each other: as itself (<30, Io32>, launch 1 and the host
-// side), as cordic_fm_rx_lj29.hip (<29, Io32>), as cordic_fm_rx_io16.hip
-// (<30, Io16>) and as cordic_fm_rx_c16.hip (<30, fmx::IoC16>: interleaved int16
-// I/Q in d_xval, cordic_plan_fm_rx_c16; its registers are listed there).  Each
-// defines ONE entry point, FMRX_LAUNCH, around fmx::with_stages; launch_fm_rx
-// indexes the four by fmx::unit_of.  The host side also holds fm_rx_split_c16,
-// the split kernel of the *_c16 forms' fallback.
+// The unit is compiled four times, once per entry of the receiver's unit list
+// (cordic_fm_rx_unit.h: -DCORDIC_FMRX_UNIT=0 .. 3), so that the four build
+// beside each other: <30, Io32> with launch 1 and the host side, <29, Io32>,
+// <30, Io16>, and <30, fmx::IoC16> for interleaved int16 I/Q in d_xval
+// (cordic_plan_fm_rx_c16).  Each defines ONE entry point, FMRX_ENTRY(launch_rx),
+// around fmx::with_stages; launch_fm_rx indexes the list's table by
+// fmx::unit_of.  The host side also holds fm_rx_split_c16, the split kernel of
+// the *_c16 forms' fallback.
 //
 // Registers (.vgpr_count of the gfx950 code objects, -O3, --save-temps;
 // .private_segment_fixed_size is 0 for every instance: nothing spills to
@@ -62,6 +62,7 @@
 //   fm_rx_xydir<29, N>      108  108  108  108  110  114  114
 //   fm_rx_xydir<30, N>      108  108  108  108  110  113  113
 //   ... <30, N, Io16>       106  106  106  106  108  111  111
+//   ... <30, N, IoC16>      106  106  106  106  108  110  111   (profiles/r24/fm_rx_c16.txt)
 //   fm_rx_reduce             30 (64 bytes of static LDS)
 // against 92 .. 108 of fm_mix_xydir and 90 .. 94 of the dynamic-exit
 // discriminator: up to 128 registers hold 4 waves per SIMD, the mixer's own
@@ -85,10 +86,7 @@
 #include "cordic_hostargs.h"
 #include "cordic_fm_rx.h"
 #include "cordic_fm_rx_decim.h"
-
-#ifndef CORDIC_FMRX_UNIT
-#define CORDIC_FMRX_UNIT 30	// 30: <30, Io32> and the host side; 29; 16; 0xc16
-#endif
+#include "cordic_fm_rx_unit.h"
 
 namespace cordic_amd {
 
@@ -135,27 +133,9 @@ __global__ __launch_bounds__(kBlock) void fm_rx_xydir(CoreParams kp, DirArgs da,
 		*a.acc = carry;
 }
 
-// this unit's <LJ, container> and entry point
-#if CORDIC_FMRX_UNIT == 29
-#define FMRX_LAUNCH launch_rx_lj29
-constexpr int kUnitLj = 29;
-typedef Io32 UnitIo;
-#elif CORDIC_FMRX_UNIT == 16
-#define FMRX_LAUNCH launch_rx_io16
-constexpr int kUnitLj = 30;
-typedef Io16 UnitIo;
-#elif CORDIC_FMRX_UNIT == 0xc16
-#define FMRX_LAUNCH launch_rx_c16
-constexpr int kUnitLj = 30;
-typedef fmx::IoC16 UnitIo;
-#else
-#define FMRX_LAUNCH launch_rx_lj30
-constexpr int kUnitLj = 30;
-typedef Io32 UnitIo;
-#endif
-
-bool FMRX_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxArgs &a)
+// this unit's entry point (kUnitLj, UnitIo: cordic_fm_rx_unit.h)
+bool FMRX_ENTRY(launch_rx)(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a, uint32_t)
 {
 	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
 		hipLaunchKernelGGL((fm_rx_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
@@ -163,7 +143,7 @@ bool FMRX_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
 	});
 }
 
-#if CORDIC_FMRX_UNIT == 30
+#if CORDIC_FMRX_UNIT == 0
 // Four consecutive words at any 4-byte-aligned address: one dwordx4 load
 // (span_words4, cordic_span_reduce.h)
 typedef uint32_t words4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -222,19 +202,19 @@ __global__ __launch_bounds__(1024) void fm_rx_reduce(const uint32_t *d_fcw, size
 
 } // namespace fmrx
 
-#if CORDIC_FMRX_UNIT == 30
+#if CORDIC_FMRX_UNIT == 0
 bool fmrx_conv_is_fused(const cordic_config &conv)
 {
 	return fmd_core_is_fused(conv) && !(conv.flags & CORDIC_FLAG_UNIT_GAIN);
 }
 
-int fmrx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
+int fmrx_check_call(FmForm form, size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const uint32_t *d_last, const void *d_omag, const void *d_ofreq,
-		size_t esize, const void *d_work, size_t work_bytes, uint32_t log2r, bool iq)
+		const void *d_work, size_t work_bytes)
 {
 	return iq_call_ok(n, d_acc, d_last, d_fcw, d_pm, d_xval, d_yval, d_omag, d_ofreq,
-		esize, d_work, work_bytes, log2r, iq) ? CORDIC_OK : CORDIC_ERR_ARGS;
+		form.esize(), d_work, work_bytes, form.log2r, form.iq) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 // The *_c16 forms' fallback: thread t splits complex samples 4 t .. 4 t + 3, one
@@ -280,12 +260,13 @@ int launch_fmrx_split_c16(size_t n, const int16_t *d_iq, int16_t *d_x, int16_t *
 }
 
 int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
-		const cordic_config &conv, size_t n, const uint32_t *d_fcw,
+		const cordic_config &conv, FmForm form, size_t n, const uint32_t *d_fcw,
 		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_xval,
 		const void *d_yval, uint32_t dphase0, uint32_t *d_last, void *d_omag,
-		void *d_ofreq, size_t esize, void *d_work, void *stream, uint32_t log2r, bool iq)
+		void *d_ofreq, void *d_work, void *stream)
 {
 	using namespace fmrx;
+	const uint32_t log2r = form.log2r;
 	(void)hipGetLastError();	// (a stale error is not this call's)
 	if (n == 0)
 		return CORDIC_OK;
@@ -306,11 +287,13 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 	const size_t span = cs.span;
 	const unsigned grid = (unsigned)cs.grid;
 	// the instance first: nothing is enqueued for a core without one
-	static RxLaunch *const units[4] = {launch_rx_lj30, launch_rx_lj29, launch_rx_io16,
-		launch_rx_c16};
-	static fmrxd::RxdLaunch *const dunits[4] = {fmrxd::launch_rxd_lj30,
-		fmrxd::launch_rxd_lj29, fmrxd::launch_rxd_io16, fmrxd::launch_rxd_c16};
-	const fmx::Unit u = fmx::unit_of(cfg.ww, esize, iq);
+#define PLAIN(sfx, lj, io) launch_rx_##sfx,
+#define DECIM(sfx, lj, io) launch_rxd_##sfx,
+	static RxLaunch *const entry[2][kUnits] = {{CORDIC_FMRX_UNITS(PLAIN)},
+		{CORDIC_FMRX_UNITS(DECIM)}};
+#undef PLAIN
+#undef DECIM
+	const fmx::Unit u = fmx::unit_of(cfg.ww, form.esize(), form.iq);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	uint32_t *work = static_cast<uint32_t *>(d_work);
@@ -325,9 +308,7 @@ int launch_fm_rx(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &
 		n, span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	const bool done = log2r ? dunits[u](cfg.nlive, grid, lds, st, kp, da, a, log2r)
-		: units[u](cfg.nlive, grid, lds, st, kp, da, a);
-	return tnco::finish(done);
+	return tnco::finish(entry[log2r != 0][u](cfg.nlive, grid, lds, st, kp, da, a, log2r));
 }
 #endif
 

@@ -7,7 +7,7 @@
 // that a stand-alone program can run it under a sanitizer
 // (tests/test_fm_rx_host.py) -- and the launcher of the two kernels that walk
 // the descriptors (cordic_fm_rx_bank.hip).  Host-visible types only; the handle
-// and its entry points live with the plan, in cordic_abi.cpp.
+// and its entry points live in cordic_abi_fm.cpp.
 //
 // No kernel of the DESIGN section 4.4 sweep lives here, so tools/build_stamp.py
 // does not hash this unit.
@@ -168,19 +168,20 @@ inline void span_place(RxSpan *d, const RxJob &jb, uint64_t at)
 int	fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv);
 
 // The two launches, for a plan and a converter of which the single call is
-// fused (cordic_fm_rx.h) -- the 16-bit rule where the spans were cut from
-// 16-bit jobs (io16).  d_start / d_part / d_prev: the bank's workspace (one word
-// per non-empty job, one per span, one per non-empty job).  cus: the device's,
-// at create.  An empty table launches nothing.  log2r = k in 1 .. 8: the spans
-// were cut for a decimating bank (fmrxb_rule(k)), and launch 2 is
-// fm_rxbank_decim_xydir (cordic_fm_rx_bank_decim.hip).  CORDIC_OK or
-// iq: the spans were cut from interleaved jobs (RxJobs::iq, below; io16 too):
-// the <30, IoC16> instances.  CORDIC_OK or CORDIC_ERR_DEVICE.
+// fused (cordic_fm_rx.h), in the form the spans were cut for: the container of
+// the jobs' arrays, form.iq where they were interleaved jobs (RxJobs::iq: the
+// <30, IoC16> instances), form.log2r = k in 1 .. 8 for a decimating bank
+// (fmrxb_rule(k); launch 2 is fm_rxbank_decim_xydir,
+// cordic_fm_rx_bank_decim.hip).  d_start / d_part / d_prev: the bank's workspace
+// (one word per non-empty job, one per span, one per non-empty job).  cus: the
+// device's, at create.  An empty table launches nothing.  CORDIC_OK or
+// CORDIC_ERR_DEVICE.
 struct DxInfo;		// (cordic_internal.h)
+struct FmForm;		// (cordic_fm_mix.h)
 int	launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
-		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream, uint32_t log2r = 0, bool iq = false);
+		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, FmForm form,
+		void *stream);
 
 // (as MixBankTraits, cordic_fm_mix_bank.h; the rule depends on the bank's k)
 struct RxBankTraits {
@@ -190,21 +191,6 @@ struct RxBankTraits {
 	static constexpr const char *max_spans = "CORDIC_FMRXB_MAX_SPANS";
 	static constexpr int blocks_per_cu = kFmrxbBlocksPerCu;
 };
-
-#ifdef __HIPCC__
-// Launch 2 of a decimating bank, for launch_fmrx_bank
-// (cordic_fm_rx_bank_decim.hip, compiled once per <LJ, container>); false: no
-// instance.
-namespace dev { struct CoreParams; struct DirArgs; }
-namespace fmrxd {
-typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, void *stream,
-		const dev::CoreParams &kp, const dev::DirArgs &da, const RxSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw, uint32_t log2r);
-BankLaunch launch_rxbank_decim_lj30, launch_rxbank_decim_lj29, launch_rxbank_decim_io16,
-	launch_rxbank_decim_c16;
-}
-#endif
 
 } // namespace cordic_amd
 #endif

@@ -37,14 +37,19 @@
 // Knobs: CORDIC_FMRXB_PASSES and CORDIC_FMRXB_MAX_SPANS at create,
 // CORDIC_FMRXB_MAX_BLOCKS at every run.  The bits depend on none.
 //
-// The unit is compiled four times, one <LJ, container> each: as itself (<30,
-// Io32>, launch 1 and the host side), as cordic_fm_rx_bank_lj29.hip, as
-// cordic_fm_rx_bank_io16.hip and as cordic_fm_rx_bank_c16.hip (interleaved
-// int16 I/Q: a span's x carries d_iq, its y is unused).  Each defines ONE entry
-// point, FMRXB_LAUNCH, around fmx::with_stages; launch_fmrx_bank indexes the
-// four by fmx::unit_of.
+// The unit is compiled four times, once per entry of the receiver's unit list
+// (cordic_fm_rx_unit.h; unit 0 with launch 1 and the host side; the last on
+// interleaved int16 I/Q: a span's x carries d_iq, its y is unused).  Each
+// defines ONE entry point, FMRX_ENTRY(launch_rxbank), around fmx::with_stages;
+// launch_fmrx_bank indexes the list's table by fmx::unit_of.
 //
-// Registers: the table in DESIGN.md section 4.8 and profiles/r20/fm_rx.txt.
+// Registers: the table in DESIGN.md section 4.8 and profiles/r20/fm_rx.txt;
+// .vgpr_count of the 16-bit containers (scratch 0; above 128 both: the banks'
+// grid is sized for 3 blocks per CU, kFmrxbBlocksPerCu, which holds up to 168;
+// profiles/r24/fm_rx_c16.txt):
+//   live stages                   13   16   19   20   24   27   29
+//   fm_rxbank_xydir<30, N, IoC16> 132  142  133  133  134  137  137
+//   ... <30, N, Io16>             130  132  131  131  132  135  135
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -59,10 +64,7 @@
 #include "cordic_fm_rx_decim.h"
 #include "cordic_fm_rx_bank.h"
 #include "cordic_span_reduce.h"
-
-#ifndef CORDIC_FMRXB_UNIT
-#define CORDIC_FMRXB_UNIT 30	// 30: <30, Io32>, launch 1 and the host side; 29; 16; 0xc16
-#endif
+#include "cordic_fm_rx_unit.h"
 
 namespace cordic_amd {
 
@@ -81,13 +83,6 @@ __device__ __forceinline__ void span_latch_more(const RxSpan &d, uint32_t *more)
 namespace fmrx {
 
 using namespace dev;
-
-typedef bool BankLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
-		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw);
-BankLaunch launch_rxbank_lj30, launch_rxbank_lj29, launch_rxbank_io16,
-	launch_rxbank_c16;	// by fmx::Unit
 
 // launch 2 (see the head of this file)
 template <int LJ, int NLIVE, typename IO>
@@ -134,29 +129,11 @@ __global__ __launch_bounds__(kBlock) void fm_rxbank_xydir(CoreParams kp, DirArgs
 	}
 }
 
-// this unit's <LJ, container> and entry point
-#if CORDIC_FMRXB_UNIT == 29
-#define FMRXB_LAUNCH launch_rxbank_lj29
-constexpr int kUnitLj = 29;
-typedef Io32 UnitIo;
-#elif CORDIC_FMRXB_UNIT == 16
-#define FMRXB_LAUNCH launch_rxbank_io16
-constexpr int kUnitLj = 30;
-typedef Io16 UnitIo;
-#elif CORDIC_FMRXB_UNIT == 0xc16
-#define FMRXB_LAUNCH launch_rxbank_c16
-constexpr int kUnitLj = 30;
-typedef fmx::IoC16 UnitIo;
-#else
-#define FMRXB_LAUNCH launch_rxbank_lj30
-constexpr int kUnitLj = 30;
-typedef Io32 UnitIo;
-#endif
-
-bool FMRXB_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
+// this unit's entry point (kUnitLj, UnitIo: cordic_fm_rx_unit.h)
+bool FMRX_ENTRY(launch_rxbank)(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
-		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw)
+		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw, uint32_t)
 {
 	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
 		hipLaunchKernelGGL((fm_rxbank_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
@@ -167,7 +144,7 @@ bool FMRXB_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
 
 } // namespace fmrx
 
-#if CORDIC_FMRXB_UNIT == 30
+#if CORDIC_FMRX_UNIT == 0
 int fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv)
 {
 	const dev::CoreParams ck = make_params_jobs(conv);
@@ -176,10 +153,11 @@ int fmrxb_upload_conv(const cordic_config &conv, uint32_t **d_conv)
 
 int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const uint32_t *d_conv, const RxSpan *d_spans, uint32_t nspans,
-		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, bool io16,
-		void *stream, uint32_t log2r, bool iq)
+		uint32_t *d_start, uint32_t *d_part, uint32_t *d_prev, int cus, FmForm form,
+		void *stream)
 {
 	using namespace fmrx;
+	const uint32_t log2r = form.log2r;
 	(void)hipGetLastError();	// (a stale error is not this call's)
 	if (nspans == 0)
 		return CORDIC_OK;
@@ -193,23 +171,21 @@ int launch_fmrx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxIn
 	// launch 1 has 8 waves a SIMD: 8 blocks of 4 waves a CU
 	const SpanGrids g = span_grids(nspans, cus, 8, "CORDIC_FMRXB_MAX_BLOCKS", per_cu);
 	// the instance first: nothing is enqueued for a core without one
-	static BankLaunch *const units[4] = {launch_rxbank_lj30, launch_rxbank_lj29,
-		launch_rxbank_io16, launch_rxbank_c16};
-	static fmrxd::BankLaunch *const dunits[4] = {fmrxd::launch_rxbank_decim_lj30,
-		fmrxd::launch_rxbank_decim_lj29, fmrxd::launch_rxbank_decim_io16,
-		fmrxd::launch_rxbank_decim_c16};
-	const fmx::Unit u = fmx::unit_of(cfg.ww, io16 ? 2 : 4, iq);
+#define PLAIN(sfx, lj, io) launch_rxbank_##sfx,
+#define DECIM(sfx, lj, io) launch_rxbank_decim_##sfx,
+	static BankLaunch *const entry[2][kUnits] = {{CORDIC_FMRX_UNITS(PLAIN)},
+		{CORDIC_FMRX_UNITS(DECIM)}};
+#undef PLAIN
+#undef DECIM
+	const fmx::Unit u = fmx::unit_of(cfg.ww, form.esize(), form.iq);
 	if (u == fmx::kUnitNone || !fmx_is_fused(cfg, d_dir, dx))
 		return tnco::finish(false);
 	hipLaunchKernelGGL((span_reduce<RxSpan, 256>), dim3(g.reduce), dim3(256), 0, st,
 		d_spans, nspans, d_start, d_part);
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
-	if (log2r)
-		return tnco::finish(dunits[u](cfg.nlive, g.walk, lds, stream, kp, da, d_spans,
-			nspans, d_start, d_part, d_prev, d_conv, xw, log2r));
-	return tnco::finish(units[u](cfg.nlive, g.walk, lds, st, kp, da, d_spans, nspans,
-		d_start, d_part, d_prev, d_conv, xw));
+	return tnco::finish(entry[log2r != 0][u](cfg.nlive, g.walk, lds, st, kp, da, d_spans,
+		nspans, d_start, d_part, d_prev, d_conv, xw, log2r));
 }
 #endif
 

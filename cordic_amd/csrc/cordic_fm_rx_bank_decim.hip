@@ -21,9 +21,14 @@
 // barrier.  The shares of a span's prologue (ex[8 .. 12)) are written only
 // behind those.
 //
-// The unit is compiled four times, as cordic_fm_rx_bank.hip is: as itself
-// (<30, Io32>), as cordic_fm_rx_bank_decim_lj29.hip, as
-// cordic_fm_rx_bank_decim_io16.hip and as cordic_fm_rx_bank_decim_c16.hip.  Registers: profiles/r23/fm_rx_decim.txt.
+// The unit is compiled four times, as cordic_fm_rx_bank.hip is: once per entry
+// of the receiver's unit list (cordic_fm_rx_unit.h).
+// Registers: profiles/r23/fm_rx_decim.txt; .vgpr_count of the 16-bit containers
+// (scratch 0; above 128 both: 3 blocks per CU, kFmrxbBlocksPerCu, which holds up
+// to 168; profiles/r24/fm_rx_c16.txt):
+//   live stages                         13   16   19   20   24   27   29
+//   fm_rxbank_decim_xydir<30, N, IoC16> 134  144  135  135  136  139  139
+//   ... <30, N, Io16>                   133  143  134  134  135  138  138
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,10 +39,7 @@
 #include "cordic_hostargs.h"
 #include "cordic_fm_rx_decim.h"
 #include "cordic_fm_rx_bank.h"
-
-#ifndef CORDIC_FMRXBD_UNIT
-#define CORDIC_FMRXBD_UNIT 30	// 30: <30, Io32>; 29; 16; 0xc16
-#endif
+#include "cordic_fm_rx_unit.h"
 
 namespace cordic_amd {
 
@@ -90,38 +92,23 @@ __global__ __launch_bounds__(kBlock) void fm_rxbank_decim_xydir(CoreParams kp, D
 	}
 }
 
-// this unit's <LJ, container> and entry point
-#if CORDIC_FMRXBD_UNIT == 29
-#define FMRXBD_LAUNCH launch_rxbank_decim_lj29
-constexpr int kUnitLj = 29;
-typedef Io32 UnitIo;
-#elif CORDIC_FMRXBD_UNIT == 16
-#define FMRXBD_LAUNCH launch_rxbank_decim_io16
-constexpr int kUnitLj = 30;
-typedef Io16 UnitIo;
-#elif CORDIC_FMRXBD_UNIT == 0xc16
-#define FMRXBD_LAUNCH launch_rxbank_decim_c16
-constexpr int kUnitLj = 30;
-typedef fmx::IoC16 UnitIo;
-#else
-#define FMRXBD_LAUNCH launch_rxbank_decim_lj30
-constexpr int kUnitLj = 30;
-typedef Io32 UnitIo;
-#endif
+} // namespace fmrxd
 
-bool FMRXBD_LAUNCH(int nlive, unsigned grid, size_t lds, void *stream,
+namespace fmrx {
+
+// this unit's entry point (kUnitLj, UnitIo: cordic_fm_rx_unit.h)
+bool FMRX_ENTRY(launch_rxbank_decim)(int nlive, unsigned grid, size_t lds, hipStream_t st,
 		const CoreParams &kp, const DirArgs &da, const RxSpan *spans,
 		uint32_t nspans, const uint32_t *start, const uint32_t *part,
 		const uint32_t *prev, const uint32_t *ckmem, uint32_t xw, uint32_t log2r)
 {
-	hipStream_t st = static_cast<hipStream_t>(stream);
 	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
-		hipLaunchKernelGGL((fm_rxbank_decim_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
+		hipLaunchKernelGGL((fmrxd::fm_rxbank_decim_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
 			dim3(grid), dim3(kBlock), lds, st, kp, da, spans, nspans, start, part, prev,
 			ckmem, xw, log2r);
 	});
 }
 
-} // namespace fmrxd
+} // namespace fmrx
 
 } // namespace cordic_amd

@@ -7,7 +7,7 @@
 //   (mag_j, ph_j) = what cordic_r2p writes for (dx_j, dy_j) on conv
 //   freq_j       = sext_PW((ph_j - ph_(j-1)) mod 2^PW),
 // neither the tuned nor the decimated I/Q stored.  The geometry's constants and
-// the workspace rule for cordic_abi.cpp, where the fallback (the decimating
+// the workspace rule for cordic_abi_fm.cpp, where the fallback (the decimating
 // mixer into two arrays inside the workspace, then cordic_fm_demod from them)
 // is put together; the launcher is launch_fm_rx (cordic_fm_rx.h) with log2r.
 // Behind them, for hipcc only, the pass loop of the call's kernel
@@ -44,13 +44,12 @@ constexpr size_t fmrxd_halo(uint32_t log2r)
 
 // Fallback: [the decimating mixer call's workspace | T_x | T_y of n >> k
 // elements | the discriminator's workspace for n >> k], each part on the
-// 16-byte grid.  mixd_bytes: cordic_plan_fm_mix_decim_workspace(n, k) (_decim16).
+// 16-byte grid: fmrx_layout (cordic_fm_rx.h) with m = n >> k.  mixd_bytes: cordic_plan_fm_mix_decim_workspace(n, k) (_decim16).
 constexpr size_t fmrxd_work_bytes(bool fused, size_t mixd_bytes, size_t n, uint32_t log2r,
 		size_t esize)
 {
 	return !n ? 0 : fused ? kFmrxWorkBytes
-		: mixd_bytes + 2 * fmrx_array_bytes(n >> log2r, esize)
-			+ fmd_work_bytes(n >> log2r);
+		: fmrx_layout(mixd_bytes, n >> log2r, esize).end;
 }
 
 } // namespace cordic_amd
@@ -308,12 +307,6 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 		}
 	}
 }
-
-// the launchers of the single call's instances, one unit per <LJ, container>
-// (cordic_fm_rx_decim.hip compiled three times); false: no instance
-typedef bool RxdLaunch(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const fmrx::RxArgs &a, uint32_t log2r);
-RxdLaunch launch_rxd_lj30, launch_rxd_lj29, launch_rxd_io16, launch_rxd_c16;	// by fmx::Unit
 
 // the tables, the exchange words and the ring behind them
 inline size_t lds_bytes(const DxInfo &dx, uint32_t *xw)

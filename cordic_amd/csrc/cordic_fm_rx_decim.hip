@@ -30,12 +30,17 @@
 //
 // CORDIC_FMRXD_MAX_BLOCKS=<n> caps the grid (read at every call; a test and
 // A/B knob); the bits do not depend on it.  CORDIC_FMRXD_FALLBACK=1
-// (cordic_abi.cpp) sends a fused pair's single call through the fallback.
+// (cordic_abi_fm.cpp) sends a fused pair's single call through the fallback.
 //
-// The unit is compiled four times, as cordic_fm_rx.hip is: as itself (<30,
-// Io32>), as cordic_fm_rx_decim_lj29.hip, as cordic_fm_rx_decim_io16.hip and as
-// cordic_fm_rx_decim_c16.hip (interleaved int16 I/Q in, fmx::IoC16).
-// Registers and LDS per instance: profiles/r23/fm_rx_decim.txt.
+// The unit is compiled four times, as cordic_fm_rx.hip is: once per entry of
+// the receiver's unit list (cordic_fm_rx_unit.h), the last on interleaved int16
+// I/Q (fmx::IoC16).
+// Registers and LDS per instance: profiles/r23/fm_rx_decim.txt; .vgpr_count of
+// the 16-bit containers (scratch 0; within 128: 4 waves per SIMD, the grid's 4
+// blocks per CU; profiles/r24/fm_rx_c16.txt):
+//   live stages                     13   16   19   20   24   27   29
+//   fm_rx_decim_xydir<30, N, IoC16> 116  116  117  117  118  121  121
+//   ... <30, N, Io16>               115  115  116  116  117  120  120
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -46,10 +51,7 @@
 #include "cordic_table_nco.h"
 #include "cordic_hostargs.h"
 #include "cordic_fm_rx_decim.h"
-
-#ifndef CORDIC_FMRXD_UNIT
-#define CORDIC_FMRXD_UNIT 30	// 30: <30, Io32>; 29; 16; 0xc16
-#endif
+#include "cordic_fm_rx_unit.h"
 
 namespace cordic_amd {
 
@@ -97,34 +99,20 @@ __global__ __launch_bounds__(kBlock) void fm_rx_decim_xydir(CoreParams kp, DirAr
 		*a.acc = carry;
 }
 
-// this unit's <LJ, container> and entry point
-#if CORDIC_FMRXD_UNIT == 29
-#define FMRXD_LAUNCH launch_rxd_lj29
-constexpr int kUnitLj = 29;
-typedef Io32 UnitIo;
-#elif CORDIC_FMRXD_UNIT == 16
-#define FMRXD_LAUNCH launch_rxd_io16
-constexpr int kUnitLj = 30;
-typedef Io16 UnitIo;
-#elif CORDIC_FMRXD_UNIT == 0xc16
-#define FMRXD_LAUNCH launch_rxd_c16
-constexpr int kUnitLj = 30;
-typedef fmx::IoC16 UnitIo;
-#else
-#define FMRXD_LAUNCH launch_rxd_lj30
-constexpr int kUnitLj = 30;
-typedef Io32 UnitIo;
-#endif
+} // namespace fmrxd
 
-bool FMRXD_LAUNCH(int nlive, unsigned grid, size_t lds, hipStream_t st,
-		const CoreParams &kp, const DirArgs &da, const fmrx::RxArgs &a, uint32_t log2r)
+namespace fmrx {
+
+// this unit's entry point (kUnitLj, UnitIo: cordic_fm_rx_unit.h)
+bool FMRX_ENTRY(launch_rxd)(int nlive, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const RxArgs &a, uint32_t log2r)
 {
 	return fmx::with_stages(nlive, da.dx.n, [&](auto nl) {
-		hipLaunchKernelGGL((fm_rx_decim_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
+		hipLaunchKernelGGL((fmrxd::fm_rx_decim_xydir<kUnitLj, decltype(nl)::value, UnitIo>),
 			dim3(grid), dim3(kBlock), lds, st, kp, da, a, log2r);
 	});
 }
 
-} // namespace fmrxd
+} // namespace fmrx
 
 } // namespace cordic_amd

@@ -1,5 +1,6 @@
 // cordic_queue_ring.h -- the tile queues a plan, table or quadratic handle
-// lends to its launches (host only; cordic_abi.cpp, cordic_abi_table.cpp).
+// lends to its launches (host only; cordic_abi.cpp with cordic_abi_plan.h,
+// cordic_abi_table.cpp).
 #pragma once
 #include <cstdlib>
 #include <mutex>
@@ -29,7 +30,9 @@
 // Stream identity is never taken from the handle's address (a destroyed
 // stream's address can be reused): a slot whose event has not completed is
 // always waited for on the device, whatever stream asks.
-namespace {
+// (Inline and templates only: cordic_abi_plan.h puts a ring into a handle that
+// two units share.)
+namespace cordic_amd {
 constexpr unsigned kQueueSlots = 256;
 constexpr unsigned kEagerSlots = 48;
 
@@ -165,4 +168,4 @@ template <typename H> int queue_info(const H *h, cordic_queue_info *info)
 	h->queues.info(info);
 	return CORDIC_OK;
 }
-} // namespace
+} // namespace cordic_amd

@@ -110,6 +110,62 @@ def test_null_handles_and_modes_are_refused_without_a_device_in_the_documented_o
     plan.close()
 
 
+# (entry point, container, interleaved, decimating)
+SINGLE_CALLS = (("cordic_plan_fm_rx", 4, False, False), ("cordic_plan_fm_rx16", 2, False, False),
+                ("cordic_plan_fm_rx_c16", 2, True, False),
+                ("cordic_plan_fm_rx_decim", 4, False, True),
+                ("cordic_plan_fm_rx_decim16", 2, False, True),
+                ("cordic_plan_fm_rx_decim_c16", 2, True, True))
+# the cases of the *_c16 forms that tests/test_fm_rx_c16_host.py pins already
+PINNED_C16 = {"NULL plan", "NULL converter", "converter in a p2r mode", "plan too wide",
+              "converter's PW too wide", "k = 9", "n no multiple of 2^k"}
+
+
+def test_the_status_codes_of_all_six_single_calls_and_their_queries_in_one_table():
+    """Every single-call receiver entry point and its _workspace query on the
+    arguments that are refused before the device is touched, in the order
+    include/cordic_amd.h documents: the plan (ARGS, MODE), the converter (ARGS,
+    MODE), the plan's container, the converter's, then the shape.  The sample
+    arrays are in place (addresses that are never dereferenced), so that ARGS
+    for a shape is not the ranges' ARGS; every query answers 0."""
+    import test_fm_demod16 as DEM16
+    import test_fm_mix16 as MIX16
+    L = ca.lib()
+    wide = ca.Plan(MIX.both("ww38")[0])             # IW 32: no 16-bit container
+    narrow = ca.Plan(MIX16.both("n9")[0])
+    polar = ca.Plan(DEM.both("r2p32")[0])           # a converter handed in as the plan
+    cfg3 = DEM.both("cfg3")[0]                      # IW 24, PW 24: a wide converter
+    conv16 = ca.Config.from_cli(*DEM16.CORES["io16"][0])
+    rot = MIX.both("ww38")[0]                       # a rotator as the converter
+    a = 0x100000
+    for name, es, iq, decim in SINGLE_CALLS:
+        plan, conv = (wide, cfg3) if es == 4 else (narrow, conv16)
+        cases = [("NULL plan", None, conv.ref, 3, 1024, ca.ERR_ARGS),
+                 ("NULL converter", plan._h, None, 3, 1024, ca.ERR_ARGS),
+                 ("plan in an r2p mode", polar._h, conv.ref, 3, 1024, ca.ERR_MODE),
+                 ("converter in a p2r mode", plan._h, rot.ref, 3, 1024, ca.ERR_MODE)]
+        if es == 2:
+            cases += [("plan too wide", wide._h, conv.ref, 3, 1024, ca.ERR_CONTAINER),
+                      ("converter's PW too wide", plan._h, cfg3.ref, 3, 1024,
+                       ca.ERR_CONTAINER)]
+        if decim:
+            cases += [("k = 9", plan._h, conv.ref, 9, 1024, ca.ERR_ARGS),
+                      ("n no multiple of 2^k", plan._h, conv.ref, 3, 1020, ca.ERR_ARGS)]
+        for what, p, c, k, n, want in cases:
+            if iq and what in PINNED_C16:
+                continue
+            ks = (k,) if decim else ()
+            xy = (2 * a,) if iq else (2 * a, 3 * a)
+            rest = (a, None, 0, None) + xy + (0, None, 4 * a, 5 * a, 6 * a, None)
+            got = getattr(L, name)(p, c, n, *ks, *rest)
+            assert got == want, (name, what, got)
+            assert getattr(L, name + "_workspace")(p, c, n, *ks) == 0, (name, what)
+            if what != "n no multiple of 2^k":      # in front of "n = 0 is a no-op"
+                assert getattr(L, name)(p, c, 0, *ks, *rest) == want, (name, what)
+    for h in (wide, narrow, polar):
+        h.close()
+
+
 def test_the_workspace_of_a_pair_that_is_not_fused_holds_the_two_arrays():
     plan = ca.Plan(MIX.both("ww38")[0])
     cfg3 = DEM.both("cfg3")[0]
@@ -172,6 +228,7 @@ PROGRAM = r"""
 #include "cordic_fm_mix_bank.h"
 #include "cordic_fm_demod_bank.h"
 #include "cordic_table_fm_bank.h"
+#include "cordic_fm_rx_decim.h"
 
 using namespace cordic_amd;
 
@@ -382,8 +439,91 @@ static void others()
 	EXPECT(span_job_units(kFmxbRule, 8 * 1024 + 1, 1, 4) == 4);
 }
 
+// ---- the fallbacks' places inside d_work (the layout functions next to the
+// *_work_bytes rules): every part begins on the 16-byte grid, holds its bytes,
+// ends where the next begins, and the last ends at what the rule returns --
+// which is the closed form the rule had before it was written in terms of the
+// layout
+static size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+struct Part { size_t at, bytes; };
+template <size_t N>
+static void parts_ok(const Part (&p)[N], size_t first, size_t end, size_t rule, size_t closed)
+{
+	EXPECT(p[0].at == first);
+	for (size_t k = 0; k < N; k++) {
+		const size_t next = k + 1 < N ? p[k + 1].at : end;
+		EXPECT(p[k].at % 16 == 0);
+		EXPECT(p[k].at + p[k].bytes <= next);		// no overlap
+		EXPECT(p[k].at + up16(p[k].bytes) == next);	// and no hole of a grid step
+	}
+	EXPECT(end == rule && rule == closed);
+}
+
+static void layouts()
+{
+	const size_t ns[] = {1, 4, 1023, 1024, 1025, 4096};
+	const uint32_t ks[] = {0, 1, 3, 8};
+	for (size_t n : ns) {
+		for (size_t es : {(size_t)4, (size_t)2}) {
+			for (uint32_t k : ks) {
+				if (n & (((size_t)1 << k) - 1))
+					continue;
+				const size_t m = n >> k;
+				for (size_t mix : {(size_t)160, fmx_work_bytes(false, n), kFmxWorkBytes}) {
+					// the receiver: [mixer workspace | tuned x | tuned y |
+					// discriminator workspace], m elements in the arrays
+					const FmrxLayout r = fmrx_layout(mix, m, es);
+					const Part rp[] = {{r.tx, m * es}, {r.ty, m * es},
+						{r.demod, fmd_work_bytes(m)}};
+					const size_t closed = mix + 2 * up16(m * es) + fmd_work_bytes(m);
+					parts_ok(rp, mix, r.end, fmrxd_work_bytes(false, mix, n, k, es), closed);
+					if (k == 0)
+						EXPECT(fmrx_work_bytes(false, mix, n, es) == closed);
+					EXPECT(fmrxd_work_bytes(true, mix, n, k, es) == kFmrxWorkBytes);
+					// the decimating mixer's own: [mixer workspace | tx | ty] at
+					// the full rate
+					const FmxdLayout d = fmxd_layout(mix, n, es);
+					const Part dp[] = {{d.tx, n * es}, {d.ty, n * es}};
+					parts_ok(dp, mix, d.end, fmxd_work_bytes(false, mix, n, es),
+						mix + 2 * up16(n * es));
+				}
+			}
+		}
+		// the *_c16 split: [twin | x | y of n shorts], the twin's size rounded up
+		for (size_t twin : {(size_t)16544, (size_t)16544 + 8, (size_t)1}) {
+			const FmrxC16Layout c = fmrx_c16_layout(twin, n);
+			const Part cp[] = {{c.x, n * 2}, {c.y, n * 2}};
+			parts_ok(cp, up16(twin), c.end, fmrx_c16_work_bytes(false, twin, n),
+				up16(twin) + 2 * up16(n * 2));
+			EXPECT(fmrx_c16_work_bytes(true, twin, n) == twin);
+		}
+		// the 16-bit mixer: [the 32-bit call's workspace | x | y | ox | oy] as int32
+		for (bool f32 : {false, true}) {
+			const size_t mix = fmx_work_bytes(f32, n);
+			const Fmx16Layout w = fmx16_layout(mix, n);
+			const Part wp[] = {{w.x, n * 4}, {w.y, n * 4}, {w.ox, n * 4}, {w.oy, n * 4}};
+			parts_ok(wp, mix, w.end, fmx16_work_bytes(false, f32, n), mix + 4 * up16(n * 4));
+		}
+	}
+	EXPECT(fmrx_work_bytes(false, 160, 0, 4) == 0 && fmrx_c16_work_bytes(false, 0, 0) == 0
+		&& fmxd_work_bytes(false, 160, 0, 2) == 0 && fmx16_work_bytes(false, false, 0) == 0);
+}
+static_assert(fmrx_layout(160, 1024 >> 3, 2).tx == 160
+	&& fmrx_layout(160, 1024 >> 3, 2).ty == 160 + 256
+	&& fmrx_layout(160, 1024 >> 3, 2).demod == 160 + 512
+	&& fmrx_layout(160, 1024 >> 3, 2).end == 160 + 512 + fmd_work_bytes(128), "k = 3, shorts");
+static_assert(fmrx_layout(32, 1025, 4).ty == 32 + 4112 && fmrxd_work_bytes(false, 32, 1025, 0, 4)
+	== 32 + 2 * 4112 + fmd_work_bytes(1025), "a partial grid step behind each array");
+static_assert(fmrx_c16_layout(24, 1023).x == 32 && fmrx_c16_layout(24, 1023).y == 32 + 2048
+	&& fmrx_c16_work_bytes(false, 24, 1023) == 32 + 4096, "the twin's size rounded up");
+static_assert(fmxd_layout(48, 4, 2).ty == 64 && fmxd_work_bytes(false, 48, 4, 2) == 80,
+	"two arrays of one grid step");
+static_assert(fmx16_layout(16, 1).oy == 16 + 48 && fmx16_layout(16, 1).end == 16 + 64,
+	"four widened arrays");
+
 int main()
 {
+	layouts();
 	cuts<cordic_fmrx_job>();
 	cuts<cordic_fmrx_job16>();
 	checks<cordic_fmrx_job>();
@@ -415,10 +555,15 @@ def test_the_rx_rule_and_the_job_checks_under_address_and_ub_sanitizers(tmp_path
 
 def test_the_prologue_and_the_chooser_are_shared_not_pasted():
     """one block prologue and one instance chooser for fm_mix_xydir,
-    fm_mixbank_xydir, fm_rx_xydir and fm_rxbank_xydir, in cordic_fm_mix.h"""
+    fm_mixbank_xydir, fm_rx_xydir, fm_rxbank_xydir and their decimating forms, in
+    cordic_fm_mix.h; one list of the receiver's units, in cordic_fm_rx_unit.h"""
+    import glob
     csrc = os.path.join(ROOT, "cordic_amd", "csrc")
+    receivers = ("cordic_fm_rx.hip", "cordic_fm_rx_bank.hip", "cordic_fm_rx_decim.hip",
+                 "cordic_fm_rx_bank_decim.hip")
     names = ("cordic_fm_mix.h", "cordic_fm_rx.h", "cordic_fm_demod.h", "cordic_fm_mix.hip",
-             "cordic_fm_mix_bank.hip", "cordic_fm_rx.hip", "cordic_fm_rx_bank.hip")
+             "cordic_fm_mix_bank.hip") + receivers + (
+             "cordic_fm_mix_decim.hip", "cordic_fm_mix_bank_decim.hip")
     text = {n: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, n)).read()) for n in names}
 
     def places(pattern):
@@ -438,3 +583,36 @@ def test_the_prologue_and_the_chooser_are_shared_not_pasted():
         assert not re.search(r"switch\s*\(nlive\)", text[unit]), unit
     # "WW 35 is LJ 29" and "no Io16 at WW 35" have one home
     assert places(r"ww\s*(==|<|>=)\s*35") == ["cordic_fm_mix.h"] * 2
+
+    # the receiver's units: no ladder over a unit macro in the four sources ...
+    for unit in receivers:
+        assert not re.search(r"#\s*elif[^\n]*UNIT", text[unit]), unit
+        assert not re.search(r"#\s*define\s+CORDIC_FM\w*_UNIT\b", text[unit]), unit
+        assert '#include "cordic_fm_rx_unit.h"' in text[unit], unit
+    # ... the list defined once and expanded, never written out again: a suffix
+    # behind the first stands in the list and nowhere else in the sources
+    every = {os.path.basename(f): re.sub(r"//[^\n]*", "", open(f).read())
+             for f in glob.glob(os.path.join(csrc, "*")) if f.endswith((".h", ".hip", ".cpp"))}
+    defs = [n for n, t in every.items() for _ in re.finditer(r"#\s*define\s+CORDIC_FMRX_UNITS\b", t)]
+    assert defs == ["cordic_fm_rx_unit.h"]
+    unit_h = every["cordic_fm_rx_unit.h"]
+    entries = re.findall(r"\bX\((\w+), (\d+), ([\w:]+)\)", unit_h[unit_h.index("CORDIC_FMRX_UNITS(X)"):]
+                         .split("\n\n")[0])
+    assert entries == [("lj30", "30", "Io32"), ("lj29", "29", "Io32"), ("io16", "30", "Io16"),
+                       ("c16", "30", "fmx::IoC16")]
+    assert "static_assert(fmx::unit_of(" in unit_h       # each position pinned to fmx::Unit
+    for n, t in every.items():
+        if n.startswith("cordic_fm_rx") or n == "cordic_fm_mix.h":
+            hits = re.findall(r"\blaunch_rx\w*_(?:lj30|lj29|io16|c16)\b", t)
+            assert not hits, (n, hits)
+    for unit in ("cordic_fm_rx.hip", "cordic_fm_rx_bank.hip"):
+        assert len(re.findall(r"CORDIC_FMRX_UNITS\((?:PLAIN|DECIM)\)", text[unit])) == 2, unit
+    # ... no entry point named in a brace-initialised array
+    for n, t in every.items():
+        for m in re.finditer(r"=\s*\{[^;]*\}\s*;", t):
+            assert not re.search(r"\blaunch_rx(d|bank)?\w*\b(?!##)", m.group(0)), (n, m.group(0))
+    # ... and no source that only sets the macro and includes another
+    for tail in ("lj29", "io16", "c16"):
+        assert not glob.glob(os.path.join(csrc, "cordic_fm_rx*_%s.hip" % tail)), tail
+    make = open(os.path.join(csrc, "Makefile")).read()
+    assert make.count("-DCORDIC_FMRX_UNIT=") == 1

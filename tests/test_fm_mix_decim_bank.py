@@ -47,10 +47,11 @@ class Jobs:
     """the host side of a bank: per job tuning words, optional pm, samples, an
     optional preset d_acc word and a phase0 whose sum with it wraps"""
 
-    def __init__(self, name, i16, k, seed=60):
+    def __init__(self, name, i16, k, seed=60, ns=None):
         cfg = core(name, i16)
         rng = np.random.default_rng(seed + k)
-        self.name, self.i16, self.k, self.ns = name, i16, k, job_lengths(k)
+        self.name, self.i16, self.k = name, i16, k
+        self.ns = job_lengths(k) if ns is None else list(ns)     # (ns: multiples of R)
         self.fcw, self.pm, self.x, self.y, self.preset, self.phase0 = [], [], [], [], [], []
         for j, n in enumerate(self.ns):
             s = int(rng.integers(0, 1 << 30))

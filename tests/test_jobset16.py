@@ -244,8 +244,8 @@ def test_create16_refusals():
     p17 = ca.Plan(ca.Config.from_cli(ca.P2R, 16, 16, 2, 17, 16))
     assert status(p17, ca.JOBS_P2R_XY, [jb]) == ca.ERR_CONTAINER
     ca.Jobset(p17, ca.JOBS_MIX, [jb]).close()
-    assert status(ca.Plan(ca.Config.from_cli(ca.P2R, 17, 16, 2, 16, 16)), ca.JOBS_MIX,
-                  [jb]) == ca.ERR_CONTAINER
+    iw17 = ca.Plan(ca.Config.from_cli(ca.P2R, 17, 16, 2, 16, 16))
+    assert status(iw17, ca.JOBS_MIX, [jb]) == ca.ERR_CONTAINER
     # an odd byte address; a missing array
     assert status(plan, ca.JOBS_MIX, [dict(jb, x=t.data_ptr() + 1)]) == ca.ERR_ARGS
     assert status(plan, ca.JOBS_MIX, [dict(jb, oy=t.data_ptr() + 33)]) == ca.ERR_ARGS
@@ -254,10 +254,16 @@ def test_create16_refusals():
     ca.Jobset(plan, ca.JOBS_MIX, [dict(jb, x=t[1:17]), dict(jb, n=0, x=None)]).close()
     # a set cut for one core does not run on another
     js = ca.Jobset(plan, ca.JOBS_MIX, [jb])
+    other = ca.Plan(ca.Config.from_cli(*P2R16_PW32))
     with pytest.raises(ca.CordicError) as e:
-        js.run(plan=ca.Plan(ca.Config.from_cli(*P2R16_PW32)))
+        js.run(plan=other)
     assert e.value.status == ca.ERR_ARGS
     js.close()
+    # (closed here, not by the collector: the frames that pytest.raises keeps
+    # hold them in cycles, and a plan destroyed by a collection inside a later
+    # test's global-mode capture invalidates that capture)
+    for p in (plan, pol, p17, iw17, other):
+        p.close()
 
 
 def test_python_picks_the_entry_point_by_the_tensors(monkeypatch):
@@ -288,6 +294,7 @@ def test_python_picks_the_entry_point_by_the_tensors(monkeypatch):
         ca.Jobset(plan, ca.JOBS_MIX, [dict(job(t16), ox=t32[0:16])])
     a.close()
     b.close()
+    plan.close()
 
 
 # ---- one launch, seen from outside the library: the run captured into a HIP

@@ -295,11 +295,16 @@ bool same_core(const cordic_config &a, const cordic_config &b)
 // Tile length (vectors) of the data-fed kinds: whole passes of a 256-thread
 // block, as long as the seeded kernels' tiles where the tile-length rule
 // (cordic_bank_host.h; 8 resident blocks per CU) allows, shorter below.
+// CORDIC_JOBS_TILE_PASSES=<1, 2, 4 or 8> in the environment (read at create; a
+// test and A/B knob like the banks' CORDIC_*_PASSES) forces a tile of that many
+// passes; anything else keeps the rule's choice.  The bits do not depend on it.
 uint32_t xy_tile_vecs(uint64_t total_vecs)
 {
 	const uint64_t per = bank_tile_room(total_vecs, cus_or_256(), 8);
-	return (uint32_t)std::min<uint64_t>(kJobTileVecs,
+	const uint32_t rule = (uint32_t)std::min<uint64_t>(kJobTileVecs,
 		std::max<uint64_t>(kJobPassVecs, per / kJobPassVecs * kJobPassVecs));
+	return kJobPassVecs * bank_forced_passes(std::getenv("CORDIC_JOBS_TILE_PASSES"),
+		kJobTileVecs / kJobPassVecs, rule / kJobPassVecs);
 }
 
 // esize: bytes per sample of every array of the jobs -- 4, or 2 for the sets of

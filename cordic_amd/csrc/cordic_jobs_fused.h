@@ -5,6 +5,19 @@
 // descriptors (TileDescXY) are the ones cordic_jobset_create cuts for every
 // data-fed set.  Host-visible types only.
 //
+// Knobs in the environment, for tests and A/B runs like the banks'
+// CORDIC_*_PASSES and CORDIC_*_MAX_BLOCKS; the bits depend on neither:
+//   CORDIC_JOBS_TILE_PASSES=<1, 2, 4 or 8>, read at create (cordic_abi.cpp:
+//     xy_tile_vecs): the tiles of a data-fed set are that many passes of
+//     kJobPassVecs vectors instead of what the tile-length rule gives; the
+//     seeded kinds keep kJobTileVecs.
+//   CORDIC_JOBS_MAX_BLOCKS=<n>, read at every run (jobs_grid below): at most n
+//     blocks walk the tiles, in launch_xy_jobs_fused and launch_xy_jobs16.
+//     launch_xy_jobs (cordic_kernels.hip: topolar_lj_jobs and the instances of
+//     cordic_inst_xydir_*) keeps its own min(tiles, CUs * 8): that unit is one
+//     of those the committed sweep is stamped with (tools/build_stamp.py), so
+//     its copy is folded into jobs_grid with the next sweep.
+//
 // None of these units holds a kernel of the DESIGN section 4.4 sweep (no swept
 // workload runs a job set), so tools/build_stamp.py does not hash them.
 #ifndef CORDIC_JOBS_FUSED_H
@@ -39,6 +52,10 @@ int	launch_xy_jobs16(const cordic_config &cfg, int kind, const JobTables &tabs,
 // CUs of the current device (< 0: no device), shared by the two launchers
 dev::CoreParams make_params_jobs(const cordic_config &c);
 int	jobs_cus_now();
+// ... and their grid: one block per tile up to the resident blocks, 8 per CU of
+// the current device; a block past that takes every gridDim.x-th tile.  < 0: no
+// device.  CORDIC_JOBS_MAX_BLOCKS=<n> caps it further (see the knobs above).
+int	jobs_grid(uint32_t ntiles);
 
 // ---- launchers of the tile kernels (cordic_jobs_rot.hip, cordic_jobs_rotw.hip,
 // cordic_jobs_pol.hip, cordic_jobs_xydir.hip); false: no instance

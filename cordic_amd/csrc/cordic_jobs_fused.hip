@@ -9,6 +9,7 @@
 #include "cordic_device.h"
 #include "cordic_launch.h"
 #include "cordic_xydir.h"
+#include "cordic_hostargs.h"
 #include "cordic_jobs_fused.h"
 
 namespace cordic_amd {
@@ -52,6 +53,16 @@ int jobs_cus_now()
 	return cus;
 }
 
+int jobs_grid(uint32_t ntiles)
+{
+	const int cus = jobs_cus_now();
+	if (cus < 0)
+		return -1;
+	// resident blocks
+	const size_t cap = env_block_cap("CORDIC_JOBS_MAX_BLOCKS", (size_t)cus * 8);
+	return (int)(ntiles < cap ? ntiles : cap);
+}
+
 int launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &j,
 		const JobTables &tabs, void *stream)
 {
@@ -76,13 +87,11 @@ int launch_xy_jobs_fused(const cordic_config &cfg, int kind, const RotatorJob &j
 		return CORDIC_ERR_UNSUPPORTED;
 	if (tabs.ntiles) {
 		const TileDescXY *tiles = reinterpret_cast<const TileDescXY *>(tabs.tiles);
-		const int cus = jobs_cus_now();
-		if (cus < 0) {
+		const int grid = jobs_grid(tabs.ntiles);
+		if (grid < 0) {
 			(void)hipGetLastError();
 			return CORDIC_ERR_DEVICE;
 		}
-		const uint32_t cap = (uint32_t)cus * 8u;	// resident blocks
-		const int grid = (int)(tabs.ntiles < cap ? tabs.ntiles : cap);
 		// container of the single call: 0 = the 32-bit one (wrap at WW 32),
 		// else left-justified by 30 (WW <= 34) or 64 - WW (WW 35 .. 40)
 		const int lj = cfg.needs_wrap ? 0 : cfg.ww <= 34 ? 30 : 64 - cfg.ww;

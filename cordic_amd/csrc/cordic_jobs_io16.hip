@@ -117,13 +117,12 @@ int launch_xy_jobs16(const cordic_config &cfg, int kind, const JobTables &tabs,
 	kp.xy_nco = kind == CORDIC_JOBS_MIX ? 1u : 0u;
 	if (tabs.ntiles) {
 		const TileDescXY *tiles = reinterpret_cast<const TileDescXY *>(tabs.tiles);
-		const int cus = jobs_cus_now();
-		if (cus < 0) {
+		const int blocks = jobs_grid(tabs.ntiles);
+		if (blocks < 0) {
 			(void)hipGetLastError();
 			return CORDIC_ERR_DEVICE;
 		}
-		const uint32_t cap = (uint32_t)cus * 8u;	// resident blocks
-		const dim3 grid(tabs.ntiles < cap ? tabs.ntiles : cap), block(kBlock);
+		const dim3 grid(blocks), block(kBlock);
 		if (pol && kp.post_mul != 0)
 			hipLaunchKernelGGL((topolar_narrow_tiles<true, Io16>), grid, block, 0, st,
 				kp, tiles, tabs.ntiles);

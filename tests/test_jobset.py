@@ -2,6 +2,9 @@
 launch of the seeded kernel.  Per job the results must be, bit for bit, what
 the oracle computes for that job alone -- ragged lengths, unaligned addresses,
 empty jobs, jobs that end inside a tile, NCO jobs whose sample index wraps."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -231,7 +234,12 @@ def test_bad_jobs_are_refused():
 # oracle's bits.
 
 def xy_tile_vecs(total_vecs):
-    """cordic_abi.cpp: xy_tile_vecs, on cordic_bank_host.h: bank_tile_room"""
+    """cordic_abi.cpp: xy_tile_vecs, on cordic_bank_host.h: bank_tile_room and
+    bank_forced_passes (CORDIC_JOBS_TILE_PASSES = 1, 2, 4 or 8 forces the tile,
+    anything else keeps the rule's; strtol reads the leading integer)"""
+    m = re.match(r"\s*[+-]?\d+", os.environ.get("CORDIC_JOBS_TILE_PASSES", ""))
+    if m and int(m.group()) in (1, 2, 4, 8):
+        return 256 * int(m.group())
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     per = total_vecs // (cus * 8 * 4)
     return min(2048, max(256, per // 256 * 256))

@@ -31,8 +31,9 @@ def both(args, flags=0):
 
 def sizes_of_the_set(rng):
     """about 100 ragged jobs: empty ones, fewer samples than a vector, one
-    vector, trailing samples behind whole vectors, one job longer than the
-    longest tile (8192 samples)"""
+    vector, trailing samples behind whole vectors, one job of several tiles (a
+    set of this size has tiles of one pass, 1024 samples; a tile of the full
+    8192 runs in test_jobset_instances.py, under CORDIC_JOBS_TILE_PASSES)"""
     fixed = [0, 1, 3, 4, 5, 255 * 4 + 2, 8192 * 2 + 4097, 0, 2, 1024, 1027]
     more = [int(v) for v in rng.randint(0, 3000, 100 - len(fixed))]
     sizes = fixed + more
@@ -69,12 +70,13 @@ def put(view, host):
 
 
 class Set16:
-    """the arrays of one set; fill() writes new inputs into the same arrays"""
+    """the arrays of one set (jobs of `sizes`, else of sizes_of_the_set);
+    fill() writes new inputs into the same arrays"""
 
-    def __init__(self, kind, cfg, seed):
+    def __init__(self, kind, cfg, seed, sizes=None):
         self.kind, self.cfg = kind, cfg
         rng = np.random.RandomState(seed)
-        self.sizes = sizes_of_the_set(rng)
+        self.sizes = sizes_of_the_set(rng) if sizes is None else list(sizes)
         nj = len(self.sizes)
         odd = [int(v) | 1 for v in rng.randint(0, 8, nj)]
         self.xv, _ = carve16(self.sizes, odd)
@@ -142,11 +144,12 @@ class Set16:
                    a, b, n=n)
         return a, b
 
-    def check(self, ocfg, gain, tag):
+    def check(self, ocfg, gain, tag, want=None):
+        """want: per job what self.want gives, where the caller has it already"""
         for k, jb in enumerate(self.jobs):
             if not jb["n"]:
                 continue
-            wa, wb = self.want(ocfg, k, gain)
+            wa, wb = want[k] if want else self.want(ocfg, k, gain)
             ga, gb = self.av[k].cpu().numpy(), self.bv[k].cpu().numpy()
             assert np.array_equal(ga, wa), (tag, k, jb["n"])
             assert np.array_equal(gb, wb), (tag, k, jb["n"])

@@ -21,7 +21,7 @@ from ._native import (  # noqa: F401
     lib, lib_path,
     p2r, p2r_const, nco, mix, r2p, fm_workspace, phase_accumulate,
     fm_demod_workspace, fm_demod_info, fm_demod16_info, fm_demod, DemodBank,
-    DemodBank16, MixBank, MixBank16, RxBank, RxBank16, RxBankC16, FmBank,
+    DemodBank16, MixBank, MixBank16, MixBankC16, RxBank, RxBank16, RxBankC16, FmBank,
     p2r_host, r2p_host, HostArray, host_last_stats, host_release,
     host_set_devices, host_lane_stats,
     fill_phase_ramp, fill_iq_ramp, digest_u32,
@@ -33,6 +33,6 @@ __all__ = [
     "p2r", "p2r_const", "nco", "r2p", "p2r_host", "r2p_host",
     "fm_workspace", "phase_accumulate",
     "fm_demod_workspace", "fm_demod_info", "fm_demod16_info", "fm_demod",
-    "DemodBank", "DemodBank16", "MixBank", "MixBank16", "RxBank", "RxBank16", "RxBankC16", "FmBank",
+    "DemodBank", "DemodBank16", "MixBank", "MixBank16", "MixBankC16", "RxBank", "RxBank16", "RxBankC16", "FmBank",
     "fill_phase_ramp", "fill_iq_ramp", "digest_u32",
 ]

@@ -351,6 +351,27 @@ ABI = {
                                         C.POINTER(C.c_void_p)]),
     "cordic_mixbank_create16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.POINTER(C.c_void_p)]),
+    "cordic_plan_fm_mix_c16_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32)]),
+    "cordic_plan_fm_mix_c16_workspace": (C.c_size_t, [C.c_void_p, C.c_size_t]),
+    "cordic_plan_fm_mix_c16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "cordic_plan_fm_mix_decim_c16_workspace": (C.c_size_t, [C.c_void_p,
+                                                            C.c_size_t,
+                                                            C.c_uint32]),
+    "cordic_plan_fm_mix_decim_c16": (C.c_int, [C.c_void_p, C.c_size_t,
+                                               C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_uint32,
+                                               C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    "cordic_mixbank_create_c16": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.POINTER(C.c_void_p)]),
+    "cordic_mixbank_create_decim_c16": (C.c_int, [C.c_void_p, C.c_uint32,
+                                                  C.c_size_t, C.c_void_p,
+                                                  C.POINTER(C.c_void_p)]),
     "cordic_mixbank_destroy": (None, [C.c_void_p]),
     "cordic_mixbank_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint32),
@@ -779,6 +800,56 @@ class Plan:
         _same16("cordic_plan_fm_mix_decim16", x, y, ox, oy)
         self._fm_mix_decim("fm_mix_decim16", log2r, fcw, x, y, ox, oy, work, pm,
                            n, phase0, acc, stream)
+
+    def fm_mix_c16_info(self):
+        """cordic_plan_fm_mix_c16_info: (fused, tile) of fm_mix_c16 on this
+        plan -- fused where fm_mix16 is"""
+        fused, tile = C.c_int32(0), C.c_int32(0)
+        _check(lib().cordic_plan_fm_mix_c16_info(self._h, C.byref(fused),
+                                                 C.byref(tile)),
+               "cordic_plan_fm_mix_c16_info")
+        return int(fused.value), int(tile.value)
+
+    def fm_mix_c16_workspace(self, n):
+        """cordic_plan_fm_mix_c16_workspace: bytes of device scratch an
+        fm_mix_c16 call of n complex samples needs"""
+        return int(lib().cordic_plan_fm_mix_c16_workspace(self._h, n))
+
+    def fm_mix_decim_c16_workspace(self, n, log2r):
+        """cordic_plan_fm_mix_decim_c16_workspace: the same for
+        fm_mix_decim_c16 at R = 2**log2r; 0 where the call would fail"""
+        return int(lib().cordic_plan_fm_mix_decim_c16_workspace(self._h, n,
+                                                                log2r))
+
+    def _fm_mix_c16(self, cname, wsize, args, fcw, iq, oiq, work, pm, n, phase0,
+                    acc, stream):
+        _same16(cname, iq, oiq)
+        n = iq.numel() // 2 if n is None else n
+        if hasattr(iq, "numel") and iq.numel() < 2 * n:
+            raise ValueError("%s: iq holds %d shorts, 2 n = %d"
+                             % (cname, iq.numel(), 2 * n))
+        _need_work(work, n, wsize, n, *args)
+        _check(getattr(lib(), cname)(
+            self._h, n, *args, _ptr(fcw), _ptr(pm), phase0 & 0xffffffff,
+            _ptr(acc), _ptr(iq), _ptr(oiq), _ptr(work), _stream(stream)), cname)
+
+    def fm_mix_c16(self, fcw, iq, oiq, work=None, pm=None, n=None, phase0=0,
+                   acc=None, stream=None):
+        """cordic_plan_fm_mix_c16: fm_mix16 on INTERLEAVED int16 I/Q, in and
+        out -- iq and oiq are int16 tensors of 2 n elements, I0 Q0 I1 Q1 ..
+        The bits of fm_mix16 on iq[0::2], iq[1::2] in oiq[0::2], oiq[1::2].
+        n None: iq.numel() // 2.  work: fm_mix_c16_workspace(n) bytes."""
+        self._fm_mix_c16("cordic_plan_fm_mix_c16", self.fm_mix_c16_workspace,
+                         (), fcw, iq, oiq, work, pm, n, phase0, acc, stream)
+
+    def fm_mix_decim_c16(self, log2r, fcw, iq, oiq, work=None, pm=None, n=None,
+                         phase0=0, acc=None, stream=None):
+        """cordic_plan_fm_mix_decim_c16: fm_mix_decim16 on interleaved int16
+        I/Q (iq: 2 n shorts); oiq holds 2 (n >> log2r) shorts.  work:
+        fm_mix_decim_c16_workspace(n, log2r) bytes."""
+        self._fm_mix_c16("cordic_plan_fm_mix_decim_c16",
+                         self.fm_mix_decim_c16_workspace, (log2r,), fcw, iq,
+                         oiq, work, pm, n, phase0, acc, stream)
 
     def fm_rx_workspace(self, conv, n):
         """cordic_plan_fm_rx_workspace: bytes of device scratch an fm_rx call
@@ -2276,7 +2347,8 @@ class _CFmMixJob(C.Structure):
 _FMMIX_KEYS = ("fcw", "pm", "x", "y", "ox", "oy", "n", "phase0", "acc")
 # a job key that is a tensor or a device address, and its field in the C struct
 _JOB_FIELDS = {"fcw": "d_fcw", "pm": "d_pm", "x": "d_xval", "y": "d_yval",
-               "ox": "d_oxval", "oy": "d_oyval", "iq": "d_iq", "mag": "d_omag",
+               "ox": "d_oxval", "oy": "d_oyval", "iq": "d_iq", "oiq": "d_oiq",
+               "mag": "d_omag",
                "freq": "d_ofreq", "acc": "d_acc", "last": "d_last"}
 
 
@@ -2373,6 +2445,39 @@ class MixBank16(MixBank):
                 else tuple(jb)
             _same16(self._create, *jb[2:6])
         MixBank.__init__(self, plan, jobs, log2r)
+
+
+class _CFmMixJobC16(C.Structure):
+    """cordic_fmmix_job_c16"""
+    _fields_ = [("d_fcw", C.c_void_p), ("d_pm", C.c_void_p),
+                ("d_iq", C.c_void_p), ("d_oiq", C.c_void_p),
+                ("d_acc", C.c_void_p), ("n", C.c_uint64),
+                ("phase0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+_FMMIX_C16_KEYS = ("fcw", "pm", "iq", "oiq", "n", "phase0", "acc")
+
+
+class MixBankC16(_SpanBank):
+    """cordic_mixbank_create_c16: a MixBank of fm_mix_c16 jobs on INTERLEAVED
+    int16 I/Q, in and out.  jobs: tuples (fcw, pm, iq, oiq, n, phase0, acc) or
+    dicts with those keys; iq and oiq are int16 tensors (or device addresses)
+    of 2 n and 2 (n >> log2r) shorts, I0 Q0 I1 Q1 ..; fcw, pm and acc stay
+    32-bit; n None: fcw.numel().  log2r = k > 0
+    (cordic_mixbank_create_decim_c16): a bank of fm_mix_decim_c16 jobs.  info,
+    run and close are MixBank's: the handle is an ordinary cordic_mixbank."""
+
+    _prefix = "cordic_mixbank"
+    _create = "cordic_mixbank_create_c16"
+    _create_decim = "cordic_mixbank_create_decim_c16"
+    _keys, _job = _FMMIX_C16_KEYS, _CFmMixJobC16
+
+    def __init__(self, plan, jobs, log2r=0):
+        for jb in jobs:
+            jb = tuple(jb.get(k) for k in _FMMIX_C16_KEYS) if isinstance(jb, dict) \
+                else tuple(jb)
+            _same16(self._create, *jb[2:4])
+        self._open(plan, (), jobs, log2r or None)
 
 
 class _CFmRxJob(C.Structure):

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdlib>
+#include <new>
 #include <vector>
 
 #include "cordic_abi_plan.h"
@@ -191,10 +192,17 @@ static bool fm_mix_decim_fused(const cordic_plan *plan, FmForm f)
 }
 
 // a plan that the call accepts; 0 where the call would fail.  (k = 0: the
-// mixer's own workspace, whatever `fused` says.)
+// mixer's own workspace, whatever `fused` says.)  An interleaved form: the
+// twin's where it is fused, else the twin's fallback with the four split arrays
+// behind it (fmx_c16_layout).
 static size_t fm_mix_decim_work_bytes(const cordic_plan *plan, FmForm f, bool fused,
 		size_t n)
 {
+	if (f.iq) {
+		const bool fu = f.log2r ? fused : fm_mix_fused(plan, f);
+		const size_t twin = fm_mix_decim_work_bytes(plan, f.split(), fu, n);
+		return twin ? fmx_c16_work_bytes(fu, twin, n, f.log2r) : 0;
+	}
 	const size_t mix = fm_mix_work_bytes(plan, f, n);
 	if (!fmxd_shape_ok(n, f.log2r))
 		return 0;
@@ -204,10 +212,53 @@ static size_t fm_mix_decim_work_bytes(const cordic_plan *plan, FmForm f, bool fu
 static int fm_mix_decim(const cordic_plan *plan, FmForm f, size_t n,
 		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
 		const void *d_xval, const void *d_yval, void *d_oxval, void *d_oyval,
+		void *d_work, void *stream, bool fused);
+
+// The interleaved forms (f.iq; the shape is checked): d_iq and d_oiq.  k = 0 is
+// the plain call, on the plan's own path; `fused` is a decimating call's.
+static int fm_mix_iq(const cordic_plan *plan, FmForm f, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const void *d_iq,
+		void *d_oiq, void *d_work, void *stream, bool fused)
+{
+	if (n == 0)
+		return CORDIC_OK;
+	if (!f.log2r)
+		fused = fm_mix_fused(plan, f);
+	if (int rc = fmx_check_call(n, d_fcw, d_pm, d_acc, d_iq, nullptr, d_oiq, nullptr,
+			f.esize(), d_work, fm_mix_decim_work_bytes(plan, f, fused, n), f.log2r, true))
+		return rc;
+	if (fused)
+		return launch_fm_mix(plan->cfg, plan->d_dir, plan->dx, n, d_fcw, d_pm, phase0,
+			d_acc, d_iq, nullptr, d_oiq, nullptr, f.esize(), d_work, stream, f.log2r, true);
+	// the fallback: one split launch into two arrays behind the twin's
+	// workspace, the twin itself from them into two more, one interleave launch
+	const FmForm twin = f.split();
+	const FmxC16Layout at = fmx_c16_layout(fm_mix_decim_work_bytes(plan, twin, false, n), n,
+		f.log2r);
+	int16_t *x = reinterpret_cast<int16_t *>(bytes_at(d_work, at.x));
+	int16_t *y = reinterpret_cast<int16_t *>(bytes_at(d_work, at.y));
+	int16_t *ox = reinterpret_cast<int16_t *>(bytes_at(d_work, at.ox));
+	int16_t *oy = reinterpret_cast<int16_t *>(bytes_at(d_work, at.oy));
+	if (int rc = launch_fmrx_split_c16(n, static_cast<const int16_t *>(d_iq), x, y, stream))
+		return rc;
+	if (int rc = fm_mix_decim(plan, twin, n, d_fcw, d_pm, phase0, d_acc, x, y, ox, oy,
+			d_work, stream, false))
+		return rc;
+	return launch_fmx_interleave_c16(n >> f.log2r, ox, oy, static_cast<int16_t *>(d_oiq),
+		stream);
+}
+
+// f.iq: d_xval is d_iq, d_oxval is d_oiq, d_yval and d_oyval are not looked at
+static int fm_mix_decim(const cordic_plan *plan, FmForm f, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const void *d_xval, const void *d_yval, void *d_oxval, void *d_oyval,
 		void *d_work, void *stream, bool fused)
 {
 	if (!fmxd_shape_ok(n, f.log2r))
 		return CORDIC_ERR_ARGS;
+	if (f.iq)
+		return fm_mix_iq(plan, f, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_oxval, d_work,
+			stream, fused);
 	if (f.log2r == 0 || n == 0)	// the mixer itself: its bits, its launches
 		return fm_mix_call(plan, f, n, d_fcw, d_pm, phase0, d_acc, d_xval, d_yval,
 			d_oxval, d_oyval, d_work, stream);
@@ -268,11 +319,59 @@ int cordic_plan_fm_mix_decim16(const cordic_plan *plan, size_t n, uint32_t log2r
 		d_oyval, d_work, stream, fm_mix_decim_fused(plan, f));
 }
 
+// ---- the mixer on interleaved int16 I/Q, in and out: the *16 twins with d_iq
+// and d_oiq in the place of the four sample pointers (cordic_fm_mix.h)
+int cordic_plan_fm_mix_c16_info(const cordic_plan *plan, int32_t *fused, int32_t *tile)
+{
+	if (int rc = fm_mix_ok(plan, kFormC16))
+		return rc;
+	const bool f = fm_mix_fused(plan, kFormC16);
+	if (fused)
+		*fused = f ? 1 : 0;
+	if (tile)
+		*tile = f ? (int32_t)kFmxPass : 0;
+	return CORDIC_OK;
+}
+
+size_t cordic_plan_fm_mix_decim_c16_workspace(const cordic_plan *plan, size_t n,
+		uint32_t log2r)
+{
+	const FmForm f = decim(kFormC16, log2r);
+	if (fm_mix_ok(plan, f) != CORDIC_OK)
+		return 0;
+	return fm_mix_decim_work_bytes(plan, f, fm_mix_decim_fused(plan, f), n);
+}
+
+size_t cordic_plan_fm_mix_c16_workspace(const cordic_plan *plan, size_t n)
+{
+	return cordic_plan_fm_mix_decim_c16_workspace(plan, n, 0);
+}
+
+int cordic_plan_fm_mix_decim_c16(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc,
+		const int16_t *d_iq, int16_t *d_oiq, void *d_work, void *stream)
+{
+	const FmForm f = decim(kFormC16, log2r);
+	if (int rc = fm_mix_ok(plan, f))
+		return rc;
+	return fm_mix_decim(plan, f, n, d_fcw, d_pm, phase0, d_acc, d_iq, nullptr, d_oiq,
+		nullptr, d_work, stream, fm_mix_decim_fused(plan, f));
+}
+
+int cordic_plan_fm_mix_c16(const cordic_plan *plan, size_t n, const uint32_t *d_fcw,
+		const uint32_t *d_pm, uint32_t phase0, uint32_t *d_acc, const int16_t *d_iq,
+		int16_t *d_oiq, void *d_work, void *stream)
+{
+	return cordic_plan_fm_mix_decim_c16(plan, n, 0, d_fcw, d_pm, phase0, d_acc, d_iq,
+		d_oiq, d_work, stream);
+}
+
 // ---- FM mixer banks: many of those jobs in two launches
 // (cordic_fm_mix_bank.h)
 struct cordic_mixbank : BankHandle<cordic_fmmix_job> {
 	const cordic_plan *plan = nullptr;	// the caller's; outlives the bank
-	FmForm	form;				// the jobs' container; log2r > 0: a decimating bank
+	FmForm	form;				// the jobs' container; iq: d_xval / d_oxval are
+						// interleaved I/Q (_c16); log2r > 0: a decimating bank
 	uint32_t passes = 0;
 	SpanTable<MixSpan> spans;		// fused
 };
@@ -333,12 +432,12 @@ static int plan_bank_create(const cordic_plan *plan, size_t njobs, Jobs jobs, Fm
 	return CORDIC_OK;
 }
 
-// all four creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h;
+// all six creates: `jobs` is either job struct (MixJobs, cordic_fm_mix_bank.h;
 // no jobs at all: the 32-bit rules)
 static int mixbank_create(const cordic_plan *plan, size_t njobs, MixJobs jobs,
 		cordic_mixbank **bank)
 {
-	const FmForm f = decim(jobs.j16 ? kForm16 : kForm32, jobs.log2r);
+	const FmForm f = {jobs.j16 ? 2u : 4u, jobs.iq, jobs.log2r};
 	return plan_bank_create<MixBankTraits>(plan, njobs, jobs, f, bank,
 		[&] { return fm_mix_ok(plan, f); }, [&] { return fm_mix_fused(plan, f); },
 		[&](size_t n) { return fm_mix_decim_work_bytes(plan, f, false, n); },
@@ -367,6 +466,44 @@ int cordic_mixbank_create_decim16(const cordic_plan *plan, uint32_t log2r, size_
 		const cordic_fmmix_job16 *jobs, cordic_mixbank **bank)
 {
 	return mixbank_create(plan, njobs, MixJobs(jobs, log2r), bank);
+}
+
+// the interleaved creates: the jobs as 16-bit ones whose d_xval is d_iq and
+// whose d_oxval is d_oiq (fmxb_from_c16); the checks keep mixbank_create's order
+static int mixbank_create_c16(const cordic_plan *plan, uint32_t log2r, size_t njobs,
+		const cordic_fmmix_job_c16 *jobs, cordic_mixbank **bank)
+{
+	if (!bank || (njobs && !jobs))
+		return CORDIC_ERR_ARGS;
+	// the plan, its mode and its container, then the count, as mixbank_create
+	// has them -- in front of the copy, which is then at most 2^28 jobs
+	if (int rc = fm_mix_ok(plan, kFormC16))
+		return rc;
+	if (njobs >= ((size_t)1 << 28))
+		return CORDIC_ERR_ARGS;
+	std::vector<cordic_fmmix_job16> split;
+	try {
+		split.resize(njobs + 1);
+	} catch (const std::bad_alloc &) {	// (nothing is thrown across the C ABI)
+		return CORDIC_ERR_NOMEM;
+	}
+	for (size_t k = 0; k < njobs; k++)
+		split[k] = fmxb_from_c16(jobs[k]);
+	// (NULL jobs with njobs == 0: NULL on, as _create16 would see it)
+	const cordic_fmmix_job16 *j16 = jobs ? split.data() : nullptr;
+	return mixbank_create(plan, njobs, MixJobs(j16, log2r, true), bank);
+}
+
+int cordic_mixbank_create_c16(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job_c16 *jobs, cordic_mixbank **bank)
+{
+	return mixbank_create_c16(plan, 0, njobs, jobs, bank);
+}
+
+int cordic_mixbank_create_decim_c16(const cordic_plan *plan, uint32_t log2r, size_t njobs,
+		const cordic_fmmix_job_c16 *jobs, cordic_mixbank **bank)
+{
+	return mixbank_create_c16(plan, log2r, njobs, jobs, bank);
 }
 
 void cordic_mixbank_destroy(cordic_mixbank *bank)
@@ -400,9 +537,10 @@ int cordic_mixbank_run(const cordic_mixbank *bank, void *stream)
 	return bank_run(*bank, [&] {
 		const SpanTable<MixSpan> &t = bank->spans;
 		return launch_fmx_bank(plan->cfg, plan->d_dir, plan->dx, t.d_spans, t.nspans,
-			t.start(), t.part(), bank->cus, f.io16(), stream, f.log2r);
+			t.start(), t.part(), bank->cus, f.io16(), stream, f.log2r, f.iq);
 	}, [&](const cordic_fmmix_job &jb) {
-		// (log2r 0: the mixer's own call, cordic_plan_fm_mix or _mix16)
+		// (log2r 0: the mixer's own call, cordic_plan_fm_mix or _mix16; an
+		// interleaved job's d_xval / d_oxval carry its d_iq / d_oiq)
 		return fm_mix_decim(plan, f, (size_t)jb.n, jb.d_fcw, jb.d_pm, jb.phase0,
 			jb.d_acc, jb.d_xval, jb.d_yval, jb.d_oxval, jb.d_oyval, bank->d_work, stream,
 			false);
@@ -458,8 +596,9 @@ static size_t fm_rx_work_bytes(const cordic_plan *plan, const cordic_config *con
 		return 0;
 	const bool fused = !one_by_one && fm_rx_fused(plan, conv, f);
 	const bool mix_fused = !one_by_one && f.log2r && fm_mix_decim_fused(plan, f);
+	// (the mixer call of the fallback is the split one's, whatever the input)
 	const size_t twin = fmrxd_work_bytes(fused,
-		fm_mix_decim_work_bytes(plan, f, mix_fused, n), n, f.log2r, f.esize());
+		fm_mix_decim_work_bytes(plan, f.split(), mix_fused, n), n, f.log2r, f.esize());
 	return f.iq ? fmrx_c16_work_bytes(fused, twin, n) : twin;
 }
 

@@ -104,10 +104,13 @@ static_assert(kFmxWorkBytes % 16 == 0, "the widened arrays sit on the 16-byte gr
 // no output range (d_acc and the `work_bytes` of d_work included) over
 // anything else, by the true byte ranges; nothing is launched.  n > 0.  log2r:
 // the two outputs hold n >> log2r elements (the decimating mixer).
+// iq (the *_c16 mixers): d_xval is the one interleaved input (4 n bytes) and
+// d_oxval the one interleaved output (4 (n >> log2r) bytes), both on the grid of
+// a complex sample; d_yval and d_oyval are not looked at.
 int	fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
-		size_t work_bytes, uint32_t log2r = 0);
+		size_t work_bytes, uint32_t log2r = 0, bool iq = false);
 
 // The fused path: two launches on `stream` (fm_reduce, then fm_mix_xydir),
 // nothing else.  The sample arrays hold int32 (esize 4) or int16 (esize 2).
@@ -117,7 +120,8 @@ int	fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 int	launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
 		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
-		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r = 0);
+		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r = 0,
+		bool iq = false);
 
 // ---- the decimating mixer (cordic_plan_fm_mix_decim, _decim16), k = log2r in
 // 1 .. 8 and n a multiple of 2^k.  Fused where the mixer is, with the mixer's
@@ -161,6 +165,33 @@ int	launch_fmx_widen(size_t n, const int16_t *d_x, const int16_t *d_y,
 		int32_t *d_wx, int32_t *d_wy, void *stream);
 int	launch_fmx_narrow(size_t n, const int32_t *d_wox, const int32_t *d_woy,
 		int16_t *d_ox, int16_t *d_oy, void *stream);
+
+// ---- the mixers on INTERLEAVED int16 I/Q, in and out (cordic_plan_fm_mix_c16,
+// _decim_c16, cordic_mixbank_create_c16 / _create_decim_c16): the *16 twins with
+// d_iq (complex sample i is the dword at d_iq + 2 i, I in its low half) in the
+// place of d_xval / d_yval and d_oiq in that of d_oxval / d_oyval.  Fused where
+// the twin is, with the twin's launches and workspace: launch_fm_mix with iq,
+// whose launch 2 is a <30, N, IoC16io> instance (below).  The fallback is [the
+// twin's workspace | x | y of n shorts | ox | oy of n >> k shorts], each part on
+// the 16-byte grid: one split launch (launch_fmrx_split_c16, cordic_fm_rx.h),
+// the twin, one interleave launch.
+struct FmxC16Layout {
+	size_t	x, y, ox, oy, end;	// byte offsets in d_work
+};
+constexpr FmxC16Layout fmx_c16_layout(size_t twin_bytes, size_t n, uint32_t log2r)
+{
+	const size_t at = (twin_bytes + 15) & ~(size_t)15;
+	const size_t in = fmxd_array_bytes(n, 2), out = fmxd_array_bytes(n >> log2r, 2);
+	return FmxC16Layout{at, at + in, at + 2 * in, at + 2 * in + out,
+		at + 2 * in + 2 * out};
+}
+constexpr size_t fmx_c16_work_bytes(bool fused, size_t twin_bytes, size_t n, uint32_t log2r)
+{
+	return !n || fused ? twin_bytes : fmx_c16_layout(twin_bytes, n, log2r).end;
+}
+// d_oiq[2 j], d_oiq[2 j + 1] = d_ox[j], d_oy[j], j < m; d_oiq on the 4-byte grid
+int	launch_fmx_interleave_c16(size_t m, const int16_t *d_ox, const int16_t *d_oy,
+		int16_t *d_oiq, void *stream);
 
 } // namespace cordic_amd
 
@@ -397,12 +428,40 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v, const uint32_t g,
 // + k bits; it travels as sum(v >> k), below 2^31 in magnitude, and sum(v & (R
 // - 1)), below 2^16: floor(S / R) = the first + (the second >> k).  Plain
 // stores: non-temporal ones measured the same (profiles/r22/ab_nt_stores.txt).
-template <typename T>
+//
+// OIQ (the interleaved output of IoC16io, below): ox is d_oiq, output j is the
+// dword at ox + 2 j, packed (I | Q << 16), and oy is not looked at.  k = 1: the
+// lane's two outputs are one 8-byte store (hi is a multiple of 2 only: where i +
+// 2 == hi the one dword); k >= 2: one dword where the split form has two 2-byte
+// stores.
+__device__ __forceinline__ uint32_t pack_iq(int32_t re, int32_t im)
+{
+	return ((uint32_t)re & 0xffffu) | ((uint32_t)im << 16);
+}
+
+template <bool OIQ = false, typename T>
 __device__ __forceinline__ void store_decim(const i32x4 &rx, const i32x4 &ry, T *ox,
 		T *oy, const size_t i, const size_t hi, const uint32_t k, const unsigned tid)
 {
 	if (k == 1) {		// two outputs per lane
 		const size_t o = i >> 1;
+		if constexpr (OIQ) {
+			typedef u32x2 u32x2g __attribute__((aligned(4)));
+			u32x2 d;
+#pragma unroll
+			for (int h = 0; h < 2; h++) {
+				const int32_t a = rx[2 * h], b = rx[2 * h + 1];
+				const int32_t c = ry[2 * h], e = ry[2 * h + 1];
+				d[h] = pack_iq((a >> 1) + (b >> 1) + (((a & 1) + (b & 1)) >> 1),
+					(c >> 1) + (e >> 1) + (((c & 1) + (e & 1)) >> 1));
+			}
+			uint32_t *o2 = reinterpret_cast<uint32_t *>(ox) + o;
+			if (i + kVec <= hi)
+				*reinterpret_cast<u32x2g *>(o2) = d;
+			else if (i < hi)
+				o2[0] = d[0];
+			return;
+		}
 #pragma unroll
 		for (int h = 0; h < 2; h++) {
 			if (i + 2 * h < hi) {
@@ -432,8 +491,13 @@ __device__ __forceinline__ void store_decim(const i32x4 &rx, const i32x4 &ry, T 
 		ly = group_sum(ly, g, lane);
 	}
 	if ((lane & (g - 1u)) == g - 1u && i < hi) {
-		ox[i >> k] = (T)(int32_t)(hx + (lx >> k));
-		oy[i >> k] = (T)(int32_t)(hy + (ly >> k));
+		if constexpr (OIQ) {
+			reinterpret_cast<uint32_t *>(ox)[i >> k] = pack_iq(
+				(int32_t)(hx + (lx >> k)), (int32_t)(hy + (ly >> k)));
+		} else {
+			ox[i >> k] = (T)(int32_t)(hx + (lx >> k));
+			oy[i >> k] = (T)(int32_t)(hy + (ly >> k));
+		}
 	}
 }
 
@@ -540,8 +604,18 @@ __device__ __forceinline__ RotRegs rot_regs(const CoreParams &kp, const DirArgs 
 struct IoC16 : Io16 {
 	typedef u32x4 cvec __attribute__((aligned(4)));
 };
+// IoC16io: interleaved on BOTH sides (the *_c16 mixers): the input is IoC16's,
+// and the two outputs are one array, complex sample j the dword (I | Q << 16) at
+// oiq + 2 j -- a lane's 4 are ONE 16-byte store at any 4-byte-aligned address,
+// packed in registers (v_and_or / v_lshl_or per sample, the two that narrowing
+// two values to shorts costs Io16); fmx::pass_loop stores them behind
+// is_oiq<IO>, and store_decim one dword per decimated sample.
+struct IoC16io : IoC16 {};
 template <typename IO> struct is_iq : std::false_type {};
 template <> struct is_iq<IoC16> : std::true_type {};
+template <> struct is_iq<IoC16io> : std::true_type {};
+template <typename IO> struct is_oiq : std::false_type {};
+template <> struct is_oiq<IoC16io> : std::true_type {};
 // 4 input samples of one array as they wait in registers (IoC16: of both)
 template <typename IO> struct raw_in {
 	typedef decltype(IO::narrow(i32x4{})) type;
@@ -549,6 +623,7 @@ template <typename IO> struct raw_in {
 template <> struct raw_in<IoC16> {
 	typedef u32x4 type;
 };
+template <> struct raw_in<IoC16io> : raw_in<IoC16> {};
 // a lane's (x, y) from what it loaded
 template <typename IO, typename RAW>
 __device__ __forceinline__ void widen_iq(IO, const RAW &nx, const RAW &ny, i32x4 &tx,
@@ -565,6 +640,11 @@ __device__ __forceinline__ void widen_iq(IoC16, const u32x4 &q, const u32x4 &, i
 		tx[v] = (int32_t)(q[v] << 16) >> 16;
 		ty[v] = (int32_t)q[v] >> 16;
 	}
+}
+__device__ __forceinline__ void widen_iq(IoC16io, const u32x4 &q, const u32x4 &n, i32x4 &tx,
+		i32x4 &ty)
+{
+	widen_iq(IoC16{}, q, n, tx, ty);
 }
 
 // ---- the block's prologue, of all four launch-2 kernels (fm_mix_xydir,
@@ -609,8 +689,11 @@ __device__ __forceinline__ RotRegs block_ready(const CoreParams &kp, const DirAr
 // by pass, so that a pass has ONE barrier; it runs on from call to call.
 // pm may be NULL (wave-uniform).  Nothing at or behind hi is read or written.
 //
-// IO (Io32 / Io16, cordic_device.h; deduced from the tag behind `wave`) is the
-// container of the four sample arrays and of nothing else: a lane's 4 samples
+// IO (Io32 / Io16, cordic_device.h, or IoC16io above; deduced from the tag
+// behind `wave`) is the container of the four sample arrays and of nothing else
+// (IoC16io: ax is d_iq, aox is d_oiq, complex sample i at + 2 i shorts, ay and
+// aoy are not looked at; the load and the store take the paths behind is_iq<IO>
+// and is_oiq<IO>, and for the other two the loop is the code it was): a lane's 4 samples
 // are one 16-byte or one 8-byte access per array, at any element alignment,
 // widened behind the load and narrowed in front of the store; the tuning words
 // and pm are 32-bit words in either, and so is everything in between.  The
@@ -635,7 +718,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 {
 	typedef typename IO::ivec ivec;
 	typedef typename IO::ielem ielem;
-	typedef decltype(IO::narrow(i32x4{})) raw4;	// 4 samples as they lie in memory
+	// 4 samples as they lie in memory (interleaved: 4 complex ones, in x)
+	typedef typename raw_in<IO>::type raw4;
 	// this lane's 4 samples of the pass at t0; nothing at or behind hi is read,
 	// and a tuning word that is not there counts 0
 	auto load_pass = [&](size_t t0, u32x4 &f, u32x4 &m, raw4 &x, raw4 &y) {
@@ -648,8 +732,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 			f = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(fcw + i));
 			if (pm)	// (wave-uniform)
 				m = CORDIC_LOAD_IN(reinterpret_cast<const u32x4g *>(pm + i));
-			x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
-			y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			if constexpr (is_iq<IO>::value) {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const typename IO::cvec *>(ax + 2 * i));
+			} else {
+				x = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ax + i));
+				y = CORDIC_LOAD_IN(reinterpret_cast<const ivec *>(ay + i));
+			}
 		} else if (i < hi) {	// the last, partial vector: one lane of the job
 #pragma unroll
 			for (int v = 0; v < kVec; v++) {
@@ -657,8 +745,12 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 					f[v] = fcw[i + v];
 					if (pm)
 						m[v] = pm[i + v];
-					x[v] = ax[i + v];
-					y[v] = ay[i + v];
+					if constexpr (is_iq<IO>::value) {
+						x[v] = reinterpret_cast<const uint32_t *>(ax)[i + v];
+					} else {
+						x[v] = ax[i + v];
+						y[v] = ay[i + v];
+					}
 				}
 			}
 		}
@@ -669,7 +761,8 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 	load_pass(lo, nf, nm, nx, ny);
 	for (size_t t0 = lo; t0 < hi; t0 += kFmxPass) {
 		const u32x4 f = nf, m = nm;
-		const i32x4 tx = IO::widen(nx), ty = IO::widen(ny);
+		i32x4 tx, ty;
+		widen_iq(IO{}, nx, ny, tx, ty);
 		// the next pass's words are on their way while this one is rotated
 		if (t0 + kFmxPass < hi)
 			load_pass(t0 + kFmxPass, nf, nm, nx, ny);
@@ -702,7 +795,23 @@ __device__ __forceinline__ void pass_loop(const CoreParams &kp, const DirArgs &d
 
 		const size_t i = t0 + (size_t)kVec * tid;
 		if constexpr (DECIM) {
-			store_decim(rx, ry, aox, aoy, i, hi, log2r, tid);
+			store_decim<is_oiq<IO>::value>(rx, ry, aox, aoy, i, hi, log2r, tid);
+		} else if constexpr (is_oiq<IO>::value) {
+			// four packed dwords at aox + 2 i; the last, partial vector dword
+			// by dword
+			u32x4 d;
+#pragma unroll
+			for (int v = 0; v < kVec; v++)
+				d[v] = pack_iq(rx[v], ry[v]);
+			uint32_t *o = reinterpret_cast<uint32_t *>(aox) + i;
+			if (i + kVec <= hi) {
+				CORDIC_STORE_OUT(true, reinterpret_cast<typename IO::cvec *>(o), d);
+			} else if (i < hi) {
+#pragma unroll
+				for (int v = 0; v < kVec; v++)
+					if (i + v < hi)
+						o[v] = d[v];
+			}
 		} else if (i + kVec <= hi) {
 			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aox + i), IO::narrow(rx));
 			CORDIC_STORE_OUT(true, reinterpret_cast<ivec *>(aoy + i), IO::narrow(ry));
@@ -755,7 +864,16 @@ constexpr Unit unit_of(int ww, size_t esize, bool iq)
 	return !iq ? u : u == kUnitIo16 ? kUnitC16 : kUnitNone;
 }
 
-// Calls f(integral_constant<int, LJ>, IO) for the unit; false: none, or f's
+// Calls f(integral_constant<int, LJ>, IO) for the unit; false: none, or f's.
+// kUnitC16 is NOT served here and answers false: its instances live in objects
+// of their own, behind launchers of their own -- the receivers' in
+// cordic_fm_rx_unit.h, the mixers' launch_fm_mix_scan_c16 and its three kin
+// (below, and cordic_fm_mix_bank.h) -- so that a unit that calls with_unit does
+// not instantiate them.  A launcher that can meet kUnitC16 asks for it by name
+// in front of this call (launch_fm_mix, launch_fm_mix_decim_scan,
+// launch_fmx_bank, launch_fmx_bank_decim_walk); one that forgets launches
+// nothing and reports CORDIC_ERR_DEVICE through tnco::finish(false), which the
+// per-instance tests of tests/test_fm_mix_c16.py and _bank.py would show.
 template <typename F>
 bool with_unit(Unit u, F &&f)
 {
@@ -794,9 +912,22 @@ bool with_stages(int nlive, int ngroups, F &&f)
 
 // Launch 2 of a decimating single call, for launch_fm_mix
 // (cordic_fm_mix_decim.hip); false: no instance.
-bool	launch_fm_mix_decim_scan(int ww, int nlive, int ngroups, size_t esize, unsigned grid,
+bool	launch_fm_mix_decim_scan(fmx::Unit unit, int nlive, int ngroups, unsigned grid,
 		size_t lds, void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
 		const fmx::FmxArgs &a, uint32_t log2r);
+
+// Launch 2 on interleaved int16 I/Q, in and out (fmx::kUnitC16; a.x is d_iq,
+// a.ox is d_oiq): the <30, N, IoC16io> instances.  fmx::with_unit does not know
+// them: each of the four mixer sources (cordic_fm_mix.hip, .._decim.hip,
+// .._bank.hip, .._bank_decim.hip) is compiled a second time with
+// -DCORDIC_FMX_C16 into an object of its own, which holds the kernel's 7
+// instances and one launcher -- these two, and the banks' two in
+// cordic_fm_mix_bank.h -- so that they build beside the others.  The plain form
+// ignores log2r.  false: no instance.
+typedef bool FmxScanC16(int nlive, int ngroups, unsigned grid, size_t lds, void *stream,
+		const dev::CoreParams &kp, const dev::DirArgs &da, const fmx::FmxArgs &a,
+		uint32_t log2r);
+FmxScanC16 launch_fm_mix_scan_c16, launch_fm_mix_decim_scan_c16;
 
 } // namespace cordic_amd
 #endif // __HIPCC__

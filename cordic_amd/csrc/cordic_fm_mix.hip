@@ -63,6 +63,7 @@
 //   rotator_xydir<30, N>  89   95   90   90   91   94   94
 //   fm_mix_xydir<30, N>   92   98   95   95  102  103  103
 //   ... <30, N, Io16>     92   96   92   92   99  100  100
+//   ... <30, N, IoC16io>  90   94   91   91   90   93   93
 // The scan costs 3 .. 11 registers: four more words in flight per lane (fcw and
 // pm against the phase) and the carry.  With 512 registers per lane of a SIMD,
 // allocated in eights, up to 96 hold 5 waves and up to 128 hold 4: an occupancy
@@ -85,6 +86,21 @@
 // (global_load_dwordx2 / global_store_dwordx2) at any 2-byte alignment: 16
 // bytes per sample (20 with pm) against 24 (28).  The 16-bit fallback's two
 // elementwise kernels, fmx_widen and fmx_narrow, take 12 registers each.
+//
+// IoC16io (cordic_fm_mix.h; cordic_plan_fm_mix_c16): interleaved int16 I/Q on
+// both sides.  A lane's 4 complex samples are ONE 16-byte load at d_iq + 2 i and
+// ONE 16-byte store of four packed dwords (I | Q << 16) at d_oiq + 2 i, at any
+// 4-byte alignment; the bytes per sample are Io16's.  The 7 instances live in an
+// object of their own -- this source compiled a second time with
+// -DCORDIC_FMX_C16 (the Makefile's FMX_C16_SRCS) holds them and
+// launch_fm_mix_scan_c16 and nothing of the host side -- so that they build
+// beside the others; fmx::with_unit does not know them, launch_fm_mix asks
+// fmx::unit_of(ww, esize, iq) and calls that launcher for kUnitC16.  They take 2
+// .. 9 registers fewer than the Io16 instances (the next pass's samples wait in
+// four registers where Io16 has four in two arrays, and one output address is
+// made where Io16 makes two); nothing spills, and the grid's 4 blocks per CU
+// hold.  The fallback's interleave kernel, fmx_interleave_c16, is one thread per
+// output dword.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -134,6 +150,18 @@ __global__ __launch_bounds__(kBlock) void fm_mix_xydir(CoreParams kp, DirArgs da
 		*a.acc = carry;
 }
 
+// launch 2 for one <LJ, container>; false: no instance for nlive
+template <int LJ, typename IO>
+static bool launch_scan(int nlive, int ngroups, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const FmxArgs &a)
+{
+	return with_stages(nlive, ngroups, [&](auto nl) {
+		hipLaunchKernelGGL((fm_mix_xydir<LJ, decltype(nl)::value, IO>), dim3(grid),
+			dim3(kBlock), lds, st, kp, da, a);
+	});
+}
+
+#ifndef CORDIC_FMX_C16
 // ---------------------------------------------------------------- host side
 // the 16-bit fallback's elementwise kernels
 __global__ __launch_bounds__(kBlock) void fmx_widen(size_t n,
@@ -158,6 +186,16 @@ __global__ __launch_bounds__(kBlock) void fmx_narrow(size_t n,
 	}
 }
 
+// the interleaved forms' fallback: the twin's two output arrays into one
+__global__ __launch_bounds__(kBlock) void fmx_interleave_c16(size_t m,
+		const int16_t *__restrict__ ox, const int16_t *__restrict__ oy,
+		uint32_t *__restrict__ oiq)
+{
+	const size_t stride = (size_t)gridDim.x * kBlock;
+	for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += stride)
+		oiq[j] = pack_iq(ox[j], oy[j]);
+}
+
 // (at most 2^16 blocks, each walking on by the grid)
 static unsigned elementwise_grid(size_t n)
 {
@@ -165,8 +203,22 @@ static unsigned elementwise_grid(size_t n)
 	return (unsigned)(blocks < 65536 ? blocks : 65536);
 }
 
+#endif // CORDIC_FMX_C16
+
 } // namespace fmx
 
+#ifdef CORDIC_FMX_C16
+// This object (cordic_fm_mix_c16.o): the kernel's <30, N, IoC16io> instances and
+// their launcher, nothing of the host side.
+bool launch_fm_mix_scan_c16(int nlive, int ngroups, unsigned grid, size_t lds, void *stream,
+		const dev::CoreParams &kp, const dev::DirArgs &da, const fmx::FmxArgs &a,
+		uint32_t log2r)
+{
+	(void)log2r;
+	return fmx::launch_scan<30, fmx::IoC16io>(nlive, ngroups, grid, lds,
+		static_cast<hipStream_t>(stream), kp, da, a);
+}
+#else
 bool fmx_is_fused(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx)
 {
 	if (!d_dir || dx.n <= 0 || cfg.ww > 35 || cfg.needs_wrap
@@ -189,16 +241,16 @@ bool fmx_is_fused16(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 int fmx_check_call(size_t n, const uint32_t *d_fcw, const uint32_t *d_pm,
 		const uint32_t *d_acc, const void *d_xval, const void *d_yval,
 		const void *d_oxval, const void *d_oyval, size_t esize, const void *d_work,
-		size_t work_bytes, uint32_t log2r)
+		size_t work_bytes, uint32_t log2r, bool iq)
 {
 	return iq_call_ok(n, d_acc, nullptr, d_fcw, d_pm, d_xval, d_yval, d_oxval, d_oyval,
-		esize, d_work, work_bytes, log2r) ? CORDIC_OK : CORDIC_ERR_ARGS;
+		esize, d_work, work_bytes, log2r, iq, iq) ? CORDIC_OK : CORDIC_ERR_ARGS;
 }
 
 int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		size_t n, const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
 		uint32_t *d_acc, const void *d_xval, const void *d_yval, void *d_oxval,
-		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r)
+		void *d_oyval, size_t esize, void *d_work, void *stream, uint32_t log2r, bool iq)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -227,14 +279,17 @@ int launch_fm_mix(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo 
 		span, xw};
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
+	// iq: a.x is d_iq, a.ox is d_oiq, a.y and a.oy are not looked at
+	const Unit unit = unit_of(cfg.ww, esize, iq);
 	if (log2r)	// the decimating scan (cordic_fm_mix_decim.hip): n is whole groups
-		return tnco::finish(launch_fm_mix_decim_scan(cfg.ww, cfg.nlive, dx.n, esize, grid,
-			lds, stream, kp, da, a, log2r));
-	const bool done = with_unit(unit_of(cfg.ww, esize), [&](auto lj, auto io) {
-		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
-			hipLaunchKernelGGL((fm_mix_xydir<decltype(lj)::value, decltype(nl)::value,
-				decltype(io)>), dim3(grid), dim3(kBlock), lds, st, kp, da, a);
-		});
+		return tnco::finish(launch_fm_mix_decim_scan(unit, cfg.nlive, dx.n, grid, lds,
+			stream, kp, da, a, log2r));
+	if (unit == kUnitC16)	// (cordic_fm_mix_c16.o)
+		return tnco::finish(launch_fm_mix_scan_c16(cfg.nlive, dx.n, grid, lds, stream, kp,
+			da, a, 0));
+	const bool done = with_unit(unit, [&](auto lj, auto io) {
+		return launch_scan<decltype(lj)::value, decltype(io)>(cfg.nlive, dx.n, grid, lds,
+			st, kp, da, a);
 	});
 	return tnco::finish(done);
 }
@@ -258,5 +313,16 @@ int launch_fmx_narrow(size_t n, const int32_t *d_wox, const int32_t *d_woy,
 		static_cast<hipStream_t>(stream), n, d_wox, d_woy, d_ox, d_oy);
 	return tnco::finish(true);
 }
+
+int launch_fmx_interleave_c16(size_t m, const int16_t *d_ox, const int16_t *d_oy,
+		int16_t *d_oiq, void *stream)
+{
+	using namespace fmx;
+	(void)hipGetLastError();
+	hipLaunchKernelGGL(fmx_interleave_c16, dim3(elementwise_grid(m)), dim3(kBlock), 0,
+		static_cast<hipStream_t>(stream), m, d_ox, d_oy, reinterpret_cast<uint32_t *>(d_oiq));
+	return tnco::finish(true);
+}
+#endif // CORDIC_FMX_C16
 
 } // namespace cordic_amd

@@ -59,6 +59,7 @@
 //   fm_mix_xydir<30, N> after   92   98   95   95  102  103  103
 //   fm_mixbank_xydir<30, N>    115  117  116  116  115  124  124
 //   ... <30, N, Io16>          111  113  112  112  112  120  120
+//   ... <30, N, IoC16io>       111  113  112  112  111  112  112
 //   span_reduce<MixSpan, 256>   42 (32 bytes of static LDS)
 // The single call's counts did not move.  The bank's kernel takes 12 .. 23
 // more: six array addresses, the sample count and the indices arrive per span
@@ -73,7 +74,11 @@
 // addresses, which the host's cutter advances by 2 or 4 bytes per sample, and
 // span_reduce reads tuning words only.  The table was taken again with
 // the parameter in place: the 32-bit rows did not move, and no Io16 instance
-// (LJ = 30 only, see fmx_is_fused16) spills.
+// (LJ = 30 only, see fmx_is_fused16) spills.  IoC16io: a bank of interleaved
+// jobs (cordic_mixbank_create_c16) -- a span's x is its d_iq, its ox its d_oiq,
+// y and oy are 0 (span_place); the instances are in cordic_fm_mix_bank_c16.o,
+// this source compiled with -DCORDIC_FMX_C16, behind launch_fmx_bank_walk_c16
+// (cordic_fm_mix_bank.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -135,11 +140,36 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_xydir(CoreParams kp, DirArg
 	}
 }
 
+// launch 2 for one <LJ, container>; false: no instance for nlive
+template <int LJ, typename IO>
+static bool launch_walk(int nlive, int ngroups, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const MixSpan *d_spans, uint32_t nspans,
+		const uint32_t *d_start, const uint32_t *d_part, uint32_t xw)
+{
+	return with_stages(nlive, ngroups, [&](auto nl) {
+		hipLaunchKernelGGL((fm_mixbank_xydir<LJ, decltype(nl)::value, IO>), dim3(grid),
+			dim3(kBlock), lds, st, kp, da, d_spans, nspans, d_start, d_part, xw);
+	});
+}
+
 } // namespace fmx
 
+#ifdef CORDIC_FMX_C16
+// This object (cordic_fm_mix_bank_c16.o): the kernel's <30, N, IoC16io>
+// instances and their launcher, nothing of the host side.
+bool launch_fmx_bank_walk_c16(int nlive, int ngroups, unsigned grid, size_t lds,
+		void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
+		const MixSpan *d_spans, uint32_t nspans, const uint32_t *d_start,
+		const uint32_t *d_part, uint32_t xw, uint32_t log2r)
+{
+	(void)log2r;
+	return fmx::launch_walk<30, fmx::IoC16io>(nlive, ngroups, grid, lds,
+		static_cast<hipStream_t>(stream), kp, da, d_spans, nspans, d_start, d_part, xw);
+}
+#else
 int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInfo &dx,
 		const MixSpan *d_spans, uint32_t nspans, uint32_t *d_start,
-		uint32_t *d_part, int cus, bool io16, void *stream, uint32_t log2r)
+		uint32_t *d_part, int cus, bool io16, void *stream, uint32_t log2r, bool iq)
 {
 	using namespace fmx;
 	(void)hipGetLastError();	// (a stale error is not this call's)
@@ -156,18 +186,20 @@ int launch_fmx_bank(const cordic_config &cfg, const uint32_t *d_dir, const DxInf
 	const unsigned grid = g.walk;
 	const DirArgs da{d_dir, dx};
 	const CoreParams kp = make_params_jobs(cfg);
+	// iq: the spans' x is d_iq, their ox d_oiq, y and oy are 0 (span_place)
+	const Unit unit = unit_of(cfg.ww, io16 ? 2 : 4, iq);
 	if (log2r)	// a decimating bank's walk (cordic_fm_mix_bank_decim.hip)
-		return tnco::finish(launch_fmx_bank_decim_walk(cfg.ww, cfg.nlive, dx.n, io16, grid,
-			lds, stream, kp, da, d_spans, nspans, d_start, d_part, xw, log2r));
-	const bool done = with_unit(unit_of(cfg.ww, io16 ? 2 : 4), [&](auto lj, auto io) {
-		return with_stages(cfg.nlive, dx.n, [&](auto nl) {
-			hipLaunchKernelGGL((fm_mixbank_xydir<decltype(lj)::value,
-				decltype(nl)::value, decltype(io)>), dim3(grid), dim3(kBlock), lds, st,
-				kp, da, d_spans, nspans, (const uint32_t *)d_start,
-				(const uint32_t *)d_part, xw);
-		});
+		return tnco::finish(launch_fmx_bank_decim_walk(unit, cfg.nlive, dx.n, grid, lds,
+			stream, kp, da, d_spans, nspans, d_start, d_part, xw, log2r));
+	if (unit == kUnitC16)	// (cordic_fm_mix_bank_c16.o)
+		return tnco::finish(launch_fmx_bank_walk_c16(cfg.nlive, dx.n, grid, lds, stream,
+			kp, da, d_spans, nspans, d_start, d_part, xw, 0));
+	const bool done = with_unit(unit, [&](auto lj, auto io) {
+		return launch_walk<decltype(lj)::value, decltype(io)>(cfg.nlive, dx.n, grid, lds,
+			st, kp, da, d_spans, nspans, d_start, d_part, xw);
 	});
 	return tnco::finish(done);
 }
+#endif // CORDIC_FMX_C16
 
 } // namespace cordic_amd

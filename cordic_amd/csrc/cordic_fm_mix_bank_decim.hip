@@ -7,6 +7,9 @@
 // of R -- so the loop runs over [0, d.n) and writes [0, d.n >> k) of them.
 // Launch 1, the grids and the span table are launch_fmx_bank's, which calls
 // this unit for a bank with k > 0.  k is one per bank, a kernel argument.
+// The <30, N, IoC16io> instances (cordic_mixbank_create_decim_c16) are in
+// cordic_fm_mix_bank_decim_c16.o, this source compiled with -DCORDIC_FMX_C16;
+// their registers stand in the table of cordic_fm_mix_decim.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -60,22 +63,49 @@ __global__ __launch_bounds__(kBlock) void fm_mixbank_decim_xydir(CoreParams kp, 
 	}
 }
 
+// launch 2 for one <LJ, container>; false: no instance for nlive
+template <int LJ, typename IO>
+static bool launch_walk(int nlive, int ngroups, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const MixSpan *d_spans, uint32_t nspans,
+		const uint32_t *d_start, const uint32_t *d_part, uint32_t xw, uint32_t log2r)
+{
+	return with_stages(nlive, ngroups, [&](auto nl) {
+		hipLaunchKernelGGL((fm_mixbank_decim_xydir<LJ, decltype(nl)::value, IO>),
+			dim3(grid), dim3(kBlock), lds, st, kp, da, d_spans, nspans, d_start, d_part,
+			xw, log2r);
+	});
+}
+
 } // namespace fmx
 
-bool launch_fmx_bank_decim_walk(int ww, int nlive, int ngroups, bool io16, unsigned grid,
+#ifdef CORDIC_FMX_C16
+// This object (cordic_fm_mix_bank_decim_c16.o): the kernel's <30, N, IoC16io>
+// instances and their launcher.
+bool launch_fmx_bank_decim_walk_c16(int nlive, int ngroups, unsigned grid, size_t lds,
+		void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
+		const MixSpan *d_spans, uint32_t nspans, const uint32_t *d_start,
+		const uint32_t *d_part, uint32_t xw, uint32_t log2r)
+{
+	return fmx::launch_walk<30, fmx::IoC16io>(nlive, ngroups, grid, lds,
+		static_cast<hipStream_t>(stream), kp, da, d_spans, nspans, d_start, d_part, xw,
+		log2r);
+}
+#else
+bool launch_fmx_bank_decim_walk(int unit, int nlive, int ngroups, unsigned grid,
 		size_t lds, void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
 		const MixSpan *d_spans, uint32_t nspans, const uint32_t *d_start,
 		const uint32_t *d_part, uint32_t xw, uint32_t log2r)
 {
 	using namespace fmx;
 	hipStream_t st = static_cast<hipStream_t>(stream);
-	return with_unit(unit_of(ww, io16 ? 2 : 4), [&](auto lj, auto io) {
-		return with_stages(nlive, ngroups, [&](auto nl) {
-			hipLaunchKernelGGL((fm_mixbank_decim_xydir<decltype(lj)::value,
-				decltype(nl)::value, decltype(io)>), dim3(grid), dim3(kBlock), lds, st,
-				kp, da, d_spans, nspans, d_start, d_part, xw, log2r);
-		});
+	if (unit == kUnitC16)	// (cordic_fm_mix_bank_decim_c16.o)
+		return launch_fmx_bank_decim_walk_c16(nlive, ngroups, grid, lds, stream, kp, da,
+			d_spans, nspans, d_start, d_part, xw, log2r);
+	return with_unit((Unit)unit, [&](auto lj, auto io) {
+		return launch_walk<decltype(lj)::value, decltype(io)>(nlive, ngroups, grid, lds, st,
+			kp, da, d_spans, nspans, d_start, d_part, xw, log2r);
 	});
 }
+#endif // CORDIC_FMX_C16
 
 } // namespace cordic_amd

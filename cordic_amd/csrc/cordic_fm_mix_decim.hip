@@ -43,16 +43,25 @@
 //   fm_mix_decim_xydir<30, N>      97   99   96   96  103  104  104
 //   fm_mix_xydir<30, N, Io16>      92   96   92   92   99  100  100
 //   fm_mix_decim_xydir<.., Io16>   95   97   94   94  101  102  102
+//   fm_mix_xydir<30, N, IoC16io>   90   94   91   91   90   93   93
+//   fm_mix_decim_...<.., IoC16io>  91   95   92   92   91   94   94
 //   fm_mixbank_xydir<29, N>       114  120  114  114  115  122  122
 //   fm_mixbank_decim_xydir<29, N> 119  121  118  118  125  126  126
 //   fm_mixbank_xydir<30, N>       115  117  116  116  115  124  124
 //   fm_mixbank_decim_xydir<30, N> 117  119  118  118  124  126  126
 //   fm_mixbank_xydir<.., Io16>    111  113  112  112  112  120  120
 //   fm_mixbank_decim_...<.., Io16> 125 128  126  126  126  128  128
+//   fm_mixbank_xydir<.., IoC16io> 111  113  112  112  111  112  112
+//   fm_mixbank_decim..<.., IoC16io> 112 114 113  113  112  113  113
 //   fmx_decimate<int32 / int16>    18
 // The sum costs -1 .. 5 registers in the single call and 1 .. 15 in the bank;
 // every instance stays within the 128 that hold 4 waves per SIMD, which the
-// grids of both launchers assume, so no occupancy step is crossed.
+// grids of both launchers assume, so no occupancy step is crossed.  The IoC16io
+// rows (interleaved int16 I/Q in and out, the *_c16 mixers; objects of their
+// own, -DCORDIC_FMX_C16, see cordic_fm_mix.hip) store ONE dword (I | Q << 16)
+// per decimated sample where Io16 has two 2-byte stores (k = 1: one 8-byte store
+// of the lane's two); the decimating bank's instances take 12 .. 15 registers
+// fewer than Io16's, which sit at the edge of 128.
 //
 // Knobs: CORDIC_FMX_MAX_BLOCKS caps the grid as for the mixer
 // (cordic_fm_mix.hip).  CORDIC_FMXD_FALLBACK=1 (cordic_abi_fm.cpp; a test and A/B
@@ -110,6 +119,18 @@ __global__ __launch_bounds__(kBlock) void fm_mix_decim_xydir(CoreParams kp, DirA
 		*a.acc = carry;
 }
 
+// launch 2 for one <LJ, container>; false: no instance for nlive
+template <int LJ, typename IO>
+static bool launch_scan(int nlive, int ngroups, unsigned grid, size_t lds, hipStream_t st,
+		const CoreParams &kp, const DirArgs &da, const FmxArgs &a, uint32_t log2r)
+{
+	return with_stages(nlive, ngroups, [&](auto nl) {
+		hipLaunchKernelGGL((fm_mix_decim_xydir<LJ, decltype(nl)::value, IO>), dim3(grid),
+			dim3(kBlock), lds, st, kp, da, a, log2r);
+	});
+}
+
+#ifndef CORDIC_FMX_C16
 // the fallback's decimation: out[j] = floor((in[jR] + .. + in[jR + R - 1]) / R)
 // for both arrays, j < nout
 template <typename T>
@@ -130,20 +151,33 @@ __global__ __launch_bounds__(kBlock) void fmx_decimate(size_t nout, uint32_t log
 	}
 }
 
+#endif // CORDIC_FMX_C16
+
 } // namespace fmx
 
-bool launch_fm_mix_decim_scan(int ww, int nlive, int ngroups, size_t esize, unsigned grid,
+#ifdef CORDIC_FMX_C16
+// This object (cordic_fm_mix_decim_c16.o): the kernel's <30, N, IoC16io>
+// instances and their launcher, nothing of the host side.
+bool launch_fm_mix_decim_scan_c16(int nlive, int ngroups, unsigned grid, size_t lds,
+		void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
+		const fmx::FmxArgs &a, uint32_t log2r)
+{
+	return fmx::launch_scan<30, fmx::IoC16io>(nlive, ngroups, grid, lds,
+		static_cast<hipStream_t>(stream), kp, da, a, log2r);
+}
+#else
+bool launch_fm_mix_decim_scan(fmx::Unit unit, int nlive, int ngroups, unsigned grid,
 		size_t lds, void *stream, const dev::CoreParams &kp, const dev::DirArgs &da,
 		const fmx::FmxArgs &a, uint32_t log2r)
 {
 	using namespace fmx;
 	hipStream_t st = static_cast<hipStream_t>(stream);
-	return with_unit(unit_of(ww, esize), [&](auto lj, auto io) {
-		return with_stages(nlive, ngroups, [&](auto nl) {
-			hipLaunchKernelGGL((fm_mix_decim_xydir<decltype(lj)::value,
-				decltype(nl)::value, decltype(io)>), dim3(grid), dim3(kBlock), lds, st,
-				kp, da, a, log2r);
-		});
+	if (unit == kUnitC16)	// (cordic_fm_mix_decim_c16.o)
+		return launch_fm_mix_decim_scan_c16(nlive, ngroups, grid, lds, stream, kp, da, a,
+			log2r);
+	return with_unit(unit, [&](auto lj, auto io) {
+		return launch_scan<decltype(lj)::value, decltype(io)>(nlive, ngroups, grid, lds, st,
+			kp, da, a, log2r);
 	});
 }
 
@@ -167,5 +201,6 @@ int launch_fmx_decimate(size_t n, uint32_t log2r, size_t esize, const void *d_tx
 			static_cast<int32_t *>(d_ox), static_cast<int32_t *>(d_oy));
 	return tnco::finish(true);
 }
+#endif // CORDIC_FMX_C16
 
 } // namespace cordic_amd

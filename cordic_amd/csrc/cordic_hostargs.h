@@ -62,16 +62,22 @@ inline bool outputs_overlap(const Range (&out)[NOUT], const Range (&in)[NIN],
 // two output arrays hold n >> out_shift elements (the decimating mixer).
 // interleaved: the two sample inputs are ONE array at d_x, I and Q by turns --
 // there, on the grid of a complex sample (2 * esize), 2 * esize * n bytes --
-// and d_y is not looked at (the *_c16 receivers); the outputs stay two arrays.
+// and d_y is not looked at (the *_c16 receivers); the outputs stay two arrays
+// unless out_interleaved says the same of them (the *_c16 mixers): ONE array at
+// d_o0 on the grid of a complex sample, 2 * esize * (n >> out_shift) bytes, and
+// d_o1 is not looked at.
 inline bool iq_call_ok(size_t n, const void *d_acc, const void *d_last,
 		const void *d_fcw, const void *d_pm, const void *d_x, const void *d_y,
 		const void *d_o0, const void *d_o1, size_t esize, const void *d_work,
-		size_t work_bytes, unsigned out_shift = 0, bool interleaved = false)
+		size_t work_bytes, unsigned out_shift = 0, bool interleaved = false,
+		bool out_interleaved = false)
 {
 	if (interleaved)
 		d_y = nullptr;
-	if (!d_fcw || !d_x || (!d_y && !interleaved) || !d_o0 || !d_o1 || !d_work
-			|| n > (~(size_t)0 >> 4))
+	if (out_interleaved)
+		d_o1 = nullptr;
+	if (!d_fcw || !d_x || (!d_y && !interleaved) || !d_o0 || (!d_o1 && !out_interleaved)
+			|| !d_work || n > (~(size_t)0 >> 4))
 		return false;
 	const uintptr_t words = reinterpret_cast<uintptr_t>(d_fcw)
 		| reinterpret_cast<uintptr_t>(d_pm) | reinterpret_cast<uintptr_t>(d_acc)
@@ -81,10 +87,12 @@ inline bool iq_call_ok(size_t n, const void *d_acc, const void *d_last,
 		| reinterpret_cast<uintptr_t>(d_o1);
 	if ((words & 3u) || (samples & (esize - 1))
 			|| (reinterpret_cast<uintptr_t>(d_work) & 15u)
-			|| (interleaved && (reinterpret_cast<uintptr_t>(d_x) & (2 * esize - 1))))
+			|| (interleaved && (reinterpret_cast<uintptr_t>(d_x) & (2 * esize - 1)))
+			|| (out_interleaved && (reinterpret_cast<uintptr_t>(d_o0) & (2 * esize - 1))))
 		return false;
 	const size_t nout = n >> out_shift;
-	const Range out[5] = {range_of(d_o0, nout * esize), range_of(d_o1, nout * esize),
+	const Range out[5] = {range_of(d_o0, nout * esize * (out_interleaved ? 2 : 1)),
+		range_of(d_o1, nout * esize),
 		range_of(d_acc, 4), range_of(d_last, 4), range_of(d_work, work_bytes)};
 	const Range in[4] = {range_of(d_fcw, n * 4), range_of(d_pm, n * 4),
 		range_of(d_x, n * esize * (interleaved ? 2 : 1)), range_of(d_y, n * esize)};

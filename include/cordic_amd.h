@@ -1843,6 +1843,107 @@ int	cordic_rxbank_create_decim_c16(const cordic_plan *plan, const cordic_config 
 		uint32_t log2r, size_t njobs, const cordic_fmrx_job_c16 *jobs,
 		cordic_rxbank **bank);
 
+/* FM mixer on INTERLEAVED int16 I/Q, in and out: single, decimating, banks.
+ *
+ * The digital down-converter for a caller who needs the tuned (or decimated)
+ * I/Q itself, in the form it arrived in.  d_iq holds n complex samples as 2 n
+ * shorts, x_i = d_iq[2 i], y_i = d_iq[2 i + 1]; d_oiq receives n >> k complex
+ * samples the same way, and d_oiq[2 j], d_oiq[2 j + 1] and the word *d_acc are,
+ * bit for bit, what the split-array twin writes to d_oxval[j], d_oyval[j] and
+ * *d_acc on d_xval[i] = d_iq[2 i], d_yval[i] = d_iq[2 i + 1]:
+ *   cordic_plan_fm_mix_c16          cordic_plan_fm_mix16
+ *   cordic_plan_fm_mix_decim_c16    cordic_plan_fm_mix_decim16
+ *   cordic_mixbank_create_c16       cordic_mixbank_create16
+ *   cordic_mixbank_create_decim_c16 cordic_mixbank_create_decim16
+ * without the caller's split pass in front and interleave pass behind (two
+ * launches and 8 + 8 / R bytes per sample).  Everything the twins document
+ * carries over: phase0 is added by every call; consecutive calls that share a
+ * d_acc give the bits of one call (the decimating forms: cut at multiples of
+ * R); a captured call replayed continues; n == 0 is CORDIC_OK with nothing
+ * touched; k = 0 is the plain form (the same bits, launches and workspace); the
+ * decimating forms need n % R == 0 and k <= 8.
+ *
+ * Status codes: those of the *16 twin, in its order -- CORDIC_ERR_ARGS for a
+ * NULL plan, CORDIC_ERR_MODE, CORDIC_ERR_CONTAINER unless IW <= 16 and OW <=
+ * 16, the checks of k and n, n == 0, the pointer checks.  Those differ in one
+ * place: d_iq and d_oiq replace the four sample pointers.  Both must be
+ * non-NULL and sit on the 4-byte grid, one complex sample -- ANY 4-byte
+ * alignment is served, not only 16.  Their byte ranges are 4 n and 4 (n >> k);
+ * no output (d_oiq, the word at d_acc, d_work) may overlap an input or another
+ * output, which is found on the host with nothing written.  In-place is not
+ * offered: d_oiq over d_iq is CORDIC_ERR_ARGS.
+ *
+ * Two paths, identical bits:
+ *   fused     exactly where the twin is (cordic_plan_fm_mix_info answers 1 and
+ *             WW < 35); cordic_plan_fm_mix_c16_info reports *fused = 1 and
+ *             *tile = 1024 there, 0 and 0 elsewhere.  The twin's two launches,
+ *             grid, spans and workspace.  In the second a lane gets its four
+ *             complex samples by ONE 16-byte load at d_iq + 2 i, separates the
+ *             halves in registers, and stores (uint16_t)I | (uint32_t)Q << 16
+ *             per sample: k = 0, ONE 16-byte store of four at d_oiq + 2 i (the
+ *             last, partial vector dword by dword); k = 1, one 8-byte store of
+ *             its two outputs; k >= 2, one dword per output, from the group's
+ *             last lane.  Nothing at or behind complex sample n is read, nothing
+ *             at or behind complex sample n >> k is written.  Legal inside a
+ *             stream capture; no block waits for another.  The twin's bytes
+ *             per sample.
+ *   fallback  every other plan the twin accepts: one small kernel splits d_iq
+ *             into two int16 arrays inside d_work, the *16 twin runs from them
+ *             into two more, one small kernel interleaves those into d_oiq.
+ *             Nothing is allocated.  CORDIC_FMXD_FALLBACK=1 forces it for
+ *             cordic_plan_fm_mix_decim_c16, as for its twin; banks ignore it.
+ *
+ * d_work: at least cordic_plan_fm_mix_c16_workspace(plan, n) bytes
+ * (cordic_plan_fm_mix_decim_c16_workspace(plan, n, log2r)).  Pure host
+ * functions: 0 where the call would fail and for n == 0, a multiple of 16,
+ * non-decreasing in n (over the multiples of R).  Fused: the twin's workspace.
+ * Otherwise [the twin's workspace | x | y of n shorts | ox | oy of n >> k
+ * shorts], each part on the 16-byte grid: at most the twin's + 4 n + 4 (n >> k)
+ * + 64 bytes.
+ *
+ * Banks: cordic_mixbank_create_c16 / _create_decim_c16 take jobs of
+ * cordic_fmmix_job_c16 and follow every rule of cordic_mixbank_create16 /
+ * _create_decim16 in its order, with d_iq and d_oiq in the place of the four
+ * sample pointers: on the 4-byte grid, 4 n and 4 (n >> k) bytes in the sorted
+ * overlap check.  The result is an ordinary cordic_mixbank: _run, _info and
+ * _destroy serve it unchanged, and cordic_mixbank_info tells fused from one by
+ * one (run then loops the single *_c16 call over the jobs with a workspace
+ * allocated at create for the longest job).
+ * Measured: profiles/r26/fm_mix_c16.txt -- best against best, 0.97 .. 1.00 of the
+ * *16 twins' rate (>= 0.97 required; the decimating single call 0.99 .. 1.00: the one
+ * dword per decimated sample does not show in its rate) and 1.26 .. 1.74 of the twin
+ * with a split launch in front and an interleave launch behind (> 1.00
+ * required).  MISSED in the second of the file's two runs: the plain call on
+ * cfg1's core, 0.967 of cordic_plan_fm_mix16 (1.00 in the first run); every
+ * other requirement held in both.
+ */
+int	cordic_plan_fm_mix_c16_info(const cordic_plan *plan, int32_t *fused, int32_t *tile);
+size_t	cordic_plan_fm_mix_c16_workspace(const cordic_plan *plan, size_t n);
+int	cordic_plan_fm_mix_c16(const cordic_plan *plan, size_t n,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_iq, int16_t *d_oiq, void *d_work,
+		void *stream);
+size_t	cordic_plan_fm_mix_decim_c16_workspace(const cordic_plan *plan, size_t n,
+		uint32_t log2r);
+int	cordic_plan_fm_mix_decim_c16(const cordic_plan *plan, size_t n, uint32_t log2r,
+		const uint32_t *d_fcw, const uint32_t *d_pm, uint32_t phase0,
+		uint32_t *d_acc, const int16_t *d_iq, int16_t *d_oiq, void *d_work,
+		void *stream);
+typedef struct cordic_fmmix_job_c16 {
+	const uint32_t *d_fcw;		/* offset  0: n words                   */
+	const uint32_t *d_pm;		/* offset  8: n words, or NULL          */
+	const int16_t *d_iq;		/* offset 16: 2 n shorts: I0 Q0 I1 Q1 ..*/
+	int16_t	*d_oiq;			/* offset 24: 2 (n >> k) shorts         */
+	uint32_t *d_acc;		/* offset 32: optional device word      */
+	uint64_t n;			/* offset 40: complex samples; 0 allowed*/
+	uint32_t phase0;		/* offset 48                            */
+	uint32_t reserved;		/* offset 52: 0                         */
+} cordic_fmmix_job_c16;			/* 56 bytes                             */
+int	cordic_mixbank_create_c16(const cordic_plan *plan, size_t njobs,
+		const cordic_fmmix_job_c16 *jobs, cordic_mixbank **bank);
+int	cordic_mixbank_create_decim_c16(const cordic_plan *plan, uint32_t log2r,
+		size_t njobs, const cordic_fmmix_job_c16 *jobs, cordic_mixbank **bank);
+
 /* ------------------------------------------- clocked view (streaming shim)
  *
  * For benches that step the Verilated PIPELINED cores clock by clock with
